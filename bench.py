@@ -13,12 +13,29 @@ replay. Weights are random (no checkpoints offline) but of the real
 architecture and size, generated in HBM before timing. The prompt is 13
 synthetic token ids (the README prompt's length) hydrated first.
 
-At N = 1 fp16 the line also carries `fp8`: config 3, the same decode with E5M2
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, write the outputs (`--dump-outputs DIR`) and print the line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the workload and
+the bytes/token `step_roofline`, which is arithmetic on the timed figure).
+
+`--full` adds every other measurement to the same line: the dominant kernel's
+`roofline` (HIP-event time, same-process streaming envelope, committed
+FETCH_SIZE traffic), `kernels_per_token`, `gpu_state`, `long_context`, the CPU
+baselines and, at N = 1 fp16, `fp8`: config 3, the same decode with E5M2
 weights (a child run of this script; `--no-fp8` skips it), and `prefill`:
 config 4 (Llama-3.2-3B, one 4096-position `-m perplexity` pass as a batched
-MFMA prefill) with its own MFMA roofline (`--no-prefill` skips it).
+MFMA prefill) with its own MFMA roofline (`--no-prefill` skips it). The
+`--no-*` options only trim a `--full` run.
+
+`--dump-outputs DIR` writes what the timed greedy loop handed back at its last
+step as DIR/<name>.npy: `logits` (float32, the last timed step's logits; one
+GPU or replicas), `tokens` (float64, the greedy token ids since the first
+generated token: warm-up then the timed steps, the first 65536 at most) and
+`last_step` (float64, [token, position] after the last timed step). Weights,
+prompt and seeds are fixed, so the same arguments give the same inputs.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp16|fp8]
+                       [--full] [--dump-outputs DIR]
 With --gpus N > 1 and no WORLD_SIZE in the environment, the script starts N
 rank processes itself (before any GPU call); under torch.distributed.run each
 rank reads RANK / LOCAL_RANK / WORLD_SIZE. Rank 0 prints ONE JSON line.
@@ -45,6 +62,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--model", default="mistral-7b")
     ap.add_argument("--dtype", default="fp16", choices=["fp16", "fp8"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: kernel roofline, envelope, gpu state, "
+                         "fp8, long-context and prefill legs, CPU baselines (the --no-* options trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (logits, tokens, last_step) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bounded CPU-baseline sample budget")
     ap.add_argument("--kernel-iters", type=int, default=64)
@@ -490,7 +513,7 @@ def fp8_leg(args):
     this script whose JSON line is parsed. Started BEFORE this process makes any GPU call (a
     child of a process holding the GPU is not started here)."""
     try:
-        cmd = [sys.executable, os.path.abspath(__file__), "--dtype", "fp8", "--steps", str(args.steps),
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--dtype", "fp8", "--steps", str(args.steps),
                "--warmup", str(args.warmup), "--no-cpu-baseline", "--no-prefill", "--no-gpu-state",
                "--kernel-iters", str(args.kernel_iters)] + (["--no-envelope"] if args.no_envelope else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -538,9 +561,9 @@ def main():
 
     profiled = any(k.startswith("ROCPROF") for k in os.environ)
     fp8_leg_out = None
-    if world == 1 and args.dtype == "fp16" and not args.no_fp8 and not profiled:
+    if args.full and world == 1 and args.dtype == "fp16" and not args.no_fp8 and not profiled:
         fp8_leg_out = fp8_leg(args)  # before any GPU call of this process
-    state = gpu_state() if local_rank == 0 and not (args.no_gpu_state or profiled) else None
+    state = gpu_state() if args.full and local_rank == 0 and not (args.no_gpu_state or profiled) else None
     from yalm_amd import models as M
     from yalm_amd import runtime
 
@@ -568,7 +591,8 @@ def main():
 
     def timed_decode(dec, tp):
         """Hydrate the prompt, warm up, then time exactly args.steps greedy tokens
-        between barrier + sync points; (max-over-ranks seconds, pos0, pos1, ranks agree)."""
+        between barrier + sync points; (max-over-ranks seconds, pos0, pos1, ranks agree,
+        the arrays --dump-outputs writes or None)."""
         prompt = [(7 * i + 1) % cfg.vocab_size for i in range(PROMPT_LEN)]
         for pos, t in enumerate(prompt[:-1]):
             dec.forward(t, pos, runtime.HYDRATE_KV_CACHE)
@@ -594,6 +618,14 @@ def main():
         elapsed = t1 - t0
         tok1, pos1 = dec.device_step()
         assert pos1 - pos0 == args.steps, (pos0, pos1)
+        dump = None
+        if args.dump_outputs and rank == 0:
+            import numpy as np
+
+            dump = {"tokens": np.asarray(dec.device_tokens(), np.float64),
+                    "last_step": np.asarray([tok1, pos1], np.float64)}
+            if not tp:  # under tensor parallelism the greedy step keeps only this rank's vocabulary slice
+                dump["logits"] = dec.get_logits().astype(np.float32)
         agree = None
         if dist is not None:
             # every rank's whole greedy sequence since generate_greedy (first token, warm-up,
@@ -607,7 +639,7 @@ def main():
             elapsed = max(v[0] for v in allv)
             if tp:  # every rank must have produced the same token sequence
                 agree = len({(v[1], v[2]) for v in allv}) == 1
-        return elapsed, pos0, pos1, agree
+        return elapsed, pos0, pos1, agree, dump
 
     fallback = None
     result = None
@@ -645,27 +677,43 @@ def main():
         dm.close()
         return
 
-    elapsed, pos0, pos1, agree = result
+    elapsed, pos0, pos1, agree, dump = result
 
-    # ---- roofline of the dominant kernel: the W1/W3 GEMV + SiLU-GLU (52.9% of the bytes)
-    wb = M.DTYPE_BYTES[cfg.weight_dtype]
-    hid_local = cfg.hidden_dim // tp_size
-    KID = 3
-    kern_bytes = 2 * hid_local * cfg.dim * wb + 2 * cfg.dim * 4 + hid_local * 4
-    wt = "WF16" if args.dtype == "fp16" else "WF8"
-    avg_ms = dec.time_kernel(KID, args.kernel_iters)
-    achieved = kern_bytes / (avg_ms * 1e-3) / 1e9
-    kname = dec.kernel_name(KID)
-    traffic, traffic_src = pmc_traffic((f"gemv_rb_kernel<{wt}", "PGlu"))
-    exch_us = None
-    kernels_per_token = graph_kernels(dec)
-    if tp and tp_size > 1:
-        exch_us = dec.time_kernel(6, args.kernel_iters) * 1e3
-    env_ms = None
-    if not args.no_envelope:
-        if dist is not None:
-            dist.barrier()
-        env_ms = runtime.stream_envelope(kern_bytes, 16)
+    roofline = exch_us = kernels_per_token = None
+    if args.full:
+        # ---- roofline of the dominant kernel: the W1/W3 GEMV + SiLU-GLU (52.9% of the bytes)
+        wb = M.DTYPE_BYTES[cfg.weight_dtype]
+        hid_local = cfg.hidden_dim // tp_size
+        KID = 3
+        kern_bytes = 2 * hid_local * cfg.dim * wb + 2 * cfg.dim * 4 + hid_local * 4
+        wt = "WF16" if args.dtype == "fp16" else "WF8"
+        avg_ms = dec.time_kernel(KID, args.kernel_iters)
+        achieved = kern_bytes / (avg_ms * 1e-3) / 1e9
+        kname = dec.kernel_name(KID)
+        traffic, traffic_src = pmc_traffic((f"gemv_rb_kernel<{wt}", "PGlu"))
+        kernels_per_token = graph_kernels(dec)
+        if tp and tp_size > 1:
+            exch_us = dec.time_kernel(6, args.kernel_iters) * 1e3
+        env_ms = None
+        if not args.no_envelope:
+            if dist is not None:
+                dist.barrier()
+            env_ms = runtime.stream_envelope(kern_bytes, 16)
+        roofline = {
+            "bound": "hbm",
+            "kernel": kname,
+            "avg_launch_us": round(avg_ms * 1e3, 3),
+            "algorithmic_bytes_per_launch": int(kern_bytes),
+            "achieved": round(achieved, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "envelope_us": round(env_ms * 1e3, 3) if env_ms else None,
+            "envelope_gbs": round(kern_bytes / (env_ms * 1e-3) / 1e9, 1) if env_ms else None,
+            "frac_of_envelope": round(env_ms / avg_ms, 4) if env_ms else None,
+        }
 
     toks = args.steps * (1 if tp else world)
     value = toks / elapsed
@@ -710,27 +758,13 @@ def main():
             "unit": "GB/s",
             "frac": round(per_gpu_gbs / HBM_PEAK_GBS, 4),
         },
-        "roofline": {
-            "bound": "hbm",
-            "kernel": kname,
-            "avg_launch_us": round(avg_ms * 1e3, 3),
-            "algorithmic_bytes_per_launch": int(kern_bytes),
-            "achieved": round(achieved, 1),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": traffic,
-            "traffic_source": traffic_src,
-            "envelope_us": round(env_ms * 1e3, 3) if env_ms else None,
-            "envelope_gbs": round(kern_bytes / (env_ms * 1e-3) / 1e9, 1) if env_ms else None,
-            "frac_of_envelope": round(env_ms / avg_ms, 4) if env_ms else None,
-        },
+        "roofline": roofline,
         "gpu_state": state,
         "cpu_baseline": None,
     }
     out["kernels_per_token"] = kernels_per_token
     if tp and tp_size > 1:
-        out["tp"] = tp_info(mode, exch_us, kernels_per_token, cfg, agree)
+        out["tp"] = tp_info(mode, exch_us, kernels_per_token, cfg, agree) if args.full else {"ranks_agree": agree}
     if cu_part is not None:
         out["n_gpus"] = 1
         out["config"]["parallelism"] += "-rehearsal"
@@ -740,7 +774,7 @@ def main():
     if fallback:
         out["fallback"] = fallback
     dec.close()
-    if mode == "single" and args.dtype == "fp16" and not args.no_long:
+    if args.full and mode == "single" and args.dtype == "fp16" and not args.no_long:
         try:  # decode at long context (kv_len 4096, sink regime) on the same weights
             out["long_context"] = long_context_leg(runtime, M, cfg, dm, steps=args.long_steps,
                                                    kernel_iters=args.kernel_iters)
@@ -766,19 +800,21 @@ def main():
                     dec.close()
                     dm.close()
                 raise err2 or RuntimeError("the IPC decoder failed on another rank")
-            e2, _, _, agree2 = timed_decode(dec, True)
-            k2 = graph_kernels(dec)
-            ex2 = dec.time_kernel(6, args.kernel_iters) * 1e3
+            e2, _, _, agree2, dump2 = timed_decode(dec, True)
+            k2 = graph_kernels(dec) if args.full else None
+            ex2 = dec.time_kernel(6, args.kernel_iters) * 1e3 if args.full else None
             out["tp_ipc"] = {"value": round(args.steps / e2, 3), "ms_per_step": round(e2 / args.steps * 1e3, 4),
-                             "exchange_us": round(ex2, 3), "kernels_per_token": k2, "ranks_agree": agree2}
+                             "exchange_us": round(ex2, 3) if args.full else None, "kernels_per_token": k2,
+                             "ranks_agree": agree2}
             dec.close()
             dm.close()
             if agree2 and e2 < elapsed:
                 # the line's value is the faster measured transport (both measured in this run,
                 # same workload, same barriers and max-over-ranks clock); the other stays beside it
                 out["tp_rccl"] = {"value": out["value"], "ms_per_step": out["ms_per_step"],
-                                  "exchange_us": out["tp"]["exchange_us"],
+                                  "exchange_us": out["tp"].get("exchange_us"),
                                   "kernels_per_token": out["kernels_per_token"], "ranks_agree": out["tp"]["ranks_agree"]}
+                dump = dump2
                 del out["tp_ipc"]
                 out["value"] = round(args.steps / e2, 3)
                 out["ms_per_step"] = round(e2 / args.steps * 1e3, 4)
@@ -787,18 +823,18 @@ def main():
                 out["step_roofline"]["frac"] = round(gbs / HBM_PEAK_GBS, 4)
                 out["config"]["parallelism"] = f"tp{tp_size}-ipc"
                 out["kernels_per_token"] = k2
-                out["tp"] = tp_info("tp-ipc", ex2, k2, cfg, agree2)
+                out["tp"] = tp_info("tp-ipc", ex2, k2, cfg, agree2) if args.full else {"ranks_agree": agree2}
                 out["tp"]["transport"] = "ipc (faster of the two measured)"
         except Exception as e:  # report, never hide
             out["tp_ipc"] = {"error": str(e)[:200]}
     if fp8_leg_out is not None:
         out["fp8"] = fp8_leg_out
-    if world == 1 and args.dtype == "fp16" and not args.no_prefill:
+    if args.full and world == 1 and args.dtype == "fp16" and not args.no_prefill:
         try:  # config 4 beside config 2 (the decoder above is closed: its HBM is free again)
             out["prefill"] = prefill_leg(runtime, M, iters=args.prefill_iters)
         except Exception as e:  # report, never hide
             out["prefill"] = {"error": repr(e)[:300]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_seconds)
         except Exception as e:  # report, never hide
@@ -811,6 +847,12 @@ def main():
             except Exception as e:  # report, never hide
                 out["prefill"]["cpu_baseline"] = {"error": repr(e)[:300]}
     if rank == 0:
+        if dump is not None:
+            import numpy as np
+
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(out), file=real_stdout, flush=True)
     if dist is not None:
         dist.barrier()

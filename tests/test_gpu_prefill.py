@@ -230,7 +230,7 @@ def test_prefill_short_prompt_paths(cfg_name, n):
 
 
 def test_bench_prefill_leg():
-    """bench.py's config-4 leg (the `prefill` object of the default line) on a small
+    """bench.py's config-4 leg (the `prefill` object of the `--full` line) on a small
     model: the fields the driver reads, a finite MFMA rate, and its spot check of the
     prefill's log p against the decode engine within LP_ATOL."""
     import bench

@@ -1,6 +1,6 @@
 """Config 4 of BASELINE.json on its own: Llama-3.2-3B fp16, 4k context, `-m perplexity`
 as ONE batched MFMA prefill (yalm_prefill). Same measurement as the `prefill` object of
-bench.py's default line (bench.prefill_leg), for other models / lengths.
+bench.py's `--full` line (bench.prefill_leg), for other models / lengths.
 
 usage: python tools/bench_prefill.py [--model llama-3.2-3b] [--n 4096] [--iters 3]"""
 import argparse
