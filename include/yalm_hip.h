@@ -44,8 +44,9 @@ typedef struct yalm_stream_s *yalm_stream;
  * 303-327) — scratch buffers, KV caches, per-mode hipGraphs. */
 typedef struct yalm_decoder_s *yalm_decoder;
 
-/* Config (model.h:41-68). Same field meaning; MoE fields are not carried
- * because the reference GPU path asserts on MoE (infer.cu:865-867). */
+/* Config (model.h:41-68). Same field meaning; the mixture-of-experts fields
+ * (model.h:57-59) travel beside it in yalm_moe_config (yalm_decoder_create_moe),
+ * so this struct keeps its layout. */
 typedef struct yalm_config {
 	int dim, hidden_dim, head_dim, n_layers, n_heads, n_kv_heads, vocab_size, max_seq_len;
 	float rope_theta;
@@ -145,7 +146,8 @@ int yalm_get_logits(yalm_decoder d, float *host);
 /* Average device time (ms) of one kernel of the forward, launched eagerly on
  * the decoder's stream `iters` times between HIP events (layers rotated so the
  * weights come from HBM). kernel_id: 0 = QKV GEMV, 1 = attention, 2 = Wo GEMV,
- * 3 = W1/W3 GEMV+GLU, 4 = W2 GEMV, 5 = logits GEMV, 6 = one tensor-parallel
+ * 3 = W1/W3 GEMV+GLU, 4 = W2 GEMV (a mixture-of-experts decoder: the expert launches;
+ * 9 = its router), 5 = logits GEMV, 6 = one tensor-parallel
  * exchange of x (RCCL all-reduce or IPC exchange; collective: every rank calls it
  * with the same iters), 8 = the fused attention + Wo
  * launch (yalm_decoder_attn_wo; each timed launch gets a fresh step epoch, so its
@@ -207,6 +209,33 @@ int yalm_attn_wo_plan(const yalm_config *config, int slots, int *splits, int *gr
  * attention units and mergers, the rest Wo. */
 int yalm_attn_wo_trace(yalm_decoder d, unsigned long long *host, size_t count, int *workgroups,
                        int *attention_workgroups);
+
+/* ---------------- mixture of experts (Mixtral), one GPU ----------------
+ * The reference runs MoE on the CPU only (infer.cpp:100-132, 347-384; its GPU path
+ * asserts, infer.cu:865-867). Per layer: a router launch (rmsnorm(x) . moegate^T, then
+ * the reference's top-k: K rounds of a first-maximum scan, softmax over the selected
+ * logits) leaves the K expert indices and weights in device memory; one W1 | W3 + GLU
+ * launch streams only the selected experts' rows of the stacked tensors; W2 of all
+ * selected experts runs as one launch of row length K * hidden_dim when that fits the
+ * LDS and hidden_dim is a multiple of 64 x the elements of a 16-byte load, else as one
+ * launch per selected expert. 1 <= n_experts_active <= n_experts <= 64. */
+typedef struct yalm_moe_config {
+	int n_experts, n_experts_active;
+} yalm_moe_config;
+/* As yalm_decoder_create; blocks[l].w1 / w3 point at stacked (n_experts, hidden_dim, dim)
+ * tensors, w2 at (n_experts, dim, hidden_dim); moegate: HOST array of n_layers device
+ * pointers, each (n_experts, dim) in the weight dtype. yalm_forward,
+ * yalm_generate_greedy, yalm_enqueue_greedy, yalm_block, yalm_get_x / yalm_set_x,
+ * yalm_graph_kernels and yalm_decoder_set_launch work as on a dense decoder;
+ * yalm_time_kernel ids 3 and 4 time the expert launches (on the layer's most recent
+ * routing), id 9 the router; yalm_prefill returns YALM_ERR_UNSUPPORTED (callers run
+ * position by position). There is no tensor-parallel form. */
+int yalm_decoder_create_moe(const yalm_config *config, const yalm_moe_config *moe, const yalm_model_weights *weights,
+                            const void *const *moegate, yalm_stream s, yalm_decoder *out);
+/* The routing of the most recent forward / yalm_block: experts[n_layers * K] and
+ * weights[n_layers * K] (host, either may be NULL), layer-major, in selection order
+ * (descending logit). YALM_ERR_ARG on a dense decoder. */
+int yalm_moe_routing(yalm_decoder d, int *experts, float *weights);
 
 /* ---------------- tensor parallelism (BASELINE config 5) ----------------
  * Megatron row/column split of one model over tp_size GPUs, one process per
@@ -319,6 +348,14 @@ int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint16_t *vb, co
 /* ffn_cuda: xout = W2 (act(W1 x) * W3 x). */
 int yalm_ffn(float *xout, const float *x, const void *w1, const void *w2, const void *w3, int hidden_dim, int dim,
              int act, int dtype);
+
+/* The MoE FFN of one block without the norm and the residual (host pointers,
+ * synchronous): the router on x, then xout = sum_k weight_k * W2[e_k] (act(W1[e_k] x) *
+ * W3[e_k] x) through the decoder's kernels; experts / weights (n_active each, may be
+ * NULL) receive the routing. */
+int yalm_moe_ffn(float *xout, int *experts, float *weights, const float *x, const void *moegate, const void *w1,
+                 const void *w2, const void *w3, int n_experts, int n_active, int hidden_dim, int dim, int act,
+                 int dtype);
 
 /* Device greedy sampling (sampler.cpp:27-38 sample_argmax: strict '>' scan, the
  * FIRST maximum wins, 0 when nothing exceeds -FLT_MAX): *out = argmax of n host

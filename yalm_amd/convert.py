@@ -7,7 +7,9 @@ with sentencepiece '▁' -> ' ' or GPT-2 byte decoding and NUL -> BEL
 (permute_reverse, convert.py:145-158), f32 norms, weights cast to fp32 /
 fp16 (round-to-nearest-even) / fp8 E5M2 (torch's fp8e5m2_from_fp32_value:
 RNE, >= 2^16 -> inf), tied classifier when ``tie_word_embeddings`` is not
-False (convert.py:200). MoE (Mixtral) checkpoints are out of scope.
+False (convert.py:200). Mixtral checkpoints (convert.py:54-56, 78-80, 188-193): the
+router gate becomes ``moegate``, each layer's experts are stacked along a new
+leading axis, and n_experts / n_experts_active go into the metadata.
 
 Usage: python -m yalm_amd.convert [--dtype fp16] out.yalm hf_dir/
 """
@@ -22,7 +24,7 @@ import numpy as np
 
 from .yalmfile import read_yalm, write_yalm
 
-SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM"]
+SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM"]
 SUPPORTED_DTYPES = ["fp32", "fp16", "fp8"]
 
 
@@ -56,6 +58,9 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
         "norm_type": "rmsnorm",
         "act_type": config["hidden_act"],
     }
+    if arch == "MixtralForCausalLM":
+        md["n_experts"] = config["num_local_experts"]
+        md["n_experts_active"] = config["num_experts_per_tok"]
     # str() of the python value, as convert.py:63-80 does (floats print as 10000.0, 1e-05)
     return {k: str(v) for k, v in md.items()}
 
@@ -183,9 +188,15 @@ def convert(hf_dir: str, out_path: str, dtype: str = "fp16") -> None:
         put(q + "attn.wv.weight", conv(p + "self_attn.v_proj.weight"))
         put(q + "attn.wo.weight", conv(p + "self_attn.o_proj.weight"))
         put(q + "mlp.norm.weight", (_to_f32(src[p + "post_attention_layernorm.weight"]), "F32"))
-        put(q + "mlp.w1.weight", conv(p + "mlp.gate_proj.weight"))
-        put(q + "mlp.w2.weight", conv(p + "mlp.down_proj.weight"))
-        put(q + "mlp.w3.weight", conv(p + "mlp.up_proj.weight"))
+        if md["arch"] == "MixtralForCausalLM":
+            put(q + "moegate.weight", conv(p + "block_sparse_moe.gate.weight"))
+            for key in ("w1", "w2", "w3"):  # experts stacked along a new leading axis
+                parts = [conv(p + f"block_sparse_moe.experts.{e}.{key}.weight") for e in range(int(md["n_experts"]))]
+                put(q + f"mlp.{key}.weight", (np.stack([a for a, _ in parts]), parts[0][1]))
+        else:
+            put(q + "mlp.w1.weight", conv(p + "mlp.gate_proj.weight"))
+            put(q + "mlp.w2.weight", conv(p + "mlp.down_proj.weight"))
+            put(q + "mlp.w3.weight", conv(p + "mlp.up_proj.weight"))
     put("model.norm.weight", (_to_f32(src["model.norm.weight"]), "F32"))
     if config.get("tie_word_embeddings", None) == False:  # noqa: E712 (convert.py:200 semantics: absent -> tied)
         put("model.output.weight", conv("lm_head.weight"))

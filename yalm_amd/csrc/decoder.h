@@ -168,6 +168,12 @@ struct yalm_decoder_s {
 	long long awo_kv_hint = -1;      // kv_len of the forward being enqueued, -1 unknown
 	unsigned long long *awo_gran = nullptr; // [n_layers][q_dim] attention outputs as {value, epoch} granules
 	unsigned *awo_err = nullptr;     // error word of the in-launch waits (bit 0 fused Wo gather, bit 1 attention merger)
+	// mixture of experts (yalm_decoder_create_moe, moe.h): b[l].w1 / w2 / w3 are stacked (n_experts, ...)
+	// tensors, hb holds moe_K * hidden_dim floats; 0 experts = a dense decoder
+	int moe_E = 0, moe_K = 0;
+	std::vector<const void *> moegate; // [n_layers] router weights (n_experts, dim)
+	int *moe_sel = nullptr;            // [n_layers][moe_K] the routing of the most recent forward
+	float *moe_wts = nullptr;          // [n_layers][moe_K]
 };
 
 // ------------------------------------------------------------------ shared helpers

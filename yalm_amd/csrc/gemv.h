@@ -95,6 +95,30 @@ struct early_of<P, true> {
 	using type = typename P::Early;
 };
 
+// policies whose row address depends on the chunk (CHUNKED = true, moe.h): chunk(g, r, c) is the
+// address of 64-lane chunk c of virtual row (g, r); every other policy keeps row(g, r) + c * chunk bytes
+template <class P, class = void>
+struct gemv_chunked : std::false_type {};
+template <class P>
+struct gemv_chunked<P, std::void_t<decltype(P::CHUNKED)>> : std::bool_constant<P::CHUNKED> {};
+
+// policies that read launch-invariant device data before anything else (PREPARE = true, moe.h: the
+// selected expert indices): prepare() returns it by value, the kernel keeps it in registers and hands
+// it to row(g, r, prep) / chunk(g, r, c, prep), so that no weight address waits on a load in the stream
+template <class P, class = void>
+struct gemv_prepared : std::false_type {};
+template <class P>
+struct gemv_prepared<P, std::void_t<decltype(P::PREPARE)>> : std::bool_constant<P::PREPARE> {};
+struct NoPrep {};
+template <class P, bool = gemv_prepared<P>::value>
+struct prep_of {
+	using type = NoPrep;
+};
+template <class P>
+struct prep_of<P, true> {
+	using type = typename P::Prep;
+};
+
 template <class P, class = void>
 struct gemv_pre : std::false_type {};
 template <class P>
@@ -412,6 +436,9 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(P p, const float *__
 	constexpr int EPL = WT::EPL;
 	constexpr int CH = YALM_WAVE * EPL; // elements per wave-wide chunk
 	const int n = p.n;
+	typename prep_of<P>::type prep{};
+	if constexpr (gemv_prepared<P>::value)
+		prep = p.prepare();
 	p.prologue();
 	stage_x<NORM>(xs, x, normw, n, eps);
 
@@ -428,8 +455,12 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(P p, const float *__
 			break;
 		const char *rp[R];
 #pragma unroll
-		for (int r = 0; r < R; ++r)
-			rp[r] = p.row(g, r) + (size_t)lane * EPL * WT::BYTES;
+		for (int r = 0; r < R; ++r) {
+			if constexpr (gemv_prepared<P>::value)
+				rp[r] = p.row(g, r, prep) + (size_t)lane * EPL * WT::BYTES;
+			else
+				rp[r] = p.row(g, r) + (size_t)lane * EPL * WT::BYTES;
+		}
 		float acc[R];
 #pragma unroll
 		for (int r = 0; r < R; ++r)
@@ -506,6 +537,9 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 	constexpr size_t CHB = (size_t)CH * WT::BYTES;
 	constexpr int W = THREADS / YALM_WAVE;
 	const int n = p.n;
+	typename prep_of<P>::type prep{};
+	if constexpr (gemv_prepared<P>::value)
+		prep = p.prepare();
 	const int nch = n / CH;
 	const int NB = gridDim.x;
 	const int b = blockIdx.x;
@@ -538,7 +572,12 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 	};
 	auto iaddr = [&](int vr, int c) {
 		const int gl = vr / R, r = vr - gl * R;
-		return p.row(b + gl * NB, r) + (size_t)c * CHB + lane_off;
+		if constexpr (gemv_chunked<P>::value)
+			return p.chunk(b + gl * NB, r, c, prep) + lane_off;
+		else if constexpr (gemv_prepared<P>::value)
+			return p.row(b + gl * NB, r, prep) + (size_t)c * CHB + lane_off;
+		else
+			return p.row(b + gl * NB, r) + (size_t)c * CHB + lane_off;
 	};
 	auto pslot = [&](int vr) { return vr * W + wave; }; // LDS partial slot of item row vr
 

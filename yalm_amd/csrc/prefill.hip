@@ -660,6 +660,10 @@ int hd(HostDev &b, const void *host, size_t bytes) {
 
 extern "C" int yalm_prefill(yalm_decoder d, const int *tokens, int n, int pos0, float *logprobs) {
 	ARGCHK(d && tokens && n > 0 && pos0 >= 0, "yalm_prefill: bad argument");
+	if (d->moe_E > 0) { // callers fall back to per-position forwards on this code
+		set_err("yalm_prefill: batched prefill of a mixture-of-experts model is not implemented");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	const yalm_config &c = d->c;
 	ARGCHK(pos0 + n <= c.max_seq_len, "yalm_prefill: pos0 + n must be <= max_seq_len (no sliding window in prefill)");
 	TRY(check_prefill_shape(c));
@@ -729,6 +733,10 @@ extern "C" int yalm_prefill_info(yalm_decoder d, int *passes, int *scaled_layers
 
 extern "C" int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms) {
 	ARGCHK(d && n > 0 && iters > 0 && avg_ms, "yalm_prefill_time: bad argument");
+	if (d->moe_E > 0) {
+		set_err("yalm_prefill_time: batched prefill of a mixture-of-experts model is not implemented");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	const yalm_config &c = d->c;
 	ARGCHK(n <= c.max_seq_len, "yalm_prefill_time: n > max_seq_len");
 	TRY(check_prefill_shape(c));

@@ -22,6 +22,7 @@
 #include "device_common.h"
 #include "gemv.h"
 #include "misc_kernels.h"
+#include "moe.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -178,6 +179,29 @@ template <class WT>
 struct RowsMode<PQKV<WT>> {
 	static constexpr bool value = true;
 };
+// the expert policies (moe.h) stream as their dense counterparts do
+template <class WT, int ACT>
+struct RowsMode<PMoeGlu<WT, ACT>> {
+	static constexpr bool value = true;
+};
+template <class WT>
+struct RowsMode<PMoeW2<WT>> {
+	static constexpr bool value = true;
+};
+template <class WT>
+struct RowsMode<PMoeW2One<WT>> {
+	static constexpr bool value = true;
+};
+
+// policies that never consume a tensor-parallel exchange (no TIN instantiation): the expert GLU
+template <class P>
+struct LocalX {
+	static constexpr bool value = false;
+};
+template <class WT, int ACT>
+struct LocalX<PMoeGlu<WT, ACT>> {
+	static constexpr bool value = true;
+};
 
 // One launch of gemv_rb_kernel; a consumer of an IPC exchange (tin.n > 0, always a
 // normalising GEMV: QKV, W1|W3, logits) runs the TIN instantiation.
@@ -185,7 +209,7 @@ template <class WT, class P, bool NORM, int THREADS, int U, bool ROWS>
 static int launch_rb_k(const P &p, const float *x, const float *normw, float eps, int nb, size_t lds, hipStream_t st,
                        const TpX &tin) {
 	auto kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS>;
-	if constexpr (NORM) {
+	if constexpr (NORM && !LocalX<P>::value) {
 		if (tin.n > 0)
 			kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS, true>;
 	} else if (tin.n > 0) {
@@ -305,6 +329,95 @@ template <class WT, class P, bool NORM>
 static int launch_gemv_d(yalm_decoder_s *d, const P &p, const float *x, const float *normw, float eps, int kind,
                          const TpX &tin = TpX{}) {
 	return launch_gemv<WT, P, NORM>(p, x, normw, eps, kind, d->gemv[kind], d->stream, tin);
+}
+
+// ---- mixture of experts (moe.h): router, the selected experts' W1 | W3 + GLU, their W2
+struct MoeArgs {
+	const void *gate, *w1, *w2, *w3; // moegate (E, dim); stacked (E, hidden, dim) / (E, dim, hidden)
+	int E, K, hidden, dim, act;
+	int *experts;   // the layer's routing slot [K]
+	float *weights; // [K]
+	float *hb;      // [K * hidden]
+};
+
+#define MOE_LDS_BYTES (160 * 1024) // LDS of one gfx950 CU
+
+// W2 of all K selected experts as ONE launch of row length K * hidden: every 64-lane chunk must
+// lie inside one expert's row, the launch addresses at most MOE_SEL_REGS experts, and hb plus the partial slots (at most 16 waves) must fit the LDS.
+template <class WT>
+static bool moe_w2_one_launch(const MoeArgs &a) {
+	constexpr int CH = YALM_WAVE * WT::EPL;
+	if (a.hidden % CH != 0 || a.K > MOE_SEL_REGS)
+		return false;
+	const int ncu = device_cu_count();
+	const size_t ngl = a.dim <= ncu ? 1 : (a.dim + ncu - 1) / ncu;
+	return ((size_t)a.K * a.hidden + 64 + ngl * 16) * sizeof(float) <= MOE_LDS_BYTES;
+}
+
+template <class WT, bool NORM>
+static int launch_moe_router(const MoeArgs &a, const float *x, const float *normw, float eps, hipStream_t st) {
+	const size_t lds = ((size_t)((a.dim + 3) & ~3) + 64 + MOE_MAX_EXPERTS) * sizeof(float);
+	auto kern = moe_router_kernel<WT, NORM>;
+	if (lds > 65536)
+		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	hipLaunchKernelGGL(kern, dim3(1), dim3(MOE_ROUTER_THREADS), lds, st, (const char *)a.gate, x, normw, eps, a.dim, a.E,
+	                   a.K, a.experts, a.weights);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+template <class WT, bool NORM, int ACT>
+static int launch_moe_glu_act(const MoeArgs &a, const float *x, const float *normw, float eps, GemvCfg cfg,
+                              hipStream_t st) {
+	for (int k0 = 0; k0 < a.K; k0 += MOE_SEL_REGS) { // one launch per MOE_SEL_REGS selected experts
+		const int cnt = std::min(MOE_SEL_REGS, a.K - k0);
+		PMoeGlu<WT, ACT> p;
+		p.w1 = (const char *)a.w1;
+		p.w3 = (const char *)a.w3;
+		p.n = a.dim;
+		p.out = a.hb + (size_t)k0 * a.hidden;
+		p.n_groups = cnt * a.hidden;
+		p.hidden = a.hidden;
+		p.sel = MoeSel{a.experts + k0, a.weights + k0, a.E, cnt};
+		TRY((launch_gemv<WT, PMoeGlu<WT, ACT>, NORM>(p, x, normw, eps, GK_GLU, cfg, st)));
+	}
+	return YALM_OK;
+}
+template <class WT, bool NORM>
+static int launch_moe_glu(const MoeArgs &a, const float *x, const float *normw, float eps, GemvCfg cfg, hipStream_t st) {
+	return a.act == YALM_SILU ? launch_moe_glu_act<WT, NORM, 1>(a, x, normw, eps, cfg, st)
+	                          : launch_moe_glu_act<WT, NORM, 0>(a, x, normw, eps, cfg, st);
+}
+
+// out[row] += sum_k W2[e_k][row] . hb_k
+template <class WT>
+static int launch_moe_w2(const MoeArgs &a, float *out, GemvCfg cfg, hipStream_t st) {
+	if (moe_w2_one_launch<WT>(a)) {
+		PMoeW2<WT> p;
+		p.W = (const char *)a.w2;
+		p.n = a.K * a.hidden;
+		p.out = out;
+		p.n_groups = a.dim;
+		p.hidden = a.hidden;
+		p.sel = MoeSel{a.experts, a.weights, a.E, a.K};
+		return launch_rb<WT, PMoeW2<WT>, false>(p, a.hb, nullptr, 0.f, GK_W2, cfg, st, TpX{});
+	}
+	for (int k = 0; k < a.K; ++k) { // one launch per selected expert, in selection order
+		PMoeW2One<WT> p;
+		p.W = (const char *)a.w2;
+		p.n = a.hidden;
+		p.out = out;
+		p.n_groups = a.dim;
+		p.sel = MoeSel{a.experts + k, a.weights + k, a.E, 1};
+		TRY((launch_gemv<WT, PMoeW2One<WT>, false>(p, a.hb + (size_t)k * a.hidden, nullptr, 0.f, GK_W2, cfg, st)));
+	}
+	return YALM_OK;
+}
+
+static int validate_moe(int n_experts, int n_active) {
+	ARGCHK(n_experts >= 1 && n_experts <= MOE_MAX_EXPERTS && n_active >= 1 && n_active <= n_experts,
+	       "mixture of experts: need 1 <= n_experts_active <= n_experts <= 64");
+	return YALM_OK;
 }
 
 static bool attn_supported(int head_dim, int G) {
@@ -688,6 +801,12 @@ static TpX tpx_consume(yalm_decoder_s *d, int ex, int n) {
 	return tpx_ex(d, ex);
 }
 
+static MoeArgs moe_layer_args(const yalm_decoder_s *d, int l) {
+	const yalm_block_weights &w = d->b[l];
+	return MoeArgs{d->moegate[l], w.w1, w.w2, w.w3, d->moe_E, d->moe_K, d->c.hidden_dim, d->c.dim, d->c.act,
+	               d->moe_sel + (size_t)l * d->moe_K, d->moe_wts + (size_t)l * d->moe_K, d->hb};
+}
+
 // One layer. IPC tensor parallelism (tp_exchange.h): the Wo partial is exchange ex0 (the GLU
 // consumes it), the W2 partial exchange ex0 + 1 (push_w2; the next QKV or the logits GEMV
 // consumes it); x_exchanged: the layer's input x is exchange ex0 - 1 (the QKV GEMV consumes
@@ -724,6 +843,12 @@ static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, 
 		TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, d->q, w.key_cache, w.value_cache, d->step, c.max_seq_len,
 		                d->part, l, c.n_layers, d->awo_err, nullptr, d->xb2, st));
 		TRY(enqueue_residual_gemv<WT>(d, w.wo, q_dim, d->xb2, GK_WO, ex0));
+	}
+	if (d->moe_E > 0) { // router, then the selected experts' FFN (never tensor parallel)
+		const MoeArgs a = moe_layer_args(d, l);
+		TRY((launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, st)));
+		TRY((launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], st)));
+		return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], st);
 	}
 	// the GLU consumes the Wo exchange under IPC tensor parallelism
 	if (c.act == YALM_SILU) {
@@ -926,11 +1051,19 @@ static int replay(yalm_decoder_s *d, int which) {
 // comm: an initialised ncclComm_t (tensor parallelism) or null. config holds
 // the local (per-rank) dims; vocab_full the unsharded vocabulary.
 static int create_decoder(const yalm_config *config, const yalm_model_weights *weights, yalm_stream s,
-                          yalm_decoder *out, void *comm, int tp_rank, int tp_size, int vocab_full) {
+                          yalm_decoder *out, void *comm, int tp_rank, int tp_size, int vocab_full,
+                          const yalm_moe_config *moe = nullptr, const void *const *moegate = nullptr) {
 	ARGCHK(config && weights && out && weights->blocks, "yalm_decoder_create: null argument");
 	TRY(validate_config(config));
+	if (moe)
+		TRY(validate_moe(moe->n_experts, moe->n_experts_active));
 	yalm_decoder_s *d = new yalm_decoder_s();
 	d->c = *config;
+	if (moe) {
+		d->moe_E = moe->n_experts;
+		d->moe_K = moe->n_experts_active;
+		d->moegate.assign(moegate, moegate + config->n_layers);
+	}
 	d->comm = comm;
 	d->tp_rank = tp_rank;
 	d->tp_size = tp_size;
@@ -977,7 +1110,9 @@ static int create_decoder(const yalm_config *config, const yalm_model_weights *w
 	if ((r = dalloc(d, (void **)&d->step, sizeof(StepState))) || (r = dalloc(d, (void **)&d->x, sizeof(float) * c.dim)) ||
 	    (r = dalloc(d, (void **)&d->q, sizeof(float) * q_dim)) ||
 	    (r = dalloc(d, (void **)&d->xb2, sizeof(float) * q_dim)) ||
-	    (r = dalloc(d, (void **)&d->hb, sizeof(float) * c.hidden_dim)) ||
+	    (r = dalloc(d, (void **)&d->hb, sizeof(float) * c.hidden_dim * std::max(1, d->moe_K))) ||
+	    (r = dalloc(d, (void **)&d->moe_sel, sizeof(int) * (size_t)c.n_layers * d->moe_K)) ||
+	    (r = dalloc(d, (void **)&d->moe_wts, sizeof(float) * (size_t)c.n_layers * d->moe_K)) ||
 	    (r = dalloc(d, (void **)&d->part, sizeof(unsigned long long) * (size_t)c.n_heads * nsplit * (c.head_dim + 2))) ||
 	    (r = dalloc(d, (void **)&d->awo_err, sizeof(unsigned) * AWO_REPL_STRIDE)) ||
 	    (r = dalloc(d, (void **)&d->logits, sizeof(float) * vocab_full)) ||
@@ -1029,6 +1164,27 @@ extern "C" int yalm_decoder_create(const yalm_config *config, const yalm_model_w
                                    yalm_decoder *out) {
 	ARGCHK(config, "yalm_decoder_create: null config");
 	return create_decoder(config, weights, s, out, nullptr, 0, 1, config->vocab_size);
+}
+
+// Mixture of experts on one GPU (moe.h): blocks[l].w1 / w2 / w3 are the stacked expert tensors.
+extern "C" int yalm_decoder_create_moe(const yalm_config *config, const yalm_moe_config *moe,
+                                       const yalm_model_weights *weights, const void *const *moegate, yalm_stream s,
+                                       yalm_decoder *out) {
+	ARGCHK(config && moe && moegate, "yalm_decoder_create_moe: null argument");
+	for (int l = 0; l < config->n_layers; ++l)
+		ARGCHK(moegate[l], "yalm_decoder_create_moe: null moegate pointer");
+	return create_decoder(config, weights, s, out, nullptr, 0, 1, config->vocab_size, moe, moegate);
+}
+
+extern "C" int yalm_moe_routing(yalm_decoder d, int *experts, float *weights) {
+	ARGCHK(d && d->moe_E > 0, "yalm_moe_routing: not a mixture-of-experts decoder");
+	HIPCHK(hipStreamSynchronize(d->stream));
+	const size_t n = (size_t)d->c.n_layers * d->moe_K;
+	if (experts)
+		HIPCHK(hipMemcpy(experts, d->moe_sel, sizeof(int) * n, hipMemcpyDeviceToHost));
+	if (weights)
+		HIPCHK(hipMemcpy(weights, d->moe_wts, sizeof(float) * n, hipMemcpyDeviceToHost));
+	return YALM_OK;
 }
 
 // ------------------------------------------------------------------ tensor parallelism
@@ -1357,6 +1513,14 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	const yalm_config &c = d->c;
 	const yalm_block_weights &w = d->b[l];
 	const int q_dim = c.n_heads * c.head_dim;
+	if (d->moe_E > 0 && (kernel_id == 3 || kernel_id == 4 || kernel_id == 9)) { // the layer's last routing
+		const MoeArgs a = moe_layer_args(d, l);
+		if (kernel_id == 9)
+			return launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->stream);
+		if (kernel_id == 3)
+			return launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], d->stream);
+		return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], d->stream);
+	}
 	switch (kernel_id) {
 	case 0:
 	case 2:
@@ -1493,8 +1657,9 @@ static int time_loop(yalm_decoder_s *d, int kernel_id, int iters, bool bump, boo
 }
 
 extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms) {
-	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 8 && kernel_id != 7,
-	       "bad argument (kernel ids 0-6, 8)");
+	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 9 && kernel_id != 7,
+	       "bad argument (kernel ids 0-6, 8, 9)");
+	ARGCHK(kernel_id != 9 || d->moe_E > 0, "kernel 9 (expert router) needs a mixture-of-experts decoder");
 	ARGCHK(kernel_id != 6 || d->comm || d->ipc, "kernel 6 (tensor-parallel exchange) needs a tensor-parallel decoder");
 	ARGCHK(kernel_id != 8 || d->attn_wo, "kernel 8 (fused attention + Wo) needs yalm_decoder_attn_wo");
 	// in-launch hand-offs and the IPC exchange: fresh tags per launch (one exchange per bump)
@@ -1544,10 +1709,13 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 		break;
 	case 2:
 	case 4:
-		s = gk + ", PResidual<";
+		s = gk + (kernel_id == 4 && d->moe_E > 0 ? ", PMoeW2" : ", PResidual<");
 		break;
 	case 3:
-		s = gk + ", PGlu<";
+		s = gk + (d->moe_E > 0 ? ", PMoeGlu<" : ", PGlu<");
+		break;
+	case 9:
+		s = d->moe_E > 0 ? std::string("moe_router_kernel<") + wt : "";
 		break;
 	case 5:
 		s = gk + ", PStore<";
@@ -1804,5 +1972,43 @@ extern "C" int yalm_ffn(float *xout, const float *x, const void *w1, const void 
 	                dim, act));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(xout, dout.p, sizeof(float) * dim, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+template <class WT>
+static int moe_ffn_t(const MoeArgs &a, float *out, const float *x) {
+	TRY((launch_moe_router<WT, false>(a, x, nullptr, 0.f, nullptr)));
+	TRY((launch_moe_glu<WT, false>(a, x, nullptr, 0.f, GemvCfg{}, nullptr)));
+	return launch_moe_w2<WT>(a, out, GemvCfg{}, nullptr); // out starts at 0: the sum without a residual
+}
+
+extern "C" int yalm_moe_ffn(float *xout, int *experts, float *weights, const float *x, const void *moegate,
+                            const void *w1, const void *w2, const void *w3, int n_experts, int n_active, int hidden_dim,
+                            int dim, int act, int dtype) {
+	ARGCHK(xout && x && moegate && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "bad argument");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "bad dtype");
+	ARGCHK(dim % 16 == 0 && hidden_dim % 16 == 0, "dims must be multiples of 16");
+	ARGCHK(act == YALM_SILU || act == YALM_GELU, "bad activation");
+	TRY(validate_moe(n_experts, n_active));
+	const size_t wb = wbytes(dtype) * (size_t)n_experts * hidden_dim * dim;
+	DevBuf dx, dg, d1, d2, d3, dhb, dout, dsel, dwts;
+	TRY(up(dx, x, sizeof(float) * dim));
+	TRY(up(dg, moegate, wbytes(dtype) * (size_t)n_experts * dim));
+	TRY(up(d1, w1, wb));
+	TRY(up(d2, w2, wb));
+	TRY(up(d3, w3, wb));
+	TRY(up(dhb, nullptr, sizeof(float) * (size_t)n_active * hidden_dim));
+	TRY(up(dout, nullptr, sizeof(float) * dim));
+	TRY(up(dsel, nullptr, sizeof(int) * n_active));
+	TRY(up(dwts, nullptr, sizeof(float) * n_active));
+	const MoeArgs a{dg.p, d1.p, d2.p, d3.p, n_experts, n_active, hidden_dim, dim, act, (int *)dsel.p, (float *)dwts.p,
+	                (float *)dhb.p};
+	TRY(DISPATCH_WT(dtype, moe_ffn_t, a, (float *)dout.p, (const float *)dx.p));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(xout, dout.p, sizeof(float) * dim, hipMemcpyDeviceToHost));
+	if (experts)
+		HIPCHK(hipMemcpy(experts, dsel.p, sizeof(int) * n_active, hipMemcpyDeviceToHost));
+	if (weights)
+		HIPCHK(hipMemcpy(weights, dwts.p, sizeof(float) * n_active, hipMemcpyDeviceToHost));
 	return YALM_OK;
 }

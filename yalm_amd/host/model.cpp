@@ -57,9 +57,8 @@ void Config::from_yalm(YALMData &yalm, int context) {
 		weight_dtype = DType::F8E5M2;
 	else
 		throw std::runtime_error("FATAL: unsupported dtype: " + dtype);
-	if (n_experts > 0)
-		throw std::runtime_error("FATAL: mixture-of-experts models are CPU-only in the reference (infer.cu:865-867) "
-		                         "and out of scope for this engine");
+	if (n_experts > 0 && !(n_experts_active >= 1 && n_experts_active <= n_experts && n_experts <= 64))
+		throw std::runtime_error("FATAL: mixture of experts needs 1 <= n_experts_active <= n_experts <= 64");
 }
 
 size_t Config::active_bytes(size_t pos) const {
@@ -68,7 +67,12 @@ size_t Config::active_bytes(size_t pos) const {
 	per_block += (size_t)n_heads * head_dim * dim * wsz;
 	per_block += 2 * (size_t)n_kv_heads * head_dim * dim * wsz;
 	per_block += (size_t)n_heads * head_dim * dim * wsz;
-	per_block += 3 * (size_t)dim * hidden_dim * wsz;
+	if (n_experts > 0) { // model.cpp:85-87: the router and the active experts
+		per_block += (size_t)n_experts * dim * wsz;
+		per_block += (size_t)n_experts_active * 3 * dim * hidden_dim * wsz;
+	} else {
+		per_block += 3 * (size_t)dim * hidden_dim * wsz;
+	}
 	const size_t kv_len = std::min((size_t)max_seq_len, pos + 1);
 	per_block += 2 * kv_len * n_kv_heads * head_dim * sizeof(f16_t);
 	return dim * wsz + n_layers * per_block + dim * sizeof(float) + (size_t)vocab_size * dim * wsz;
@@ -132,7 +136,7 @@ void InferenceState::cuda() {
 
 Block::Block(int layer_i, std::shared_ptr<Config> config, const Tensor *rms_att_weight, const Tensor *rms_ffn_weight,
              const Tensor *wq, const Tensor *wk, const Tensor *wv, const Tensor *wo, const Tensor *w1, const Tensor *w2,
-             const Tensor *w3)
+             const Tensor *w3, const Tensor *moegate)
     : _layer_i(layer_i), _config(std::move(config)) {
 	const Config &c = *_config;
 	const DType dt = c.weight_dtype;
@@ -142,9 +146,16 @@ Block::Block(int layer_i, std::shared_ptr<Config> config, const Tensor *rms_att_
 	_wk = check_tensor(wk, dt, {c.n_kv_heads * c.head_dim, c.dim, 0, 0});
 	_wv = check_tensor(wv, dt, {c.n_kv_heads * c.head_dim, c.dim, 0, 0});
 	_wo = check_tensor(wo, dt, {c.dim, c.n_heads * c.head_dim, 0, 0});
-	_w1 = check_tensor(w1, dt, {c.hidden_dim, c.dim, 0, 0});
-	_w2 = check_tensor(w2, dt, {c.dim, c.hidden_dim, 0, 0});
-	_w3 = check_tensor(w3, dt, {c.hidden_dim, c.dim, 0, 0});
+	if (c.n_experts > 0) { // model.cpp:160-164
+		_moegate = check_tensor(moegate, dt, {c.n_experts, c.dim, 0, 0});
+		_w1 = check_tensor(w1, dt, {c.n_experts, c.hidden_dim, c.dim, 0});
+		_w2 = check_tensor(w2, dt, {c.n_experts, c.dim, c.hidden_dim, 0});
+		_w3 = check_tensor(w3, dt, {c.n_experts, c.hidden_dim, c.dim, 0});
+	} else {
+		_w1 = check_tensor(w1, dt, {c.hidden_dim, c.dim, 0, 0});
+		_w2 = check_tensor(w2, dt, {c.dim, c.hidden_dim, 0, 0});
+		_w3 = check_tensor(w3, dt, {c.hidden_dim, c.dim, 0, 0});
+	}
 }
 
 Block::~Block() {
@@ -172,9 +183,12 @@ void Block::cuda() {
 	_wk = upload(_owned, _wk, kv_dim * c.dim * wsz);
 	_wv = upload(_owned, _wv, kv_dim * c.dim * wsz);
 	_wo = upload(_owned, _wo, c.dim * q_dim * wsz);
-	_w1 = upload(_owned, _w1, (size_t)c.hidden_dim * c.dim * wsz);
-	_w2 = upload(_owned, _w2, (size_t)c.dim * c.hidden_dim * wsz);
-	_w3 = upload(_owned, _w3, (size_t)c.hidden_dim * c.dim * wsz);
+	const size_t ne = c.n_experts > 0 ? c.n_experts : 1; // the whole expert stacks (the reference uploads none)
+	_w1 = upload(_owned, _w1, ne * c.hidden_dim * c.dim * wsz);
+	_w2 = upload(_owned, _w2, ne * c.dim * c.hidden_dim * wsz);
+	_w3 = upload(_owned, _w3, ne * c.hidden_dim * c.dim * wsz);
+	if (_moegate)
+		_moegate = upload(_owned, _moegate, (size_t)c.n_experts * c.dim * wsz);
 	_device = Device::HIP;
 	// The KV cache is allocated (zeroed) by the decoder in HBM: no host copy
 	// to upload (model.cpp:208-210 uploads a zero host array).
@@ -208,7 +222,7 @@ Model::Model(YALMData &yalm, int context) {
 		    get_tensor(yalm, p + "attn.wq.weight"), get_tensor(yalm, p + "attn.wk.weight"),
 		    get_tensor(yalm, p + "attn.wv.weight"), get_tensor(yalm, p + "attn.wo.weight"),
 		    get_tensor(yalm, p + "mlp.w1.weight"), get_tensor(yalm, p + "mlp.w2.weight"),
-		    get_tensor(yalm, p + "mlp.w3.weight")));
+		    get_tensor(yalm, p + "mlp.w3.weight"), c.n_experts > 0 ? get_tensor(yalm, p + "moegate.weight") : nullptr));
 	}
 	rms_final_weight = check_tensor(get_tensor(yalm, "model.norm.weight"), DType::F32, {c.dim, 0, 0, 0});
 	_tied = yalm.tensors.count("model.output.weight") == 0;
@@ -250,6 +264,14 @@ void Model::ensure_decoder(InferenceState &s) {
 		bw.push_back(b->device_weights());
 	yalm_model_weights mw{token_embedding_table, (const float *)rms_final_weight, wcls, bw.data()};
 	const yalm_config cc = config->to_c();
+	if (config->n_experts > 0) {
+		std::vector<const void *> gates;
+		for (auto &b : blocks)
+			gates.push_back(b->moegate());
+		const yalm_moe_config mc{config->n_experts, config->n_experts_active};
+		check(yalm_decoder_create_moe(&cc, &mc, &mw, gates.data(), nullptr, &s._decoder), "decoder create");
+		return;
+	}
 	check(yalm_decoder_create(&cc, &mw, nullptr, &s._decoder), "decoder create");
 }
 

@@ -90,10 +90,11 @@ private:
 struct Block {
 	Block(int layer_i, std::shared_ptr<Config> config, const Tensor *rms_att_weight, const Tensor *rms_ffn_weight,
 	      const Tensor *wq, const Tensor *wk, const Tensor *wv, const Tensor *wo, const Tensor *w1, const Tensor *w2,
-	      const Tensor *w3);
+	      const Tensor *w3, const Tensor *moegate);
 	~Block();
 	void cuda(); // device weight upload (model.cpp:185-211)
 	yalm_block_weights device_weights() const;
+	const void *moegate() const { return _moegate; } // (n_experts, dim) router weights, null when dense
 
 private:
 	int _layer_i = 0;
@@ -102,6 +103,7 @@ private:
 	const void *_rms_att = nullptr, *_rms_ffn = nullptr;
 	const void *_wq = nullptr, *_wk = nullptr, *_wv = nullptr, *_wo = nullptr, *_w1 = nullptr, *_w2 = nullptr,
 	           *_w3 = nullptr;
+	const void *_moegate = nullptr; // with experts, _w1 / _w2 / _w3 are the stacked (n_experts, ...) tensors
 	std::vector<void *> _owned;
 };
 

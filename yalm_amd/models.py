@@ -38,6 +38,10 @@ class ModelConfig:
     tied: bool = False
     bos_token_id: int = 1
     eos_token_id: int = 2
+    # mixture of experts (model.h:57-59): 0 = dense; else w1 / w2 / w3 are stacked per expert
+    # and a router tensor (moegate) selects n_experts_active of them per token and layer
+    n_experts: int = 0
+    n_experts_active: int = 0
 
     def __post_init__(self):
         if not self.rotary_dim:
@@ -62,7 +66,11 @@ class ModelConfig:
         per_layer = 2 * self.dim * 4
         per_layer += (self.q_dim + 2 * self.kv_dim) * self.dim * wb  # wq wk wv
         per_layer += self.dim * self.q_dim * wb  # wo
-        per_layer += 3 * self.dim * self.hidden_dim * wb  # w1 w2 w3
+        if self.n_experts > 0:  # model.cpp:85-87: the router + the active experts
+            per_layer += self.n_experts * self.dim * wb
+            per_layer += self.n_experts_active * 3 * self.dim * self.hidden_dim * wb
+        else:
+            per_layer += 3 * self.dim * self.hidden_dim * wb  # w1 w2 w3
         return self.n_layers * per_layer + self.dim * wb + self.dim * 4 + self.vocab_size * self.dim * wb
 
     def kv_bytes_per_token(self, kv_len: int) -> int:
@@ -73,7 +81,7 @@ class ModelConfig:
         """__metadata__ strings as convert.py writes them (convert.py:59-81)."""
         inv = {v: k for k, v in DTYPE_NAMES.items()}
         md = {
-            "arch": "MistralForCausalLM",
+            "arch": "MixtralForCausalLM" if self.n_experts > 0 else "MistralForCausalLM",
             "dtype": inv[self.weight_dtype],
             "dim": str(self.dim),
             "hidden_dim": str(self.hidden_dim),
@@ -93,6 +101,9 @@ class ModelConfig:
         }
         if self.qkv_clip != FLT_MAX:
             md["qkv_clip"] = str(self.qkv_clip)
+        if self.n_experts > 0:  # convert.py:78-80
+            md["n_experts"] = str(self.n_experts)
+            md["n_experts_active"] = str(self.n_experts_active)
         return md
 
 
@@ -124,6 +135,8 @@ def config_from_metadata(md: dict, context: int = 0, tied: bool = False) -> Mode
         tied=tied,
         bos_token_id=int(md.get("bos_token_id", "1")),
         eos_token_id=int(md.get("eos_token_id", "2")),
+        n_experts=int(md.get("n_experts", "0")),  # model.cpp:25-29
+        n_experts_active=int(md.get("n_experts_active", "0")),
     )
 
 
@@ -144,7 +157,12 @@ SMALL = ModelConfig(
     dim=512, hidden_dim=1536, head_dim=64, n_layers=4, n_heads=8, n_kv_heads=2, vocab_size=2048, max_seq_len=256,
     rope_theta=10000.0, act=SILU, weight_dtype=F16,
 )
-PRESETS = {"mistral-7b": MISTRAL_7B, "llama-3.2-3b": LLAMA_32_3B, "tiny": TINY, "small": SMALL}
+# Mixture of experts: Mistral-7B dims with 8 experts, 2 active per token (Mixtral-8x7B)
+MIXTRAL_8X7B = MISTRAL_7B.with_(n_experts=8, n_experts_active=2)
+TINY_MOE = TINY.with_(n_experts=4, n_experts_active=2)
+SMALL_MOE = SMALL.with_(n_experts=8, n_experts_active=2)
+PRESETS = {"mistral-7b": MISTRAL_7B, "llama-3.2-3b": LLAMA_32_3B, "tiny": TINY, "small": SMALL,
+           "mixtral-8x7b": MIXTRAL_8X7B, "tiny-moe": TINY_MOE, "small-moe": SMALL_MOE}
 
 
 def layer_names(l: int) -> dict:
@@ -162,6 +180,10 @@ def layer_names(l: int) -> dict:
     }
 
 
+def moegate_name(l: int) -> str:
+    return f"model.layers.{l}.moegate.weight"
+
+
 def tensor_shapes(c: ModelConfig) -> dict:
     """name -> (shape, is_norm) in .yalm naming (model.cpp:351-377)."""
     out = {"model.embed.weight": ((c.vocab_size, c.dim), False), "model.norm.weight": ((c.dim,), True)}
@@ -175,9 +197,12 @@ def tensor_shapes(c: ModelConfig) -> dict:
         out[n["wk"]] = ((c.kv_dim, c.dim), False)
         out[n["wv"]] = ((c.kv_dim, c.dim), False)
         out[n["wo"]] = ((c.dim, c.q_dim), False)
-        out[n["w1"]] = ((c.hidden_dim, c.dim), False)
-        out[n["w2"]] = ((c.dim, c.hidden_dim), False)
-        out[n["w3"]] = ((c.hidden_dim, c.dim), False)
+        e = (c.n_experts,) if c.n_experts > 0 else ()  # model.cpp:160-164: stacked per expert
+        if e:
+            out[moegate_name(l)] = ((c.n_experts, c.dim), False)
+        out[n["w1"]] = (e + (c.hidden_dim, c.dim), False)
+        out[n["w2"]] = (e + (c.dim, c.hidden_dim), False)
+        out[n["w3"]] = (e + (c.hidden_dim, c.dim), False)
     return out
 
 
@@ -212,6 +237,11 @@ def tp_shard(c: ModelConfig, name: str, rank: int, size: int):
 
 
 def tp_check(c: ModelConfig, size: int) -> None:
+    if c.n_experts > 0:
+        if not 1 <= c.n_experts_active <= c.n_experts <= 64:
+            raise ValueError("mixture of experts: need 1 <= n_experts_active <= n_experts <= 64")
+        if size > 1:
+            raise ValueError("mixture-of-experts models run on one GPU (no tensor-parallel form)")
     if c.n_heads % size or c.n_kv_heads % size or c.hidden_dim % size or c.vocab_size % size:
         raise ValueError(f"tensor parallel size {size} must divide n_heads, n_kv_heads, hidden_dim and vocab_size")
 

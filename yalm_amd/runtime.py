@@ -95,6 +95,10 @@ _sig("yalm_stream_sync", c_int, [c_void_p])
 _sig("yalm_synth", c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint64, c_float, c_float, c_void_p])
 _sig("yalm_decoder_create", c_int, [ctypes.POINTER(Config), ctypes.POINTER(ModelWeights), c_void_p,
                                      ctypes.POINTER(c_void_p)])
+_sig("yalm_decoder_create_moe", c_int, [ctypes.POINTER(Config), c_void_p, ctypes.POINTER(ModelWeights), c_void_p,
+                                         c_void_p, ctypes.POINTER(c_void_p)])
+_sig("yalm_moe_routing", c_int, [c_void_p, c_void_p, c_void_p])
+_sig("yalm_moe_ffn", c_int, [c_void_p] * 8 + [c_int] * 6)
 _sig("yalm_decoder_destroy", c_int, [c_void_p])
 _sig("yalm_forward", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
 _sig("yalm_generate_greedy", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
@@ -143,6 +147,7 @@ EXPORTED = [
     "yalm_decoder_attn_wo", "yalm_attn_wo_trace", "yalm_stream_envelope",
     "yalm_argmax", "yalm_set_prefill_forms", "yalm_attn_wo_plan", "yalm_graph_kernels",
     "yalm_stream_create_cu_part", "yalm_decoder_set_launch", "yalm_prefill_info", "yalm_set_prefill_precision",
+    "yalm_decoder_create_moe", "yalm_moe_routing", "yalm_moe_ffn",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -206,6 +211,21 @@ def ffn(x, w1, w2, w3, act: int, dtype: int) -> np.ndarray:
     out = np.zeros(dim, np.float32)
     check(lib.yalm_ffn(_ptr(out), _ptr(x), _ptr(w1), _ptr(w2), _ptr(w3), hidden_dim, dim, act, dtype))
     return out
+
+
+def moe_ffn(x, moegate, w1, w2, w3, n_active: int, act: int, dtype: int):
+    """yalm_moe_ffn: the router on x, then the selected experts' FFN summed with their
+    weights (no norm, no residual). moegate (E, dim); w1 / w3 (E, hidden, dim), w2 (E, dim,
+    hidden). Returns (xout, experts, weights), the routing in selection order."""
+    n_experts, hidden_dim, dim = w1.shape
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    moegate, w1, w2, w3 = (np.ascontiguousarray(a) for a in (moegate, w1, w2, w3))
+    out = np.zeros(dim, np.float32)
+    experts = np.zeros(max(n_active, 1), np.int32)
+    weights = np.zeros(max(n_active, 1), np.float32)
+    check(lib.yalm_moe_ffn(_ptr(out), _ptr(experts), _ptr(weights), _ptr(x), _ptr(moegate), _ptr(w1), _ptr(w2),
+                           _ptr(w3), n_experts, n_active, hidden_dim, dim, act, dtype))
+    return out, experts[:n_active], weights[:n_active]
 
 
 def stream_envelope(nbytes: int, iters: int = 16) -> float:
@@ -353,7 +373,7 @@ class DeviceModel:
             src_name = "model.embed.weight" if name == "tp.wcls" else name
             scale, offset = M.synth_params(src_name, is_norm, peak, real, cfg.tied)
             sh = M.tp_shard(cfg, name, rank, size)
-            if sh is None:
+            if sh is None or len(shape) != 2:  # (stacked expert tensors are never sharded: tp_check)
                 p = self._alloc(n * eb)
                 check(lib.yalm_synth(p, n, dt, M.synth_seed(seed, src_name), scale, offset, None))
             else:
@@ -450,6 +470,14 @@ class Decoder:
             hb = ctypes.create_string_buffer(b"".join(handles), TP_HANDLE_BYTES * size)
             check(lib.yalm_decoder_create_tp_ipc(ctypes.byref(self._c), ctypes.byref(mw), rank, size, buf, hb, sh,
                                                  ctypes.byref(h)))
+        elif self.cfg.n_experts > 0:
+            if tp_id is not None:
+                raise ValueError("mixture-of-experts models run on one GPU (no tensor-parallel form)")
+            self._moe = (c_int * 2)(self.cfg.n_experts, self.cfg.n_experts_active)  # yalm_moe_config
+            self._moegate = (c_void_p * self.cfg.n_layers)(
+                *[model.ptrs[M.moegate_name(l)] for l in range(self.cfg.n_layers)])
+            check(lib.yalm_decoder_create_moe(ctypes.byref(self._c), self._moe, ctypes.byref(mw), self._moegate, sh,
+                                              ctypes.byref(h)))
         elif tp_id is None:
             check(lib.yalm_decoder_create(ctypes.byref(self._c), ctypes.byref(mw), sh, ctypes.byref(h)))
         else:
@@ -536,6 +564,14 @@ class Decoder:
         out = np.empty(self.cfg.vocab_size, np.float32)
         check(lib.yalm_get_logits(self.h, out.ctypes.data))
         return out
+
+    def moe_routing(self):
+        """(experts, weights), each (n_layers, n_experts_active): the routing of the most
+        recent forward / block, in selection order (yalm_moe_routing)."""
+        shape = (self.cfg.n_layers, max(self.cfg.n_experts_active, 1))
+        experts, weights = np.zeros(shape, np.int32), np.zeros(shape, np.float32)
+        check(lib.yalm_moe_routing(self.h, _ptr(experts), _ptr(weights)))
+        return experts, weights
 
     def time_kernel(self, kernel_id: int, iters: int) -> float:
         ms = c_float()
