@@ -228,8 +228,9 @@ typedef struct yalm_moe_config {
  * yalm_generate_greedy, yalm_enqueue_greedy, yalm_block, yalm_get_x / yalm_set_x,
  * yalm_graph_kernels and yalm_decoder_set_launch work as on a dense decoder;
  * yalm_time_kernel ids 3 and 4 time the expert launches (on the layer's most recent
- * routing), id 9 the router; yalm_prefill returns YALM_ERR_UNSUPPORTED (callers run
- * position by position). There is no tensor-parallel form. */
+ * routing), id 9 the router; yalm_prefill / yalm_prefill_time run the batched expert
+ * FFN (below, "batched prefill") under the dense prefill's shape rules. There is no
+ * tensor-parallel form. */
 int yalm_decoder_create_moe(const yalm_config *config, const yalm_moe_config *moe, const yalm_model_weights *weights,
                             const void *const *moegate, yalm_stream s, yalm_decoder *out);
 /* The routing of the most recent forward / yalm_block: experts[n_layers * K] and
@@ -309,11 +310,22 @@ int yalm_copy_2d(void *dst, size_t dst_pitch, const void *src, size_t src_pitch,
  * a layer's GLU output (W2's A operand; trained checkpoints' "massive activations")
  * is stored with an exact power-of-two scale that W2's epilogue undoes, and the pass
  * runs again; any other operand out of range (the normalised x, Q) returns
- * YALM_ERR_UNSUPPORTED (the decode path keeps them in f32). */
+ * YALM_ERR_UNSUPPORTED (the decode path keeps them in f32).
+ * Mixture-of-experts decoders (yalm_decoder_create_moe): the attention half as above; the
+ * FFN half routes all n rows (the decode router's arithmetic on each row of the f32
+ * residual stream), groups the n * K (row, expert) entries by expert on the device
+ * (stable: rows ascending inside an expert) and runs W1 | W3 + GLU and W2 as grouped GEMMs
+ * over 256-row tiles of one expert each, then x[t] += sum_k weight_k * y[slot(t, k)] in
+ * selection order, in f32, without atomics: two prefills of the same input give the same
+ * bits. max_seq_len * n_experts_active <= 131072. */
 int yalm_prefill(yalm_decoder d, const int *tokens, int n, int pos0, float *logprobs);
 /* The last yalm_prefill's passes (1 = no operand out of range) and the number of
  * layers whose GLU output ran scaled. */
 int yalm_prefill_info(yalm_decoder d, int *passes, int *scaled_layers);
+/* The routing of the last yalm_prefill of n positions on a mixture-of-experts decoder:
+ * experts / weights [n][n_layers][K] (host, either may be NULL), in selection order.
+ * YALM_ERR_ARG on a dense decoder or before any prefill. */
+int yalm_prefill_routing(yalm_decoder d, int *experts, float *weights);
 /* Precision form of decoder d's prefill. YALM_PREFILL_FAST (default): f16 activation
  * operands (the K / V columns' over a split [hi | lo] operand). YALM_PREFILL_SPLIT: every
  * activation operand -- the normalised x, Q, the attention probabilities P, the attention
@@ -367,6 +379,18 @@ int yalm_argmax(const float *logits, int n, int n_shards, int *out);
 /* Prefill building blocks (host pointers, synchronous):
  * c[M][N] f32 = a[M][K] f16 · w[N][K]^T f16 (the MFMA GEMM; N % 128 == 0, K % 64 == 0). */
 int yalm_gemm_f16(float *c, const uint16_t *a, const uint16_t *w, int M, int N, int K);
+/* The grouped GEMM of the mixture-of-experts prefill: c[r] = a[r] . w[expert_of_row[r]]^T,
+ * w (E, N, K) f16, through the device grouping pass, the M-tile table and the grouped tile
+ * kernels (plain store in slot order, scattered back to row order); follows the forms of
+ * yalm_set_prefill_forms(NULL, ...). */
+int yalm_moe_gemm_f16(float *c, const uint16_t *a, const uint16_t *w, const int *expert_of_row, int M, int N, int K,
+                      int E);
+/* The batched router and the whole grouped expert FFN on T already-normalised rows x
+ * [T][dim] f32 (no norm, no residual): xout [T][dim], experts / weights [T][n_active] (may
+ * be NULL). f16 or fp8 (E5M2) weights, dims multiples of 128. */
+int yalm_moe_ffn_rows(float *xout, int *experts, float *weights, const float *x, int T, const void *moegate,
+                      const void *w1, const void *w2, const void *w3, int n_experts, int n_active, int hidden_dim,
+                      int dim, int act, int dtype);
 /* Causal GQA attention of T query rows at positions pos0 .. pos0 + T - 1:
  * q [T][n_heads * head_dim] f16, kc / vc [pos0 + T][n_kv_heads * head_dim] f16,
  * o [T][n_heads * head_dim] f16 (infer.cpp:216-248 per row and head). */

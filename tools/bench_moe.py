@@ -12,7 +12,13 @@ bytes/token roofline fraction and the per-kernel times of yalm_time_kernel (3 = 
 
 Prints one JSON line per model and one for the comparison; --out appends them to a file.
 
+--prefill N (repeatable) measures the batched prefill instead: yalm_prefill_time of N positions
+on the expert model and on the dense twin (same FFN FLOPs per token), fast and split-operand
+forms, and -- in the same process -- N per-position hydration forwards on the expert decoder,
+the path these models took before the grouped expert prefill.
+
 Usage: python tools/bench_moe.py [--steps 128] [--warmup 16] [--reps 3] [--layers 32] [--out FILE]
+       python tools/bench_moe.py --prefill 4096 --prefill 13 [--layers 32] [--prefill-iters 3] [--out FILE]
 """
 import argparse
 import json
@@ -73,6 +79,57 @@ def run_model(runtime, name, cfg, args, kernel_ids):
         dm.close()
 
 
+def prefill_model(runtime, name, cfg, args):
+    """yalm_prefill_time per N in both precision forms; expert models: N per-position forwards too."""
+    dm = runtime.DeviceModel.synthetic(cfg, seed=1)
+    dec = runtime.Decoder(dm)
+    out = []
+    try:
+        for n in args.prefill:
+            row = {"model": name, "prefill_n": n, "n_layers": cfg.n_layers, "n_experts": cfg.n_experts,
+                   "n_experts_active": cfg.n_experts_active, "hidden_dim": cfg.hidden_dim}
+            for form, mode in (("fast", runtime.PREFILL_FAST), ("split", runtime.PREFILL_SPLIT)):
+                dec.set_prefill_precision(mode)
+                ms = sorted(dec.prefill_time(n, args.prefill_iters) for _ in range(args.reps))
+                row[f"{form}_ms"] = round(ms[0], 3)
+                row[f"{form}_ms_all"] = [round(m, 3) for m in ms]
+            dec.set_prefill_precision(runtime.PREFILL_FAST)
+            # FFN GEMM FLOPs per pass (W1, W3, W2 of the active experts / of the twin's one FFN)
+            k = max(cfg.n_experts_active, 1)
+            row["ffn_tflop"] = round(6.0 * n * k * cfg.hidden_dim * cfg.dim * cfg.n_layers / 1e12, 3)
+            if cfg.n_experts > 0 and not args.skip_per_position:
+                dec.forward(1, 0, runtime.HYDRATE_KV_CACHE)  # warm-up (graph capture)
+                runtime.check(runtime.lib.yalm_stream_sync(None))
+                t0 = time.perf_counter()
+                for pos in range(n - 1):
+                    dec.forward((7 * pos + 1) % cfg.vocab_size, pos, runtime.HYDRATE_KV_CACHE)
+                dec.forward(3, n - 1)  # the last one with logits: its copy-back waits for them all
+                row["per_position_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+                row["per_position_over_fast"] = round(row["per_position_ms"] / row["fast_ms"], 2)
+            out.append(row)
+        return out
+    finally:
+        dec.close()
+        dm.close()
+
+
+def main_prefill(runtime, M, args):
+    moe_cfg = M.MIXTRAL_8X7B.with_(n_layers=args.layers)
+    twin_cfg = M.MISTRAL_7B.with_(n_layers=args.layers, hidden_dim=moe_cfg.n_experts_active * moe_cfg.hidden_dim)
+    moe = prefill_model(runtime, "mixtral-8x7b", moe_cfg, args)
+    twin = prefill_model(runtime, "dense-twin", twin_cfg, args)
+    rows = moe + twin
+    for m, t in zip(moe, twin):
+        rows.append({"compare": "moe_prefill_vs_twin", "prefill_n": m["prefill_n"],
+                     "fast_ms_moe_vs_twin": [m["fast_ms"], t["fast_ms"]],
+                     "fast_ratio": round(m["fast_ms"] / t["fast_ms"], 4),
+                     "split_ms_moe_vs_twin": [m["split_ms"], t["split_ms"]],
+                     "split_ratio": round(m["split_ms"] / t["split_ms"], 4),
+                     "per_position_ms": m.get("per_position_ms"),
+                     "per_position_over_fast": m.get("per_position_over_fast")})
+    return [json.dumps(x) for x in rows]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=128)
@@ -81,6 +138,12 @@ def main(argv=None):
     ap.add_argument("--layers", type=int, default=32, help="fewer layers = a smaller model of the same shapes")
     ap.add_argument("--kernel-iters", type=int, default=64)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--prefill", type=int, action="append", default=None,
+                    help="measure the batched prefill of N positions instead of decode (repeatable)")
+    ap.add_argument("--prefill-iters", type=int, default=3)
+    ap.add_argument("--skip-per-position", action="store_true",
+                    help="--prefill: leave out the per-position forwards (kernel-stats runs under a profiler: "
+                         "the per-token graph replay is not what they measure)")
     args = ap.parse_args(argv)
 
     from yalm_amd import models as M
@@ -88,6 +151,15 @@ def main(argv=None):
 
     runtime.M = M
     runtime.check(runtime.lib.yalm_set_device(0))
+    if args.prefill:
+        lines = main_prefill(runtime, M, args)
+        for l in lines:
+            print(l, flush=True)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     moe_cfg = M.MIXTRAL_8X7B.with_(n_layers=args.layers)
     twin_cfg = M.MISTRAL_7B.with_(n_layers=args.layers, hidden_dim=moe_cfg.n_experts_active * moe_cfg.hidden_dim)
     moe = run_model(runtime, "mixtral-8x7b", moe_cfg, args, (3, 4, 9))

@@ -81,6 +81,12 @@ struct PrefillBufs {
 	unsigned *range = nullptr;                 // [n_layers + 1][4] f16-operand range guard (prefill.h range_note)
 	uint16_t *wdq = nullptr;                   // fp8 models: one layer's (or the classifier's) weights as f16
 	int last_passes = 0, last_scaled = 0;      // the last yalm_prefill: passes run, layers with a scaled GLU output
+	// mixture of experts (moe_prefill.h; allocated only for such decoders): H then holds cap * K rows
+	float *Y = nullptr;                        // [cap * K][dim] f32 W2 outputs in slot order
+	int *rt_experts = nullptr;                 // [n_layers][cap][K] the routing of the last prefill
+	float *rt_weights = nullptr;               // [n_layers][cap][K]
+	int *slot_row = nullptr, *slot_of = nullptr, *tiles = nullptr, *mtiles = nullptr, *counts = nullptr; // MoeGroupTabs
+	int last_n = 0;                            // rows of the last completed yalm_prefill (0: none)
 };
 
 // Prefill GEMM forms (prefill.hip): per GEMM kind the large-tile width (-1 = auto,

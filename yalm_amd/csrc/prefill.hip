@@ -1,7 +1,8 @@
 // prefill.hip — C ABI of the batched prefill / perplexity path (prefill.h):
 // yalm_prefill (prompt hydration + per-position log p(next), replacing the
 // reference's position-by-position loop in main.cpp:128-200 / 91-97) and
-// its kernel-level test hooks (yalm_gemm_f16, yalm_attn_prefill).
+// its kernel-level test hooks (yalm_gemm_f16, yalm_attn_prefill; mixture of experts:
+// yalm_moe_gemm_f16, yalm_moe_ffn_rows).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "decoder.h"
 #include "prefill.h"
+#include "moe_prefill.h"
 #include "prefill_gemm.h"
 #include "prefill_skinny.h"
 
@@ -142,10 +144,12 @@ int pick_bn(const PfForms &f, int kind, int M, int n_eff, bool glu) {
 }
 
 // c_split / K2: columns [c_split, N) run K2 (gemm8p_kernel); c_split = N: one depth
-template <class EPI, class BMAP, int FJ0, int FJ1>
+// grp / tile_bound: row groups (prefill_gemm.h RowGroups) and the host-side bound on their M tiles
+template <class EPI, class BMAP, int FJ0, int FJ1, class GRP = pf::NoGroup>
 int launch_g8p(const PfForms &f, const uint16_t *A, int lda, int M, int K, int kb, const BMAP &bm, int N,
-               const EPI &epi, hipStream_t st, int c0, int c_split = -1, int K2 = 0) {
-	auto kern = pf::gemm8p_kernel<EPI, BMAP, FJ0, FJ1>;
+               const EPI &epi, hipStream_t st, int c0, int c_split = -1, int K2 = 0, const GRP &grp = GRP{},
+               int tile_bound = 0) {
+	auto kern = pf::gemm8p_kernel<EPI, BMAP, FJ0, FJ1, GRP>;
 	constexpr size_t lds = pf::gemm8p_lds<FJ0, FJ1>();
 	constexpr int BN = 64 * (FJ0 + FJ1);
 	static bool attr = false;
@@ -153,40 +157,40 @@ int launch_g8p(const PfForms &f, const uint16_t *A, int lda, int M, int K, int k
 		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		attr = true;
 	}
-	const int nwg = ((M + pf::G_BM - 1) / pf::G_BM) * (N / BN);
+	const int nwg = (GRP::ON ? tile_bound : (M + pf::G_BM - 1) / pf::G_BM) * (N / BN);
 	// more tiles than CUs: one persistent workgroup per CU walks them
 	const int ncu = (int)device_cu_count();
 	// (two depths: one workgroup per tile, so the hardware balances them longest first)
 	const bool two = c_split >= 0 && c_split < N;
 	const int grid = f.persist && nwg > ncu && !two ? ncu : nwg;
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(pf::G_THREADS), lds, st, A, lda, M, K, kb, bm, N, epi, c0,
-	                   two ? c_split : N, two ? K2 : K);
+	                   two ? c_split : N, two ? K2 : K, grp);
 	HIPCHK(hipGetLastError());
 	return YALM_OK;
 }
 
 // C[:, c0 .. c0 + N) = A · B^T over K columns of A (row stride lda) against B rows kb
 // wide (K > kb: B wrap, prefill_gemm.h), tile 256 x BN
-template <class EPI, class BMAP, int BN, int WM>
+template <class EPI, class BMAP, int BN, int WM, class GRP = pf::NoGroup>
 int launch_g16_t(const PfForms &f, const uint16_t *A, int lda, int M, int K, int kb, const BMAP &bm, int N,
-                 const EPI &epi, hipStream_t st, int c0 = 0) {
+                 const EPI &epi, hipStream_t st, int c0 = 0, const GRP &grp = GRP{}, int tile_bound = 0) {
 	if (f.p8) { // the 8-phase schedule at the same tile width (320: spills, stays 2-phase)
 		if constexpr (BN == 256 && WM == 2)
-			return launch_g8p<EPI, BMAP, 2, 2>(f, A, lda, M, K, kb, bm, N, epi, st, c0);
+			return launch_g8p<EPI, BMAP, 2, 2, GRP>(f, A, lda, M, K, kb, bm, N, epi, st, c0, -1, 0, grp, tile_bound);
 		if constexpr (BN == 192 && WM == 2)
-			return launch_g8p<EPI, BMAP, 2, 1>(f, A, lda, M, K, kb, bm, N, epi, st, c0);
+			return launch_g8p<EPI, BMAP, 2, 1, GRP>(f, A, lda, M, K, kb, bm, N, epi, st, c0, -1, 0, grp, tile_bound);
 		if constexpr (BN == 128 && std::is_same<BMAP, pf::BRowsPlain>::value) // GLU rows pair per 64-col wave
-			return launch_g8p<EPI, BMAP, 1, 1>(f, A, lda, M, K, kb, bm, N, epi, st, c0);
+			return launch_g8p<EPI, BMAP, 1, 1, GRP>(f, A, lda, M, K, kb, bm, N, epi, st, c0, -1, 0, grp, tile_bound);
 	}
-	auto kern = pf::gemm16_kernel<EPI, BMAP, BN, WM>;
+	auto kern = pf::gemm16_kernel<EPI, BMAP, BN, WM, GRP>;
 	constexpr size_t lds = pf::gemm16_lds<BN>();
 	static bool attr = false;
 	if (!attr) {
 		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 		attr = true;
 	}
-	const int nwg = ((M + pf::G_BM - 1) / pf::G_BM) * (N / BN);
-	hipLaunchKernelGGL(kern, dim3(nwg), dim3(pf::G_THREADS), lds, st, A, lda, M, K, kb, bm, N, epi, c0);
+	const int nwg = (GRP::ON ? tile_bound : (M + pf::G_BM - 1) / pf::G_BM) * (N / BN);
+	hipLaunchKernelGGL(kern, dim3(nwg), dim3(pf::G_THREADS), lds, st, A, lda, M, K, kb, bm, N, epi, c0, grp);
 	HIPCHK(hipGetLastError());
 	return YALM_OK;
 }
@@ -296,13 +300,13 @@ pf::BSrc one(const void *w, int rows) {
 
 // fp8 models: the tensors (E5M2 bytes, n elements each) dequantised to f16 into b.wdq, end
 // to end; returns their f16 copies in `out` (prefill.h e5m2_to_f16_kernel)
-int dequant(yalm_decoder_s *d, std::initializer_list<std::pair<const void *, size_t>> t, const uint16_t **out,
-			hipStream_t st) {
+int dequant_into(uint16_t *wdq, std::initializer_list<std::pair<const void *, size_t>> t, const uint16_t **out,
+				 hipStream_t st) {
 	pf::DqSegs s{};
 	size_t off = 0, pieces = 0;
 	for (auto &p : t) {
 		s.src[s.n] = (const uint8_t *)p.first;
-		s.dst[s.n] = d->pf.wdq + off;
+		s.dst[s.n] = wdq + off;
 		out[s.n] = s.dst[s.n];
 		pieces += p.second / 16;
 		s.end[s.n] = pieces;
@@ -318,6 +322,11 @@ int dequant(yalm_decoder_s *d, std::initializer_list<std::pair<const void *, siz
 // Xn = f16(rmsnorm(X) * w) rows (SPLIT: [hi | lo]): one wave per row with the row in
 // registers (prefill.h rmsnorm_rows_wave_kernel) when dim <= 8192, else (or forms "wnorm:0")
 // the workgroup-per-row kernel
+int dequant(yalm_decoder_s *d, std::initializer_list<std::pair<const void *, size_t>> t, const uint16_t **out,
+			hipStream_t st) {
+	return dequant_into(d->pf.wdq, t, out, st);
+}
+
 template <bool SPLIT>
 int launch_rmsnorm_t(const PfForms &f, const float *X, const float *w, int dim, int T, float eps, uint16_t *Xn,
                      unsigned *range, hipStream_t st) {
@@ -378,6 +387,145 @@ int launch_attn_prefill(const uint16_t *Q, const uint16_t *kc, const uint16_t *v
 	return YALM_ERR_UNSUPPORTED;
 }
 
+// ---- mixture of experts: the FFN half of a layer over T rows (moe_prefill.h)
+struct MoeFfn {
+	const void *gate; // moegate (E, dim) f16 (fp8 models: the exact upcast, as the expert tensors)
+	const uint16_t *w1, *w2, *w3; // stacked f16 (E, hidden, dim) / (E, dim, hidden)
+	int E, K, hidden, dim, act;
+	int T;
+	const float *X;     // [T][dim] the router's input rows
+	const float *normw; // rms_ffn: the router normalises X itself; null: X is already normalised
+	float eps;
+	const uint16_t *Xn; // [T][sp dim] f16 A operand
+	bool split;
+	int he; // the GLU output's power-of-two scale exponent
+	unsigned *range;
+	uint16_t *H; // [T K][sp hidden]
+	float *Y;    // [T K][dim]
+	pf::MoeGroupTabs tabs;
+	int *experts;   // [T][K]
+	float *weights; // [T][K]
+	float *out;     // [T][dim]
+	bool resid;     // out += (the residual stream), else out =
+};
+
+int moe_tile_bound(int slots, int E) { return (slots + pf::G_BM - 1) / pf::G_BM + std::min(E, slots); }
+
+template <class WT>
+int launch_moe_router_rows(const MoeFfn &a, hipStream_t st) {
+	const size_t lds = ((size_t)((a.dim + 3) & ~3) + 64 + MOE_MAX_EXPERTS) * sizeof(float);
+	const bool norm = a.normw != nullptr;
+	auto kern = norm ? pf::moe_router_rows_kernel<WT, true> : pf::moe_router_rows_kernel<WT, false>;
+	if (lds > 65536)
+		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	hipLaunchKernelGGL(kern, dim3(a.T), dim3(MOE_ROUTER_THREADS), lds, st, (const char *)a.gate, a.X, a.normw, a.eps, a.dim,
+	                   a.E, a.K, a.experts, a.weights);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+// the (row, k) entries of `experts` grouped by expert: slot lists and the M-tile table
+int launch_moe_group(const int *experts, int n, int K, int E, const pf::MoeGroupTabs &tabs, hipStream_t st) {
+	if (n > pf::MOE_GROUP_MAX) {
+		set_err("mixture-of-experts prefill: more than 131072 (row, expert) entries in one pass");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const size_t lds = (size_t)((n + 15) & ~15) + 2 * MOE_MAX_EXPERTS * sizeof(int);
+	static bool attr = false;
+	if (!attr) {
+		HIPCHK(hipFuncSetAttribute((const void *)pf::moe_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+		                           (int)(pf::MOE_GROUP_MAX + 2 * MOE_MAX_EXPERTS * sizeof(int))));
+		attr = true;
+	}
+	hipLaunchKernelGGL(pf::moe_group_kernel, dim3(1), dim3(pf::MOE_GROUP_THREADS), lds, st, experts, n, K, E,
+	                   moe_tile_bound(n, E), tabs);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+template <int ACT, bool SPLIT>
+int launch_moe_glu_t(const PfForms &f, const MoeFfn &a, hipStream_t st) {
+	const int slots = a.T * a.K, bound = moe_tile_bound(slots, a.E), sp = SPLIT ? 2 : 1;
+	const int bn = pick_bn(f, PG_GLU, bound * pf::G_BM, 2 * a.hidden, true);
+	using EPI = pf::E16Glu<ACT, SPLIT>;
+	EPI e;
+	e.h = a.H;
+	e.ldh = a.hidden * sp;
+	e.M = slots;
+	e.hscale = ldexpf(1.0f, -a.he);
+	e.range = a.range;
+	e.lo_off = SPLIT ? a.hidden : 0;
+	const pf::BRowsGlu<64> bm{a.w1, a.w3};
+	const pf::RowGroups g{a.tabs.tiles, a.tabs.ntiles, a.tabs.slot_row, (size_t)a.hidden * a.dim};
+	if (bn == 256)
+		return launch_g16_t<EPI, pf::BRowsGlu<64>, 256, 2, pf::RowGroups>(f, a.Xn, sp * a.dim, slots, sp * a.dim, a.dim, bm,
+		                                                                  2 * a.hidden, e, st, 0, g, bound);
+	if (bn == 128)
+		return launch_g16_t<EPI, pf::BRowsGlu<64>, 128, 4, pf::RowGroups>(f, a.Xn, sp * a.dim, slots, sp * a.dim, a.dim, bm,
+		                                                                  2 * a.hidden, e, st, 0, g, bound);
+	set_err("prefill GLU GEMM: 2 x hidden_dim must divide by 128 (or by a forced width of 128 / 256)");
+	return YALM_ERR_UNSUPPORTED;
+}
+
+// C[slot] = scale * A[rowmap[slot]] . W[expert of slot]^T (E16StoreScaled), W (E, N, kb)
+int launch_moe_plain(const PfForms &f, int kind, const uint16_t *A, int lda, int slots, int E, int K, int kb,
+                     const uint16_t *w, int N, const pf::E16StoreScaled &e, const pf::MoeGroupTabs &tabs,
+                     const int *rowmap, hipStream_t st) {
+	const int bound = moe_tile_bound(slots, E);
+	const pf::RowGroups g{tabs.tiles, tabs.ntiles, rowmap, (size_t)N * kb};
+	const pf::BRowsPlain bm{one(w, N)};
+	using EPI = pf::E16StoreScaled;
+	switch (pick_bn(f, kind, bound * pf::G_BM, N, false)) {
+	case 128:
+		return launch_g16_t<EPI, pf::BRowsPlain, 128, 4, pf::RowGroups>(f, A, lda, slots, K, kb, bm, N, e, st, 0, g, bound);
+	case 192:
+		return launch_g16_t<EPI, pf::BRowsPlain, 192, 2, pf::RowGroups>(f, A, lda, slots, K, kb, bm, N, e, st, 0, g, bound);
+	case 256:
+		return launch_g16_t<EPI, pf::BRowsPlain, 256, 2, pf::RowGroups>(f, A, lda, slots, K, kb, bm, N, e, st, 0, g, bound);
+	case 320:
+		return launch_g16_t<EPI, pf::BRowsPlain, 320, 2, pf::RowGroups>(f, A, lda, slots, K, kb, bm, N, e, st, 0, g, bound);
+	}
+	set_err("prefill GEMM: no 256-row tile width (128 / 192 / 256 / 320) divides N, or the forced one does not");
+	return YALM_ERR_UNSUPPORTED;
+}
+
+int enqueue_moe_ffn(const PfForms &f, const MoeFfn &a, hipStream_t st) {
+	const int slots = a.T * a.K, sp = a.split ? 2 : 1;
+	// the tile kernels address A rows by 32-bit element offsets (as the dense launches do)
+	if ((size_t)slots * sp * std::max(a.hidden, a.dim) >= ((size_t)1 << 32)) {
+		set_err("mixture-of-experts prefill: rows x row length of an FFN operand exceeds 2^32 elements");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	TRY(launch_moe_router_rows<WF16>(a, st)); // (fp8 models: the gate's exact f16 upcast)
+	TRY(launch_moe_group(a.experts, slots, a.K, a.E, a.tabs, st));
+	if (a.act == YALM_SILU)
+		TRY(a.split ? (launch_moe_glu_t<1, true>(f, a, st)) : (launch_moe_glu_t<1, false>(f, a, st)));
+	else
+		TRY(a.split ? (launch_moe_glu_t<0, true>(f, a, st)) : (launch_moe_glu_t<0, false>(f, a, st)));
+	pf::E16StoreScaled e;
+	e.c = a.Y;
+	e.ldc = a.dim;
+	e.M = slots;
+	e.scale = ldexpf(1.0f, a.he);
+	TRY(launch_moe_plain(f, PG_W2, a.H, sp * a.hidden, slots, a.E, sp * a.hidden, a.hidden, a.w2, a.dim, e, a.tabs, nullptr,
+	                     st));
+	if (a.resid)
+		pf::moe_combine_kernel<true><<<a.T, 256, 0, st>>>(a.out, a.Y, a.tabs.slot_of, a.weights, a.K, a.dim);
+	else
+		pf::moe_combine_kernel<false><<<a.T, 256, 0, st>>>(a.out, a.Y, a.tabs.slot_of, a.weights, a.K, a.dim);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+int alloc_moe_tabs(yalm_decoder_s *d, pf::MoeGroupTabs &t, size_t slots, int E) {
+	TRY(pf_alloc(d, (void **)&t.slot_row, slots * 4));
+	TRY(pf_alloc(d, (void **)&t.slot_of, slots * 4));
+	TRY(pf_alloc(d, (void **)&t.tiles, (size_t)moe_tile_bound((int)slots, E) * 16));
+	TRY(pf_alloc(d, (void **)&t.ntiles, 4));
+	TRY(pf_alloc(d, (void **)&t.counts, (size_t)(E + 1) * 4));
+	return YALM_OK;
+}
+
 int check_prefill_shape(const yalm_config &c) {
 	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
 	if (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2) {
@@ -399,12 +547,25 @@ int ensure_bufs(yalm_decoder_s *d) {
 	const yalm_config &c = d->c;
 	const size_t cap = (size_t)c.max_seq_len, q_dim = (size_t)c.n_heads * c.head_dim;
 	const size_t ntiles = (size_t)c.vocab_size / pf::BN;
+	const size_t mk = d->moe_E > 0 ? (size_t)d->moe_K : 1, me = d->moe_E > 0 ? (size_t)d->moe_E : 1;
+	if (d->moe_E > 0 && cap * mk > (size_t)pf::MOE_GROUP_MAX) {
+		set_err("yalm_prefill: max_seq_len x n_experts_active exceeds 131072 (the expert grouping pass)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	TRY(pf_alloc(d, (void **)&b.X, cap * c.dim * 4));
 	TRY(pf_alloc(d, (void **)&b.Xn, cap * c.dim * 2 * 2));
 	// Q, O, H: [hi | lo] rows in the split-operand form, 2x wide
 	TRY(pf_alloc(d, (void **)&b.Q, cap * q_dim * 2 * 2));
 	TRY(pf_alloc(d, (void **)&b.O, cap * q_dim * 2 * 2));
-	TRY(pf_alloc(d, (void **)&b.H, cap * c.hidden_dim * 2 * 2));
+	TRY(pf_alloc(d, (void **)&b.H, cap * mk * c.hidden_dim * 2 * 2)); // experts: a row per (position, k)
+	if (d->moe_E > 0) { // the expert FFN's W2 outputs, the routing record, the grouping tables
+		TRY(pf_alloc(d, (void **)&b.Y, cap * mk * c.dim * 4));
+		TRY(pf_alloc(d, (void **)&b.rt_experts, (size_t)c.n_layers * cap * mk * 4));
+		TRY(pf_alloc(d, (void **)&b.rt_weights, (size_t)c.n_layers * cap * mk * 4));
+		pf::MoeGroupTabs t{};
+		TRY(alloc_moe_tabs(d, t, cap * mk, d->moe_E));
+		b.slot_row = t.slot_row, b.slot_of = t.slot_of, b.tiles = t.tiles, b.mtiles = t.ntiles, b.counts = t.counts;
+	}
 	TRY(pf_alloc(d, (void **)&b.tok, cap * 4));
 	TRY(pf_alloc(d, (void **)&b.tgt, cap * 4));
 	TRY(pf_alloc(d, (void **)&b.pmax, cap * ntiles * 4));
@@ -415,7 +576,8 @@ int ensure_bufs(yalm_decoder_s *d) {
 	TRY(pf_alloc(d, (void **)&b.range, (size_t)(c.n_layers + 1) * RG_N * 4));
 	if (c.weight_dtype == YALM_F8E5M2) { // the f16 copy of one layer's weights, or of the classifier
 		const size_t layer = ((size_t)q_dim + 2 * (size_t)c.n_kv_heads * c.head_dim) * c.dim + (size_t)c.dim * q_dim +
-							 3 * (size_t)c.dim * c.hidden_dim;
+							 3 * me * c.dim * c.hidden_dim + // (the stacked expert tensors
+								 (d->moe_E > 0 ? me * c.dim : 0); //  and the router's gate)
 		TRY(pf_alloc(d, (void **)&b.wdq, 2 * std::max(layer, (size_t)c.vocab_size * c.dim)));
 	}
 	{ // short-prompt split-K partials: the largest [KS][64][Np] of the layer's GEMMs
@@ -464,6 +626,7 @@ int enqueue_glu(yalm_decoder_s *d, const yalm_block_weights &w, int T, float hsc
 	                         : enqueue_glu_t<ACT, false>(d, w, T, hscale, range);
 }
 
+
 // The whole prefill on d->stream: T rows at positions pos0 .. pos0 + T - 1. hexp[l] (null:
 // all 0): layer l's GLU output is stored as f16(h * 2^-hexp[l]) and W2 adds 2^hexp[l] x its
 // product (exact power-of-two scales; yalm_prefill chooses them from the range guard).
@@ -497,7 +660,10 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	const int ks_wo = sk_pick_ks({{c.dim, q_dim, 1}}, TP);
 	const int ks_glu = sk_pick_ks({{2 * c.hidden_dim, c.dim, 1}}, TP);
 	const int ks_w2 = sk_pick_ks({{c.dim, c.hidden_dim, 1}}, TP);
-	const bool small = T <= SK_MAX_T && !f.no_skinny && !f.split && ks_qkv > 0 && ks_wo > 0 && ks_glu > 0 && ks_w2 > 0;
+	// (expert models: the attention half only; their FFN half runs the grouped large tiles at every T)
+	const bool moe = d->moe_E > 0;
+	const bool small = T <= SK_MAX_T && !f.no_skinny && !f.split && ks_qkv > 0 && ks_wo > 0 &&
+	                   (moe || (ks_glu > 0 && ks_w2 > 0));
 	// the split-operand precision form (yalm_set_prefill_precision): every activation operand
 	// [hi | lo] -- the normalised x of all three norms, Q, P (attention.h SPLIT), O and H --
 	// each GEMM over K = 2 x its depth with the B rows wrapping (prefill_gemm.h), so no operand
@@ -507,11 +673,18 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	const int bn_qkv_all = pick_bn(f, PG_QKV, T, q_dim + 2 * kv_dim, false);
 	for (int l = 0; l < c.n_layers; ++l) {
 		yalm_block_weights w = d->b[l];
+		const uint16_t *gate16 = nullptr; // fp8 expert models: the router's gate as f16
 		if (fp8) { // this layer's weights as f16 (exact), in the scratch the previous layer's GEMMs are done with
-			const uint16_t *p[7];
-			const size_t qd = (size_t)q_dim * c.dim, kd = (size_t)kv_dim * c.dim, hd = (size_t)c.hidden_dim * c.dim;
-			TRY(dequant(d, {{w.wq, qd}, {w.wk, kd}, {w.wv, kd}, {w.wo, qd}, {w.w1, hd}, {w.w2, hd}, {w.w3, hd}}, p, st));
+			const uint16_t *p[8];
+			const size_t qd = (size_t)q_dim * c.dim, kd = (size_t)kv_dim * c.dim;
+			const size_t hd = (size_t)c.hidden_dim * c.dim * (moe ? d->moe_E : 1);
+			if (moe) // + the router's gate: the same upcast, so the rows route exactly as the f16 twin's
+				TRY(dequant(d, {{w.wq, qd}, {w.wk, kd}, {w.wv, kd}, {w.wo, qd}, {w.w1, hd}, {w.w2, hd}, {w.w3, hd},
+				                {d->moegate[l], (size_t)d->moe_E * c.dim}}, p, st));
+			else
+				TRY(dequant(d, {{w.wq, qd}, {w.wk, kd}, {w.wv, kd}, {w.wo, qd}, {w.w1, hd}, {w.w2, hd}, {w.w3, hd}}, p, st));
 			w.wq = p[0], w.wk = p[1], w.wv = p[2], w.wo = p[3], w.w1 = p[4], w.w2 = p[5], w.w3 = p[6];
+			gate16 = moe ? p[7] : nullptr;
 		}
 		// normalised x as [hi | lo] (2 dim per row): hi is the q columns' A operand, hi + lo
 		// the k | v columns' (their cache rows then carry one f16 rounding, infer.cpp:299)
@@ -581,6 +754,20 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 		}
 		TRY(launch_rmsnorm(split, f, b.X, w.rms_ffn, c.dim, T, c.norm_eps, b.Xn, rg + RG_XFFN, st));
 		const float hscale = ldexpf(1.0f, -he);
+		if (moe) {
+			MoeFfn a{};
+			a.gate = fp8 ? (const void *)gate16 : d->moegate[l];
+			a.w1 = (const uint16_t *)w.w1, a.w2 = (const uint16_t *)w.w2, a.w3 = (const uint16_t *)w.w3;
+			a.E = d->moe_E, a.K = d->moe_K, a.hidden = c.hidden_dim, a.dim = c.dim, a.act = c.act, a.T = T;
+			a.X = b.X, a.normw = w.rms_ffn, a.eps = c.norm_eps, a.Xn = b.Xn, a.split = split, a.he = he;
+			a.range = rg + RG_H, a.H = b.H, a.Y = b.Y;
+			a.tabs = pf::MoeGroupTabs{b.slot_row, b.slot_of, b.tiles, b.mtiles, b.counts};
+			a.experts = b.rt_experts + (size_t)l * b.cap * d->moe_K;
+			a.weights = b.rt_weights + (size_t)l * b.cap * d->moe_K;
+			a.out = b.X, a.resid = true;
+			TRY(enqueue_moe_ffn(f, a, st));
+			continue;
+		}
 		if (small) {
 			const pf::BRowsGlu<64> bm{(const uint16_t *)w.w1, (const uint16_t *)w.w3};
 			TRY(launch_skinny(f, b.Xn, c.dim, T, c.dim, c.dim, bm, 2 * c.hidden_dim, ks_glu, 0, 2 * c.hidden_dim, b.skp,
@@ -660,10 +847,6 @@ int hd(HostDev &b, const void *host, size_t bytes) {
 
 extern "C" int yalm_prefill(yalm_decoder d, const int *tokens, int n, int pos0, float *logprobs) {
 	ARGCHK(d && tokens && n > 0 && pos0 >= 0, "yalm_prefill: bad argument");
-	if (d->moe_E > 0) { // callers fall back to per-position forwards on this code
-		set_err("yalm_prefill: batched prefill of a mixture-of-experts model is not implemented");
-		return YALM_ERR_UNSUPPORTED;
-	}
 	const yalm_config &c = d->c;
 	ARGCHK(pos0 + n <= c.max_seq_len, "yalm_prefill: pos0 + n must be <= max_seq_len (no sliding window in prefill)");
 	TRY(check_prefill_shape(c));
@@ -685,6 +868,7 @@ extern "C" int yalm_prefill(yalm_decoder d, const int *tokens, int n, int pos0, 
 	std::vector<int> hexp(L, 0);
 	std::vector<unsigned> rg((size_t)(L + 1) * RG_N);
 	b.last_passes = b.last_scaled = 0;
+	b.last_n = 0;
 	for (int pass = 1;; ++pass) {
 		HIPCHK(hipMemsetAsync(b.range, 0, rg.size() * 4, d->stream));
 		TRY(enqueue_prefill(d, n, pos0, logprobs != nullptr, hexp.data()));
@@ -717,6 +901,7 @@ extern "C" int yalm_prefill(yalm_decoder d, const int *tokens, int n, int pos0, 
 	}
 	for (int l = 0; l < L; ++l)
 		b.last_scaled += hexp[l] > 0;
+	b.last_n = n;
 	if (logprobs)
 		HIPCHK(hipMemcpy(logprobs, b.lp, sizeof(float) * n, hipMemcpyDeviceToHost));
 	return YALM_OK;
@@ -733,10 +918,6 @@ extern "C" int yalm_prefill_info(yalm_decoder d, int *passes, int *scaled_layers
 
 extern "C" int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms) {
 	ARGCHK(d && n > 0 && iters > 0 && avg_ms, "yalm_prefill_time: bad argument");
-	if (d->moe_E > 0) {
-		set_err("yalm_prefill_time: batched prefill of a mixture-of-experts model is not implemented");
-		return YALM_ERR_UNSUPPORTED;
-	}
 	const yalm_config &c = d->c;
 	ARGCHK(n <= c.max_seq_len, "yalm_prefill_time: n > max_seq_len");
 	TRY(check_prefill_shape(c));
@@ -781,6 +962,138 @@ extern "C" int yalm_gemm_f16(float *c, const uint16_t *a, const uint16_t *w, int
 	                 nullptr));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(c, dc.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+extern "C" int yalm_prefill_routing(yalm_decoder d, int *experts, float *weights) {
+	ARGCHK(d && d->moe_E > 0, "yalm_prefill_routing: not a mixture-of-experts decoder");
+	ARGCHK(d->pf.last_n > 0, "yalm_prefill_routing: no prefill has run on this decoder");
+	const PrefillBufs &b = d->pf;
+	const size_t n = (size_t)b.last_n, L = (size_t)d->c.n_layers, K = (size_t)d->moe_K;
+	std::vector<int> tmp(n * K);
+	for (size_t l = 0; l < L; ++l) { // device record [n_layers][cap][K] -> [n][n_layers][K]
+		if (experts) {
+			HIPCHK(hipMemcpy(tmp.data(), b.rt_experts + l * b.cap * K, n * K * 4, hipMemcpyDeviceToHost));
+			for (size_t t = 0; t < n; ++t)
+				memcpy(experts + (t * L + l) * K, tmp.data() + t * K, K * 4);
+		}
+		if (weights) {
+			HIPCHK(hipMemcpy(tmp.data(), b.rt_weights + l * b.cap * K, n * K * 4, hipMemcpyDeviceToHost));
+			for (size_t t = 0; t < n; ++t)
+				memcpy(weights + (t * L + l) * K, tmp.data() + t * K, K * 4);
+		}
+	}
+	return YALM_OK;
+}
+
+namespace {
+int hd_tabs(HostDev (&m)[5], pf::MoeGroupTabs &t, size_t slots, int E) {
+	TRY(hd(m[0], nullptr, slots * 4));
+	TRY(hd(m[1], nullptr, slots * 4));
+	TRY(hd(m[2], nullptr, (size_t)moe_tile_bound((int)slots, E) * 16));
+	TRY(hd(m[3], nullptr, 4));
+	TRY(hd(m[4], nullptr, (size_t)(E + 1) * 4));
+	t = pf::MoeGroupTabs{(int *)m[0].p, (int *)m[1].p, (int *)m[2].p, (int *)m[3].p, (int *)m[4].p};
+	return YALM_OK;
+}
+} // namespace
+
+extern "C" int yalm_moe_gemm_f16(float *c, const uint16_t *a, const uint16_t *w, const int *expert_of_row, int M, int N,
+                                 int K, int E) {
+	ARGCHK(c && a && w && expert_of_row && M > 0 && N > 0 && K > 0, "yalm_moe_gemm_f16: bad argument");
+	ARGCHK(E >= 1 && E <= MOE_MAX_EXPERTS, "yalm_moe_gemm_f16: 1 <= E <= 64");
+	ARGCHK(N % pf::BN == 0 && K % pf::BK == 0, "yalm_moe_gemm_f16: N % 128 and K % 64 must be 0");
+	for (int r = 0; r < M; ++r)
+		ARGCHK(expert_of_row[r] >= 0 && expert_of_row[r] < E, "yalm_moe_gemm_f16: expert index out of range");
+	HostDev da, dw, de, dy, dc, tm[5];
+	pf::MoeGroupTabs tabs{};
+	TRY(hd(da, a, (size_t)M * K * 2));
+	TRY(hd(dw, w, (size_t)E * N * K * 2));
+	TRY(hd(de, expert_of_row, (size_t)M * 4));
+	TRY(hd(dy, nullptr, (size_t)M * N * 4));
+	TRY(hd(dc, nullptr, (size_t)M * N * 4));
+	TRY(hd_tabs(tm, tabs, M, E));
+	const PfForms f = g_test_forms;
+	TRY(launch_moe_group((const int *)de.p, M, 1, E, tabs, nullptr));
+	pf::E16StoreScaled e;
+	e.c = (float *)dy.p;
+	e.ldc = N;
+	e.M = M;
+	TRY(launch_moe_plain(f, PG_TEST, (const uint16_t *)da.p, K, M, E, K, K, (const uint16_t *)dw.p, N, e, tabs,
+	                     tabs.slot_row, nullptr));
+	pf::moe_combine_kernel<false><<<M, 256, 0, nullptr>>>((float *)dc.p, (const float *)dy.p, tabs.slot_of, nullptr, 1, N);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(c, dc.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+extern "C" int yalm_moe_ffn_rows(float *xout, int *experts, float *weights, const float *x, int T, const void *moegate,
+                                 const void *w1, const void *w2, const void *w3, int n_experts, int n_active,
+                                 int hidden_dim, int dim, int act, int dtype) {
+	ARGCHK(xout && x && T > 0 && moegate && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "yalm_moe_ffn_rows: bad argument");
+	ARGCHK(act == YALM_SILU || act == YALM_GELU, "yalm_moe_ffn_rows: bad activation");
+	ARGCHK(n_experts >= 1 && n_experts <= MOE_MAX_EXPERTS && n_active >= 1 && n_active <= n_experts,
+	       "yalm_moe_ffn_rows: 1 <= n_experts_active <= n_experts <= 64");
+	if (dtype != YALM_F16 && dtype != YALM_F8E5M2) {
+		set_err("yalm_moe_ffn_rows: f16 or fp8 (E5M2) weights only (MFMA f16 operands)");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	if (dim % pf::BN || hidden_dim % pf::BN) {
+		set_err("yalm_moe_ffn_rows: dims must be multiples of 128");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const size_t wb = dtype == YALM_F16 ? 2 : 1, we = (size_t)n_experts * hidden_dim * dim;
+	const size_t slots = (size_t)T * n_active;
+	const PfForms f = g_test_forms;
+	const int sp = f.split ? 2 : 1;
+	HostDev dx, dg, d1, d2, d3, dq, dxn, dh, dy, dout, dsel, dwts, drange, tm[5];
+	MoeFfn a{};
+	TRY(hd(dx, x, (size_t)T * dim * 4));
+	TRY(hd(dg, moegate, wb * n_experts * dim));
+	TRY(hd(d1, w1, wb * we));
+	TRY(hd(d2, w2, wb * we));
+	TRY(hd(d3, w3, wb * we));
+	TRY(hd(dxn, nullptr, (size_t)T * dim * 2 * sp));
+	TRY(hd(dh, nullptr, slots * hidden_dim * 2 * sp));
+	TRY(hd(dy, nullptr, slots * dim * 4));
+	TRY(hd(dout, nullptr, (size_t)T * dim * 4));
+	TRY(hd(dsel, nullptr, slots * 4));
+	TRY(hd(dwts, nullptr, slots * 4));
+	TRY(hd(drange, nullptr, 4));
+	TRY(hd_tabs(tm, a.tabs, slots, n_experts));
+	a.w1 = (const uint16_t *)d1.p, a.w2 = (const uint16_t *)d2.p, a.w3 = (const uint16_t *)d3.p;
+	if (dtype == YALM_F8E5M2) { // the exact upcast, as a decoder's prefill
+		const uint16_t *p[4];
+		const size_t ge = (size_t)n_experts * dim;
+		TRY(hd(dq, nullptr, (3 * we + ge) * 2));
+		TRY(dequant_into((uint16_t *)dq.p, {{d1.p, we}, {d2.p, we}, {d3.p, we}, {dg.p, ge}}, p, nullptr));
+		a.w1 = p[0], a.w2 = p[1], a.w3 = p[2], a.gate = p[3];
+	}
+	if (f.split)
+		pf::moe_rows_f16_kernel<true><<<T, 256, 0, nullptr>>>((const float *)dx.p, dim, (uint16_t *)dxn.p);
+	else
+		pf::moe_rows_f16_kernel<false><<<T, 256, 0, nullptr>>>((const float *)dx.p, dim, (uint16_t *)dxn.p);
+	HIPCHK(hipGetLastError());
+	if (dtype == YALM_F16)
+		a.gate = dg.p;
+	a.E = n_experts, a.K = n_active, a.hidden = hidden_dim, a.dim = dim, a.act = act, a.T = T;
+	a.X = (const float *)dx.p, a.normw = nullptr, a.eps = 0.f, a.Xn = (const uint16_t *)dxn.p, a.split = f.split, a.he = 0;
+	a.range = (unsigned *)drange.p, a.H = (uint16_t *)dh.p, a.Y = (float *)dy.p;
+	a.experts = (int *)dsel.p, a.weights = (float *)dwts.p, a.out = (float *)dout.p, a.resid = false;
+	TRY(enqueue_moe_ffn(f, a, nullptr));
+	HIPCHK(hipDeviceSynchronize());
+	unsigned rg = 0;
+	HIPCHK(hipMemcpy(&rg, drange.p, 4, hipMemcpyDeviceToHost));
+	if (rg) {
+		set_err("yalm_moe_ffn_rows: the GLU output exceeds the f16 range of the MFMA operands");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	HIPCHK(hipMemcpy(xout, dout.p, (size_t)T * dim * 4, hipMemcpyDeviceToHost));
+	if (experts)
+		HIPCHK(hipMemcpy(experts, dsel.p, slots * 4, hipMemcpyDeviceToHost));
+	if (weights)
+		HIPCHK(hipMemcpy(weights, dwts.p, slots * 4, hipMemcpyDeviceToHost));
 	return YALM_OK;
 }
 

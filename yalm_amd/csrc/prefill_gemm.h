@@ -328,6 +328,25 @@ struct E16Logits {
 	}
 };
 
+// ---------------------------------------------------------------- row groups
+// NoGroup: the plain GEMM (M rows, tile tm = rows 256 tm ..). RowGroups (moe_prefill.h, the
+// mixture-of-experts FFN): the M tiles come from a table built on the device -- tile i =
+// {expert, first slot, rows (<= 256), 0} -- and *ntiles of them exist; the launch is sized
+// for a host-side bound and every workgroup / persistent-loop iteration past the device's
+// count exits at once. A tile's B rows are those of its expert (bstride elements apart),
+// its A row of slot s is rowmap[s] (null: s itself), its outputs are rows "slot" of C.
+struct NoGroup {
+	static constexpr bool ON = false;
+};
+struct RowGroups {
+	static constexpr bool ON = true;
+	const int *tiles;  // [bound][4]
+	const int *ntiles; // [1]
+	const int *rowmap; // [slots] or null
+	size_t bstride;
+	__device__ __forceinline__ int arow(int s) const { return rowmap ? rowmap[s] : s; }
+};
+
 // ---------------------------------------------------------------- the kernel
 // Stage ROWS x 64 f16 of one operand into a lane-linear LDS image by LDS-DMA: wave
 // instruction = 8 rows x 128 B; lane l writes row 8 rb + (l >> 3), chunk l & 7 and
@@ -354,9 +373,9 @@ __device__ __forceinline__ half8_t g16frag(const uint16_t *lds, int r, int s, in
 }
 
 // C tile [256][BN] of C = A · B^T, B rows through BMAP. 8 waves as WM x (8 / WM).
-template <class EPI, class BMAP, int BN, int WM>
+template <class EPI, class BMAP, int BN, int WM, class GRP = NoGroup>
 __global__ __launch_bounds__(G_THREADS, 1) void gemm16_kernel(const uint16_t *__restrict__ A, int lda, int M, int K,
-                                                             int kb, BMAP bm, int N, EPI epi, int c0) {
+                                                             int kb, BMAP bm, int N, EPI epi, int c0, GRP grp) {
 	constexpr int WN = 8 / WM;
 	constexpr int TM = G_BM / WM, TN = BN / WN; // per-wave output
 	constexpr int FI = TM / 16, FJ = TN / 16;
@@ -370,24 +389,42 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm16_kernel(const uint16_t *__
 
 	// XCD-aware tile order (bijective remap, cdna_hip_programming.md §5 'XCD swizzle'):
 	// the workgroups sharing an XCD walk down M for fixed column panels (B reused in L2)
-	const int tiles_m = (M + G_BM - 1) / G_BM, tiles_n = N / BN;
+	int tiles_m = (M + G_BM - 1) / G_BM;
+	if constexpr (GRP::ON)
+		tiles_m = *grp.ntiles; // the device's count (the grid covers the host's bound)
+	const int tiles_n = N / BN;
 	const int nwg = tiles_m * tiles_n;
 	int wg = blockIdx.x;
+	if constexpr (GRP::ON)
+		if (wg >= nwg)
+			return;
 	{
 		const int q = nwg / 8, rr = nwg % 8, xcd = wg % 8, idx = wg / 8;
 		wg = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
 	}
 	const int tm = wg % tiles_m, tn = wg / tiles_m;
-	const int row0 = tm * G_BM;
+	int row0 = tm * G_BM, rend = M; // the tile's rows are row0 .. min(row0 + 256, rend) - 1
+	size_t boff = 0;
+	if constexpr (GRP::ON) {
+		const int *tt = grp.tiles + 4 * tm;
+		row0 = tt[1];
+		rend = row0 + tt[2];
+		boff = (size_t)tt[0] * grp.bstride;
+	}
 	const int colB = c0 + tn * (BN / BMAP::COLS_PER_TILE_DIV); // first B column (plain) / hidden column (GLU)
 
 	const uint16_t *ap[NIA], *bp[NIB];
 #pragma unroll
-	for (int i = 0; i < NIA; ++i)
-		ap[i] = A + (size_t)min(row0 + (wave * NIA + i) * 8 + (lane >> 3), M - 1) * lda;
+	for (int i = 0; i < NIA; ++i) {
+		const int r = min(row0 + (wave * NIA + i) * 8 + (lane >> 3), rend - 1);
+		if constexpr (GRP::ON)
+			ap[i] = A + (size_t)grp.arow(r) * lda;
+		else
+			ap[i] = A + (size_t)r * lda;
+	}
 #pragma unroll
 	for (int i = 0; i < NIB; ++i)
-		bp[i] = bm.row(colB, (wave * NIB + i) * 8 + (lane >> 3), kb);
+		bp[i] = bm.row(colB, (wave * NIB + i) * 8 + (lane >> 3), kb) + boff;
 
 	f32x4_t acc[FI][FJ];
 #pragma unroll
@@ -432,6 +469,8 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm16_kernel(const uint16_t *__
 		raw_barrier();                                     // ... everyone's; everyone done reading tile kt
 	}
 	EPI e = epi;
+	if constexpr (GRP::ON)
+		e.M = rend;
 	if constexpr (EPI::NEEDS_LDS)
 		e.red = (float *)smem; // the staging buffers are free after the last barrier
 	const int n0 = BMAP::COLS_PER_TILE_DIV == 1 ? colB + wc * TN : colB + wc * (TN / 2);
@@ -489,10 +528,10 @@ constexpr int P8_HT = 128 * G_BK; // f16 per A half-tile (128 rows)
 // (twice the work) come first in dispatch order, each class keeping its own XCD-aware
 // order: with one workgroup per tile the hardware then hands the K tiles to the CUs the
 // K2 tiles leave free (longest first).
-template <class EPI, class BMAP, int FJ0 = 2, int FJ1 = 2>
+template <class EPI, class BMAP, int FJ0 = 2, int FJ1 = 2, class GRP = NoGroup>
 __global__ __launch_bounds__(G_THREADS, 1) void gemm8p_kernel(const uint16_t *__restrict__ A, int lda, int M, int K,
                                                              int kb, BMAP bm, int N, EPI epi, int c0, int c_split,
-                                                             int K2) {
+                                                             int K2, GRP grp) {
 	constexpr int FI = 8, FJ = FJ0 + FJ1, TM = 128, TN = 16 * FJ, BN = 4 * TN;
 	constexpr int HB0 = 64 * FJ0 * G_BK, HB1 = 64 * FJ1 * G_BK; // f16 per B half-tile
 	constexpr int OFF[4] = {0, P8_HT, 2 * P8_HT, 2 * P8_HT + HB0}; // Am0, Am1, Bn0, Bn1 in a buffer
@@ -504,7 +543,10 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm8p_kernel(const uint16_t *__
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const int wr = wave >> 2, wc = wave & 3;
 
-	const int tiles_m = (M + G_BM - 1) / G_BM, tiles_n = N / BN;
+	int tiles_m = (M + G_BM - 1) / G_BM;
+	if constexpr (GRP::ON)
+		tiles_m = *grp.ntiles; // the device's count: blocks and loop iterations past it do nothing
+	const int tiles_n = N / BN;
 	const int nwg = tiles_m * tiles_n;
 	const int tn_split = c_split / BN;             // column tiles with depth K
 	const int nwg2 = tiles_m * (tiles_n - tn_split); // tiles with depth K2, dispatched first
@@ -523,7 +565,14 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm8p_kernel(const uint16_t *__
 		}
 		const int tm = wg % tiles_m, tn = wg / tiles_m + (deep ? tn_split : 0);
 		const int Kt = deep ? K2 : K;
-		const int row0 = tm * G_BM;
+		int row0 = tm * G_BM, rend = M; // the tile's rows are row0 .. min(row0 + 256, rend) - 1
+		size_t boff = 0;
+		if constexpr (GRP::ON) {
+			const int *tt = grp.tiles + 4 * tm;
+			row0 = tt[1];
+			rend = row0 + tt[2];
+			boff = (size_t)tt[0] * grp.bstride;
+		}
 		const int colB = c0 + tn * (BN / BMAP::COLS_PER_TILE_DIV); // c0: first column of this launch
 
 		// staging sources: instruction i of a half-tile covers its rows lr = (NI wave + i) * 8
@@ -536,20 +585,25 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm8p_kernel(const uint16_t *__
 			const int lr = (2 * wave + i) * 8 + (lane >> 3);
 			const int sw = 8 * ((lane & 7) ^ (lr & 7));
 			const int ra = lr < 64 ? lr : lr + 64; // Am0 tile row; Am1 = + 64
-			aoff[0][i] = (uint32_t)min(row0 + ra, M - 1) * lda + sw;
-			aoff[1][i] = (uint32_t)min(row0 + ra + 64, M - 1) * lda + sw;
+			if constexpr (GRP::ON) {
+				aoff[0][i] = (uint32_t)grp.arow(min(row0 + ra, rend - 1)) * lda + sw;
+				aoff[1][i] = (uint32_t)grp.arow(min(row0 + ra + 64, rend - 1)) * lda + sw;
+			} else {
+				aoff[0][i] = (uint32_t)min(row0 + ra, M - 1) * lda + sw;
+				aoff[1][i] = (uint32_t)min(row0 + ra + 64, M - 1) * lda + sw;
+			}
 		}
 	#pragma unroll
 		for (int i = 0; i < FJ0; ++i) {
 			const int lr = (FJ0 * wave + i) * 8 + (lane >> 3);
 			const int sw = 8 * ((lane & 7) ^ (lr & 7));
-			bp[0][i] = bm.row(colB, (lr / (16 * FJ0)) * TN + lr % (16 * FJ0), kb) + sw;
+			bp[0][i] = bm.row(colB, (lr / (16 * FJ0)) * TN + lr % (16 * FJ0), kb) + boff + sw;
 		}
 	#pragma unroll
 		for (int i = 0; i < FJ1; ++i) {
 			const int lr = (FJ1 * wave + i) * 8 + (lane >> 3);
 			const int sw = 8 * ((lane & 7) ^ (lr & 7));
-			bp[1][i] = bm.row(colB, (lr / (16 * FJ1)) * TN + 16 * FJ0 + lr % (16 * FJ1), kb) + sw;
+			bp[1][i] = bm.row(colB, (lr / (16 * FJ1)) * TN + 16 * FJ0 + lr % (16 * FJ1), kb) + boff + sw;
 		}
 		// half-tile h (0 Am0, 1 Am1, 2 Bn0, 3 Bn1) of K tile kt into buffer buf
 		auto stage = [&](int buf, int h, int kt) {
@@ -703,6 +757,8 @@ __global__ __launch_bounds__(G_THREADS, 1) void gemm8p_kernel(const uint16_t *__
 			asm volatile("s_barrier" ::: "memory"); // rows back in step
 		asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
 		EPI e = epi;
+		if constexpr (GRP::ON)
+			e.M = rend;
 		if constexpr (EPI::NEEDS_LDS)
 			e.red = (float *)smem;
 		const int n0 = BMAP::COLS_PER_TILE_DIV == 1 ? colB + wc * TN : colB + wc * (TN / 2);

@@ -127,6 +127,7 @@ struct Model {
 	// Batched MFMA prefill of tokens[0..n) at positions pos0.. (yalm_prefill):
 	// fills the KV cache; logprobs (may be null) gets log p(tokens[i+1]) per
 	// position; split: the split-operand precision form (yalm_set_prefill_precision).
+	// Mixture-of-experts models take the same call (the grouped expert FFN, moe_prefill.h).
 	// Returns false when this model's shape/dtype has no prefill path (f16 / fp8
 	// weights, dims multiple of 128, head_dim 64|128), its activations leave the
 	// prefill's f16 operand range, or YALM_NO_PREFILL=1; the caller then runs the

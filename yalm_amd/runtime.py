@@ -99,6 +99,9 @@ _sig("yalm_decoder_create_moe", c_int, [ctypes.POINTER(Config), c_void_p, ctypes
                                          c_void_p, ctypes.POINTER(c_void_p)])
 _sig("yalm_moe_routing", c_int, [c_void_p, c_void_p, c_void_p])
 _sig("yalm_moe_ffn", c_int, [c_void_p] * 8 + [c_int] * 6)
+_sig("yalm_prefill_routing", c_int, [c_void_p, c_void_p, c_void_p])
+_sig("yalm_moe_gemm_f16", c_int, [c_void_p] * 4 + [c_int] * 4)
+_sig("yalm_moe_ffn_rows", c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 4 + [c_int] * 6)
 _sig("yalm_decoder_destroy", c_int, [c_void_p])
 _sig("yalm_forward", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
 _sig("yalm_generate_greedy", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
@@ -148,6 +151,7 @@ EXPORTED = [
     "yalm_argmax", "yalm_set_prefill_forms", "yalm_attn_wo_plan", "yalm_graph_kernels",
     "yalm_stream_create_cu_part", "yalm_decoder_set_launch", "yalm_prefill_info", "yalm_set_prefill_precision",
     "yalm_decoder_create_moe", "yalm_moe_routing", "yalm_moe_ffn",
+    "yalm_prefill_routing", "yalm_moe_gemm_f16", "yalm_moe_ffn_rows",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -228,6 +232,22 @@ def moe_ffn(x, moegate, w1, w2, w3, n_active: int, act: int, dtype: int):
     return out, experts[:n_active], weights[:n_active]
 
 
+def moe_ffn_rows(x, moegate, w1, w2, w3, n_active: int, act: int, dtype: int):
+    """yalm_moe_ffn_rows: the batched router and the grouped expert FFN of the prefill on
+    T already-normalised rows x (T, dim) (no norm, no residual). Returns (xout (T, dim),
+    experts (T, K), weights (T, K)), the routing in selection order."""
+    n_experts, hidden_dim, dim = w1.shape
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    T = x.shape[0]
+    moegate, w1, w2, w3 = (np.ascontiguousarray(a) for a in (moegate, w1, w2, w3))
+    out = np.zeros((T, dim), np.float32)
+    experts = np.zeros((T, max(n_active, 1)), np.int32)
+    weights = np.zeros((T, max(n_active, 1)), np.float32)
+    check(lib.yalm_moe_ffn_rows(_ptr(out), _ptr(experts), _ptr(weights), _ptr(x), T, _ptr(moegate), _ptr(w1),
+                                _ptr(w2), _ptr(w3), n_experts, n_active, hidden_dim, dim, act, dtype))
+    return out, experts, weights
+
+
 def stream_envelope(nbytes: int, iters: int = 16) -> float:
     """ms of one pure HBM read pass over nbytes (yalm_stream_envelope)."""
     ms = c_float()
@@ -267,6 +287,18 @@ def gemm_f16(a: np.ndarray, w: np.ndarray) -> np.ndarray:
     (M, K), N = a.shape, w.shape[0]
     c = np.zeros((M, N), np.float32)
     check(lib.yalm_gemm_f16(_ptr(c), _ptr(a), _ptr(w), M, N, K))
+    return c
+
+
+def moe_gemm_f16(a: np.ndarray, w: np.ndarray, expert_of_row: np.ndarray) -> np.ndarray:
+    """The grouped MFMA GEMM of the mixture-of-experts prefill: row r of a (M, K) f16 against
+    w[expert_of_row[r]] of w (E, N, K) f16 -> (M, N) f32 (yalm_moe_gemm_f16)."""
+    a = np.ascontiguousarray(a, dtype=np.float16)
+    w = np.ascontiguousarray(w, dtype=np.float16)
+    e = np.ascontiguousarray(expert_of_row, dtype=np.int32)
+    (M, K), (E, N, _) = a.shape, w.shape
+    c = np.zeros((M, N), np.float32)
+    check(lib.yalm_moe_gemm_f16(_ptr(c), _ptr(a), _ptr(w), _ptr(e), M, N, K, E))
     return c
 
 
@@ -507,7 +539,16 @@ class Decoder:
         tok = np.ascontiguousarray(tokens, dtype=np.int32)
         out = np.zeros(len(tok), np.float32) if logprobs else None
         check(lib.yalm_prefill(self.h, _ptr(tok), len(tok), pos0, _ptr(out) if logprobs else None))
+        self._prefill_n = len(tok)
         return out
+
+    def prefill_routing(self):
+        """(experts, weights), each (n, n_layers, n_experts_active): the routing of the last
+        prefill's n positions, in selection order (yalm_prefill_routing)."""
+        shape = (getattr(self, "_prefill_n", 0), self.cfg.n_layers, max(self.cfg.n_experts_active, 1))
+        experts, weights = np.zeros(shape, np.int32), np.zeros(shape, np.float32)
+        check(lib.yalm_prefill_routing(self.h, _ptr(experts), _ptr(weights)))
+        return experts, weights
 
     def set_prefill_precision(self, mode: int) -> None:
         """PREFILL_FAST (f16 activation operands) or PREFILL_SPLIT (every operand [hi | lo])."""
