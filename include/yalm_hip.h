@@ -123,6 +123,34 @@ int yalm_forward(yalm_decoder d, int token, int pos, int mode, float *logits_hos
  * launched back to back (eagerly: measured 0.3-0.5% faster than replaying the
  * per-token graph, whose kernel count yalm_graph_kernels still reports). */
 int yalm_generate_greedy(yalm_decoder d, int token, int pos, int n_steps, int *out_tokens);
+/* Device-side temperature / top-k / top-p sampling (csrc/sampler.h). The rule is in integers,
+ * so the same logits, parameters and uniform give the same token whatever the reduction order:
+ * m = the first-maximum logit; w_i = expf((l_i - m) / temperature) (sampler.cpp:50, f32),
+ * q_i = (uint64) ldexpf(w_i, 40), 0 when w_i is not finite and positive; order = logit
+ * descending (as order-preserving 32-bit keys), index ascending among equal logits; top_k > 0
+ * keeps the first min(top_k, n) of that order (q sum S_k), top_p < 1 then the shortest prefix of
+ * those whose q sum reaches min(S_k, max(1, ceil((double)top_p * S_k))); with S the kept q sum
+ * and t = min(S, max(1, ceil((double)u * S))) the token is the first kept index, ascending,
+ * whose inclusive kept prefix sum reaches t (sampler.cpp:53-57); S == 0: the first-maximum
+ * argmax. top_k = 0 and top_p = 1 is the reference's temperature sampler up to rounding at the
+ * boundaries of the cumulative distribution. */
+typedef struct yalm_sampling {
+	float temperature; /* > 0, finite */
+	int top_k;         /* >= 0; 0 = off */
+	float top_p;       /* in (0, 1]; 1 = off */
+} yalm_sampling;
+/* yalm_generate_greedy with the token of each step drawn by the rule above instead of the
+ * argmax: one launch of one workgroup in the argmax launch's place (the step has the greedy
+ * step's launch count, yalm_graph_kernels mode 3), parameters and uniforms read from device
+ * memory. uniforms: host array of n_steps values in [0, 1], one consumed per step.
+ * Dense and mixture-of-experts decoders, every weight dtype, any pos (the sliding window past
+ * max_seq_len as in yalm_forward); yalm_device_step / yalm_device_tokens / yalm_enqueue_greedy
+ * continue from it as after yalm_generate_greedy. YALM_ERR_ARG: temperature <= 0 or not
+ * finite, top_k < 0, top_p outside (0, 1], a uniform outside [0, 1], n_steps above the token
+ * buffer (65536), a vocabulary above 131072. YALM_ERR_UNSUPPORTED on tensor-parallel decoders
+ * (yalm_decoder_create_tp / _tp_ipc): their vocabulary is sharded over the ranks. */
+int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
+                          const float *uniforms, int *out_tokens);
 /* Launch-only variant for benchmarking: enqueue n_steps greedy steps
  * continuing from the decoder's device-resident token/pos; no sync. */
 int yalm_enqueue_greedy(yalm_decoder d, int n_steps);
@@ -152,7 +180,10 @@ int yalm_get_logits(yalm_decoder d, float *host);
  * with the same iters), 8 = the fused attention + Wo
  * launch (yalm_decoder_attn_wo; each timed launch gets a fresh step epoch, so its
  * Wo waves wait for the heads as in a real forward; the epoch-bump launches are
- * timed separately and subtracted). Used by bench.py for the roofline of the
+ * timed separately and subtracted), 10 = the sampling launch of yalm_generate_sampled on
+ * the decoder's current logits, with the parameters of the last such call (before any:
+ * temperature 1, no truncation) and its first uniform; it commits into a scratch step
+ * state, not the decoder's. Used by bench.py for the roofline of the
  * dominant kernel. */
 int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms);
 /* The same-process streaming envelope: average ms of one pure read-only pass over
@@ -168,7 +199,7 @@ int yalm_stream_envelope(size_t bytes, int iters, float *avg_ms);
  * Drops captured graphs (re-captured on next use). Tuning/ablation hook. */
 int yalm_set_gemv_config(yalm_decoder d, int kind, int threads, int unroll, int gpw);
 /* Kernel launches per forward of graph `mode` (0 = HYDRATE, 1 = OUTPUT_LOGITS, 2 = the
- * device greedy step): *kernels = kernel nodes of the captured per-token hipGraph (RCCL
+ * device greedy step, 3 = the device sampled step of yalm_generate_sampled): *kernels = kernel nodes of the captured per-token hipGraph (RCCL
  * collectives count as the kernels they capture), *nodes (may be NULL) = all nodes. Test
  * and measurement hook (tensor parallelism adds no exchange launches over IPC). */
 int yalm_graph_kernels(yalm_decoder d, int mode, int *kernels, int *nodes);
@@ -375,6 +406,13 @@ int yalm_moe_ffn(float *xout, int *experts, float *weights, const float *x, cons
  * runs the tensor-parallel form instead: one per-shard first max as a (value,
  * global index) pair over each n / n_shards slice, then argmax_pick_kernel. */
 int yalm_argmax(const float *logits, int n, int n_shards, int *out);
+
+/* Device sampling test hook (host pointers, synchronous): n_draws draws from the n <= 131072
+ * logits by the rule of yalm_generate_sampled, one launch of its kernel per draw, draw i with
+ * uniforms[i]. kept (n_draws, may be NULL): the kept-set size of each draw; weights_out (n,
+ * may be NULL): the q_i the kernel used. */
+int yalm_sample(const float *logits, int n, const yalm_sampling *s, const float *uniforms, int n_draws,
+                int *out_tokens, int *kept, uint64_t *weights_out);
 
 /* Prefill building blocks (host pointers, synchronous):
  * c[M][N] f32 = a[M][K] f16 · w[N][K]^T f16 (the MFMA GEMM; N % 128 == 0, K % 64 == 0). */

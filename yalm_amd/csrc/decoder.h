@@ -106,7 +106,7 @@ struct PfForms {
 PfForms pf_forms_default(); // prefill.hip: the production forms (A/B build: YALM_PF_FORMS)
 
 // ------------------------------------------------------------------ decoder
-enum { GRAPH_HYDRATE = 0, GRAPH_LOGITS = 1, GRAPH_GREEDY = 2, N_GRAPHS = 3 };
+enum { GRAPH_HYDRATE = 0, GRAPH_LOGITS = 1, GRAPH_GREEDY = 2, GRAPH_SAMPLED = 3, N_GRAPHS = 4 };
 
 struct yalm_decoder_s {
 	yalm_config c{};
@@ -121,6 +121,11 @@ struct yalm_decoder_s {
 	unsigned long long *part = nullptr; // attention chunk partials as {value, tag} granules (attention.h)
 	int *tokens = nullptr;
 	int tokens_cap = 0;
+	// device sampling (sampler.h, yalm_generate_sampled): the step's parameters and the call's
+	// uniforms live in device memory, so the sampled step is as static as the greedy one
+	struct SampleParams *smp_params = nullptr;
+	float *smp_u = nullptr;          // [tokens_cap], one consumed per step (index StepState::n_gen)
+	StepState *smp_step = nullptr;   // yalm_time_kernel id 10 commits here, not into the decode state
 	float *logits_pinned = nullptr;
 	std::vector<void *> dev_allocs;
 	hipGraph_t graph[N_GRAPHS] = {};

@@ -23,6 +23,7 @@
 #include "gemv.h"
 #include "misc_kernels.h"
 #include "moe.h"
+#include "sampler.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -953,6 +954,11 @@ static int enqueue_forward(yalm_decoder_s *d, int which) {
 		}
 		HIPCHK(hipMemcpyAsync(d->logits_pinned, d->logits, sizeof(float) * d->vocab_full, hipMemcpyDeviceToHost,
 		                      d->stream));
+	} else if (which == GRAPH_SAMPLED) { // one GPU only (yalm_generate_sampled checks): the whole vocabulary is here
+		sample_kernel<<<1, SMP_THREADS, 0, d->stream>>>(d->logits, d->c.vocab_size, d->smp_params, d->smp_u,
+		                                                d->tokens_cap, d->step, d->tokens, d->tokens_cap, nullptr,
+		                                                nullptr);
+		HIPCHK(hipGetLastError());
 	} else if (!d->comm) {
 		argmax_kernel<<<1, 1024, 0, d->stream>>>(d->logits, d->c.vocab_size, d->step, d->tokens, d->tokens_cap);
 		HIPCHK(hipGetLastError());
@@ -1040,7 +1046,7 @@ int dalloc(yalm_decoder_s *d, void **p, size_t bytes) {
 // One forward of graph `which`: a graph replay, or the same kernels launched
 // eagerly when d->eager.
 static int replay(yalm_decoder_s *d, int which) {
-	if (d->eager || (which == GRAPH_GREEDY && d->greedy_eager))
+	if (d->eager || ((which == GRAPH_GREEDY || which == GRAPH_SAMPLED) && d->greedy_eager))
 		return enqueue_forward(d, which);
 	HIPCHK(hipGraphLaunch(d->exec[which], d->stream));
 	if (d->graph_sync)
@@ -1120,7 +1126,10 @@ static int create_decoder(const yalm_config *config, const yalm_model_weights *w
 	    (r = dalloc(d, (void **)&d->amax, sizeof(float) * 2)) ||
 	    (r = dalloc(d, (void **)&d->amax_all, sizeof(float) * 2 * tp_size)) ||
 	    (r = dalloc(d, (void **)&d->inv_freq, sizeof(float) * c.head_dim / 2)) ||
-	    (r = dalloc(d, (void **)&d->tokens, sizeof(int) * d->tokens_cap)))
+	    (r = dalloc(d, (void **)&d->tokens, sizeof(int) * d->tokens_cap)) ||
+	    (r = dalloc(d, (void **)&d->smp_params, sizeof(SampleParams))) ||
+	    (r = dalloc(d, (void **)&d->smp_u, sizeof(float) * d->tokens_cap)) ||
+	    (r = dalloc(d, (void **)&d->smp_step, sizeof(StepState))))
 		return fail(r);
 	// RoPE frequencies on the host, bit for bit as the reference's compiled rope computes
 	// them. infer.cpp:203 reads 1/powf(theta, j/rotary_dim), but under its -ffast-math
@@ -1134,6 +1143,12 @@ static int create_decoder(const yalm_config *config, const yalm_model_weights *w
 		inv[j / 2] = j >= c.rotary_dim ? 0.f : powf(c.rope_theta, -((float)j * rinv));
 	if (hipMemcpy(d->inv_freq, inv.data(), sizeof(float) * inv.size(), hipMemcpyHostToDevice) != hipSuccess) {
 		set_err("inv_freq upload failed");
+		return fail(YALM_ERR_HIP);
+	}
+	// the sampling parameters before any yalm_generate_sampled (yalm_time_kernel id 10): T = 1, no truncation
+	const SampleParams smp0{1.0f, 0, 1.0f};
+	if (hipMemcpy(d->smp_params, &smp0, sizeof(smp0), hipMemcpyHostToDevice) != hipSuccess) {
+		set_err("sampling parameter upload failed");
 		return fail(YALM_ERR_HIP);
 	}
 	for (auto &bw : d->b) {
@@ -1401,13 +1416,13 @@ extern "C" int yalm_forward(yalm_decoder d, int token, int pos, int mode, float 
 
 // n greedy forwards from position pos0 (-1: unknown); the eager path passes each forward's
 // kv_len to the attention + Wo launch (awo_kv_hint), graph replays cannot
-static int replay_greedy(yalm_decoder_s *d, int n, long long pos0) {
+static int replay_greedy(yalm_decoder_s *d, int n, long long pos0, int which = GRAPH_GREEDY) {
 	if (!d->greedy_eager)
-		TRY(ensure_graph(d, GRAPH_GREEDY));
+		TRY(ensure_graph(d, which));
 	int r = YALM_OK;
 	for (int i = 0; i < n && r == YALM_OK; ++i) {
 		d->awo_kv_hint = pos0 >= 0 ? std::min<long long>(pos0 + i + 1, d->c.max_seq_len) : -1;
-		r = replay(d, GRAPH_GREEDY);
+		r = replay(d, which);
 	}
 	d->awo_kv_hint = -1;
 	return r;
@@ -1443,6 +1458,41 @@ extern "C" int yalm_generate_greedy(yalm_decoder d, int token, int pos, int n_st
 		done += batch;
 	}
 	return YALM_OK;
+}
+
+static int validate_sampling(const yalm_sampling *s, const float *uniforms, int n_u) {
+	ARGCHK(s && uniforms, "sampling: null argument");
+	ARGCHK(s->temperature > 0.0f && std::isfinite(s->temperature), "sampling: temperature must be finite and > 0");
+	ARGCHK(s->top_k >= 0, "sampling: top_k must be >= 0 (0 = off)");
+	ARGCHK(s->top_p > 0.0f && s->top_p <= 1.0f, "sampling: top_p must be in (0, 1] (1 = off)");
+	for (int i = 0; i < n_u; ++i)
+		ARGCHK(uniforms[i] >= 0.0f && uniforms[i] <= 1.0f, "sampling: every uniform must be in [0, 1]");
+	return YALM_OK;
+}
+
+extern "C" int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
+                                     const float *uniforms, int *out_tokens) {
+	ARGCHK(d && out_tokens, "null argument");
+	ARGCHK(token >= 0 && token < d->vocab_full && pos >= 0 && n_steps >= 0, "bad token/pos/n_steps");
+	ARGCHK(n_steps <= d->tokens_cap, "yalm_generate_sampled: n_steps exceeds the token buffer (65536)");
+	TRY(validate_sampling(s, uniforms, n_steps));
+	if (d->tp_size > 1 || d->comm || d->ipc) {
+		set_err("yalm_generate_sampled: tensor-parallel decoders shard the vocabulary; device sampling runs on one GPU");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	ARGCHK(d->c.vocab_size <= SMP_MAX_N, "yalm_generate_sampled: vocabulary above 131072");
+	if (n_steps == 0)
+		return YALM_OK;
+	static_assert(sizeof(yalm_sampling) == sizeof(SampleParams), "yalm_sampling layout");
+	HIPCHK(hipMemcpyAsync(d->smp_params, s, sizeof(SampleParams), hipMemcpyHostToDevice, d->stream));
+	HIPCHK(hipMemcpyAsync(d->smp_u, uniforms, sizeof(float) * n_steps, hipMemcpyHostToDevice, d->stream));
+	set_step_kernel<<<1, 1, 0, d->stream>>>(d->step, token, pos, 1);
+	HIPCHK(hipGetLastError());
+	TRY(replay_greedy(d, n_steps, pos, GRAPH_SAMPLED));
+	d->host_pos = (long long)pos + n_steps;
+	HIPCHK(hipMemcpyAsync(out_tokens, d->tokens, sizeof(int) * n_steps, hipMemcpyDeviceToHost, d->stream));
+	HIPCHK(hipStreamSynchronize(d->stream));
+	return awo_check(d);
 }
 
 extern "C" int yalm_device_step(yalm_decoder d, int *token, int *pos) {
@@ -1573,6 +1623,11 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 		if constexpr (WT::BYTES <= 2)
 			return launch_attn_wo<WT>(d, w, l, 0);
 		break;
+	case 10: // the sampling launch on the current logits; commits into a scratch step state
+		sample_kernel<<<1, SMP_THREADS, 0, d->stream>>>(d->logits, c.vocab_size, d->smp_params, d->smp_u, 1,
+		                                                d->smp_step, nullptr, 0, nullptr, nullptr);
+		HIPCHK(hipGetLastError());
+		return YALM_OK;
 	}
 	set_err("bad kernel_id");
 	return YALM_ERR_ARG;
@@ -1581,6 +1636,10 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 extern "C" int yalm_graph_kernels(yalm_decoder d, int mode, int *kernels, int *nodes) {
 	ARGCHK(d && kernels && mode >= 0 && mode < N_GRAPHS, "yalm_graph_kernels: bad argument");
 	ARGCHK(!d->eager, "yalm_graph_kernels: the decoder launches eagerly (YALM_LAUNCH_EAGER)");
+	if (mode == GRAPH_SAMPLED && (d->tp_size > 1 || d->comm || d->ipc)) {
+		set_err("yalm_graph_kernels: no sampled step on a tensor-parallel decoder");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	TRY(ensure_graph(d, mode));
 	size_t n = 0;
 	HIPCHK(hipGraphGetNodes(d->graph[mode], nullptr, &n));
@@ -1657,8 +1716,10 @@ static int time_loop(yalm_decoder_s *d, int kernel_id, int iters, bool bump, boo
 }
 
 extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms) {
-	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 9 && kernel_id != 7,
-	       "bad argument (kernel ids 0-6, 8, 9)");
+	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 10 && kernel_id != 7,
+	       "bad argument (kernel ids 0-6, 8, 9, 10)");
+	ARGCHK(kernel_id != 10 || (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
+	       "kernel 10 (device sampling) needs a one-GPU decoder and a vocabulary of at most 131072");
 	ARGCHK(kernel_id != 9 || d->moe_E > 0, "kernel 9 (expert router) needs a mixture-of-experts decoder");
 	ARGCHK(kernel_id != 6 || d->comm || d->ipc, "kernel 6 (tensor-parallel exchange) needs a tensor-parallel decoder");
 	ARGCHK(kernel_id != 8 || d->attn_wo, "kernel 8 (fused attention + Wo) needs yalm_decoder_attn_wo");
@@ -1725,6 +1786,9 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 		break;
 	case 8:
 		s = std::string("attn_wo_kernel<") + wt + ", ";
+		break;
+	case 10:
+		s = "sample_kernel";
 		break;
 	default:
 		s = "";
@@ -1924,6 +1988,34 @@ extern "C" int yalm_argmax(const float *logits, int n, int n_shards, int *out) {
 	StepState h;
 	HIPCHK(hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost));
 	*out = h.token;
+	return YALM_OK;
+}
+
+extern "C" int yalm_sample(const float *logits, int n, const yalm_sampling *s, const float *uniforms, int n_draws,
+                           int *out_tokens, int *kept, uint64_t *weights_out) {
+	ARGCHK(logits && out_tokens && n > 0 && n_draws > 0 && n_draws <= (1 << 16), "yalm_sample: bad argument");
+	ARGCHK(n <= SMP_MAX_N, "yalm_sample: n above 131072");
+	TRY(validate_sampling(s, uniforms, n_draws));
+	DevBuf dl, dst, dprm, du, dtok, dkept, dw;
+	TRY(up(dl, logits, sizeof(float) * (size_t)n));
+	TRY(up(dst, nullptr, sizeof(StepState)));
+	TRY(up(dprm, s, sizeof(SampleParams)));
+	TRY(up(du, uniforms, sizeof(float) * n_draws));
+	TRY(up(dtok, nullptr, sizeof(int) * n_draws));
+	TRY(up(dkept, nullptr, sizeof(int) * n_draws));
+	if (weights_out)
+		TRY(up(dw, nullptr, sizeof(uint64_t) * (size_t)n));
+	for (int i = 0; i < n_draws; ++i) // draw i reads uniforms[n_gen = i]; the weights are the same every time
+		sample_kernel<<<1, SMP_THREADS>>>((const float *)dl.p, n, (const SampleParams *)dprm.p, (const float *)du.p,
+		                                  n_draws, (StepState *)dst.p, (int *)dtok.p, n_draws, (int *)dkept.p,
+		                                  i == 0 ? (unsigned long long *)dw.p : nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(out_tokens, dtok.p, sizeof(int) * n_draws, hipMemcpyDeviceToHost));
+	if (kept)
+		HIPCHK(hipMemcpy(kept, dkept.p, sizeof(int) * n_draws, hipMemcpyDeviceToHost));
+	if (weights_out)
+		HIPCHK(hipMemcpy(weights_out, dw.p, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
 	return YALM_OK;
 }
 

@@ -1,7 +1,8 @@
 // main.cpp — yalm-compatible CLI over the MI355X engine (flags and modes of
 // /root/reference/src/main.cpp:17-428): completion, perplexity and passkey,
 // -d device switch (cpu | cuda | hip prefixes), -m -n -t -i -f -T -l.
-// -t 0 runs the greedy loop with the argmax on the device.
+// -t 0 runs the greedy loop with the argmax on the device; -k / -p (top-k, top-p) select
+// device sampling for -t > 0: only the token comes back per step.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -38,6 +39,9 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -n <int>    number of steps to run for in completion mode, default 256. 0 = max_seq_len, "
 	                "-1 = infinite\n");
 	fprintf(stderr, "  -t <float> temperature (default - 1.0)\n");
+	fprintf(stderr, "  -k <int>   top-k: sample among the k most likely tokens (0 - off); samples on the device\n");
+	fprintf(stderr, "  -p <float> top-p: sample from the smallest set of most likely tokens whose probability\n"
+	                "             reaches p, in (0, 1] (1 - off); samples on the device\n");
 	fprintf(stderr, "  Choose one:\n    -i <string> input prompt\n    -f <filepath> input file with prompt\n");
 	fprintf(stderr, "Passkey mode options:\n  -n <int>    number of junk lines to insert (default - 250)\n");
 	fprintf(stderr, "  -l <int>    passkey position (-1 - random)\n");
@@ -80,7 +84,8 @@ static std::vector<int> encode_prompt(const Tokenizer &tok, const std::string &p
 }
 
 static void run_completion(const std::string &path, const std::string &device, const std::string &prompt,
-                           int context, int num_steps, float temperature) {
+                           int context, int num_steps, float temperature, bool device_sampling, int top_k,
+                           float top_p) {
 	YALMData data;
 	if (data.from_file(path) != 0) {
 		fprintf(stderr, "error: cannot load %s\n", path.c_str());
@@ -99,6 +104,10 @@ static void run_completion(const std::string &path, const std::string &device, c
 
 	std::vector<int> encoding = encode_prompt(tokenizer, prompt, true);
 	const bool greedy = temperature == 0.0f;
+	// -k / -p: the token is drawn on the device (Model::forward_sampled) from one
+	// std::rand() / (float)RAND_MAX per generated token, the stream Sampler's constructor seeded
+	const bool sampled = device_sampling && !greedy;
+	auto uniform = [] { return std::rand() / (float)RAND_MAX; };
 	const uint64_t start = now_ms();
 	size_t read_bytes = 0;
 	int next = 0;
@@ -114,10 +123,16 @@ static void run_completion(const std::string &path, const std::string &device, c
 		for (size_t pos = 0; pos < first; ++pos)
 			read_bytes += model.config->active_bytes(pos);
 	}
+	// YALM_SEED (tests): re-seeded before the first draw, as in run_passkey, because the HIP
+	// runtime's initialisation above draws from std::rand too
+	if (sampled && getenv("YALM_SEED"))
+		std::srand((unsigned)sampler_seed());
 	for (size_t pos = first; pos < encoding.size(); ++pos) {
 		const bool last = pos + 1 == encoding.size();
 		if (last && greedy)
 			next = model.forward_greedy(state, encoding[pos], (int)pos);
+		else if (last && sampled)
+			next = model.forward_sampled(state, encoding[pos], (int)pos, temperature, top_k, top_p, uniform());
 		else
 			model.forward(state, encoding[pos], (int)pos,
 			              last ? InferenceMode::OUTPUT_LOGITS : InferenceMode::HYDRATE_KV_CACHE);
@@ -126,7 +141,7 @@ static void run_completion(const std::string &path, const std::string &device, c
 	const uint64_t end_hydrate = now_ms();
 	std::string ids;
 	for (int i = 0; i < num_steps || num_steps == -1; ++i) {
-		const int token = greedy ? next : sampler.sample(state, temperature);
+		const int token = greedy || sampled ? next : sampler.sample(state, temperature);
 		std::cout << tokenizer.decode_one(encoding.back(), token) << std::flush;
 		ids += std::to_string(token) + " ";
 		encoding.push_back(token);
@@ -135,7 +150,11 @@ static void run_completion(const std::string &path, const std::string &device, c
 		const int pos = (int)encoding.size() - 1;
 		if (greedy)
 			next = model.forward_greedy(state, token, pos);
-		else
+		else if (sampled) {
+			if (i + 1 == num_steps)
+				break; // no further token: no further forward, and exactly one draw per generated token
+			next = model.forward_sampled(state, token, pos, temperature, top_k, top_p, uniform());
+		} else
 			model.forward(state, token, pos);
 		read_bytes += model.config->active_bytes(pos);
 	}
@@ -286,8 +305,9 @@ static void run_passkey(const std::string &path, const std::string &device, int 
 
 int main(int argc, char *argv[]) {
 	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path;
-	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1;
-	float temperature = 1.0f;
+	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0;
+	float temperature = 1.0f, top_p = 1.0f;
+	bool device_sampling = false;
 	if (argc < 2)
 		error_usage();
 	checkpoint = argv[1];
@@ -317,6 +337,14 @@ int main(int argc, char *argv[]) {
 			break;
 		case 'i': prompt = v; break;
 		case 't': temperature = std::stof(v); break;
+		case 'k':
+			top_k = std::stoi(v);
+			device_sampling = true;
+			break;
+		case 'p':
+			top_p = std::stof(v);
+			device_sampling = true;
+			break;
 		case 'f': prompt_path = v; break;
 		case 'T': context = std::stoi(v); break;
 		case 'l': passkey_pos = std::stoi(v); break;
@@ -348,7 +376,7 @@ int main(int argc, char *argv[]) {
 	fprintf(stderr, "[yalm] Using checkpoint: %s\n", checkpoint.c_str());
 	try {
 		if (mode == "completion")
-			run_completion(checkpoint, device, prompt, context, num_steps, temperature);
+			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p);
 		else if (mode == "passkey")
 			run_passkey(checkpoint, device, context, n_junk, passkey_pos);
 		else

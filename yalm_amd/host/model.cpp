@@ -304,4 +304,12 @@ int Model::forward_greedy(InferenceState &s, int token, int pos) {
 	return next;
 }
 
+int Model::forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u) {
+	ensure_decoder(s);
+	const yalm_sampling sp{temperature, top_k, top_p};
+	int next = 0;
+	check(yalm_generate_sampled(s._decoder, token, pos, 1, &sp, &u, &next), "sampled step");
+	return next;
+}
+
 } // namespace yalm

@@ -124,6 +124,10 @@ struct Model {
 	// Greedy (-t 0) step on the device: forward + first-max argmax without
 	// copying logits to the host. Returns the next token.
 	int forward_greedy(InferenceState &s, int token, int pos);
+	// Sampled step on the device (yalm_generate_sampled, one step): forward, then temperature /
+	// top-k (0 = off) / top-p (1 = off) sampling of the logits with the uniform u in [0, 1];
+	// only the token comes back. Returns the next token.
+	int forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u);
 	// Batched MFMA prefill of tokens[0..n) at positions pos0.. (yalm_prefill):
 	// fills the KV cache; logprobs (may be null) gets log p(tokens[i+1]) per
 	// position; split: the split-operand precision form (yalm_set_prefill_precision).

@@ -62,6 +62,12 @@ class Config(ctypes.Structure):
         )
 
 
+class Sampling(ctypes.Structure):
+    """yalm_sampling: temperature > 0, top_k >= 0 (0 = off), top_p in (0, 1] (1 = off)."""
+
+    _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float)]
+
+
 class BlockWeights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("rms_att", "rms_ffn", "wq", "wk", "wv", "wo", "w1", "w2", "w3",
                                         "key_cache", "value_cache")]
@@ -106,6 +112,8 @@ _sig("yalm_decoder_destroy", c_int, [c_void_p])
 _sig("yalm_forward", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
 _sig("yalm_generate_greedy", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
 _sig("yalm_enqueue_greedy", c_int, [c_void_p, c_int])
+_sig("yalm_generate_sampled", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Sampling), c_void_p, c_void_p])
+_sig("yalm_sample", c_int, [c_void_p, c_int, ctypes.POINTER(Sampling), c_void_p, c_int, c_void_p, c_void_p, c_void_p])
 _sig("yalm_device_step", c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
 _sig("yalm_device_tokens", c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)])
 _sig("yalm_block", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int])
@@ -152,6 +160,7 @@ EXPORTED = [
     "yalm_stream_create_cu_part", "yalm_decoder_set_launch", "yalm_prefill_info", "yalm_set_prefill_precision",
     "yalm_decoder_create_moe", "yalm_moe_routing", "yalm_moe_ffn",
     "yalm_prefill_routing", "yalm_moe_gemm_f16", "yalm_moe_ffn_rows",
+    "yalm_generate_sampled", "yalm_sample",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -205,6 +214,20 @@ def argmax(logits: np.ndarray, n_shards: int = 1) -> int:
     out = c_int()
     check(lib.yalm_argmax(_ptr(lg), lg.size, n_shards, ctypes.byref(out)))
     return out.value
+
+
+def sample(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float = 1.0, uniforms=(0.5,)):
+    """Device sampling of host logits (yalm_sample: one launch of the decode loop's sampling
+    kernel per uniform). Returns (tokens, kept, q): the token and the kept-set size of every
+    draw (int32 arrays) and the uint64 fixed-point weights q_i the kernel used."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+    s = Sampling(temperature, top_k, top_p)
+    tokens = np.zeros(max(u.size, 1), np.int32)
+    kept = np.zeros(max(u.size, 1), np.int32)
+    q = np.zeros(max(lg.size, 1), np.uint64)
+    check(lib.yalm_sample(_ptr(lg), lg.size, ctypes.byref(s), _ptr(u), u.size, _ptr(tokens), _ptr(kept), _ptr(q)))
+    return tokens[:u.size], kept[:u.size], q[:lg.size]
 
 
 def ffn(x, w1, w2, w3, act: int, dtype: int) -> np.ndarray:
@@ -574,6 +597,22 @@ class Decoder:
         check(lib.yalm_generate_greedy(self.h, token, pos, n, out.ctypes.data))
         return out[:n].tolist()
 
+    def generate_sampled(self, token: int, pos: int, n: int, temperature: float, top_k: int = 0,
+                         top_p: float = 1.0, uniforms=None, seed: int = 0) -> list:
+        """n tokens sampled on the device (yalm_generate_sampled): temperature, then top-k, then
+        top-p, one uniform per step. uniforms None: numpy.random.default_rng(seed).random(n, float32)."""
+        if uniforms is None:
+            uniforms = np.random.default_rng(seed).random(n, dtype=np.float32)
+        u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.size < n:
+            raise ValueError(f"generate_sampled: {n} steps need {n} uniforms, got {u.size}")
+        if u.size == 0:
+            u = np.zeros(1, np.float32)
+        s = Sampling(temperature, top_k, top_p)
+        out = np.zeros(max(n, 1), np.int32)
+        check(lib.yalm_generate_sampled(self.h, token, pos, n, ctypes.byref(s), _ptr(u), out.ctypes.data))
+        return out[:n].tolist()
+
     def enqueue_greedy(self, n: int) -> None:
         check(lib.yalm_enqueue_greedy(self.h, n))
 
@@ -636,7 +675,7 @@ class Decoder:
         return buf[: 16 * nb.value].reshape(nb.value, 16), na.value
 
     def graph_kernels(self, mode: int = 2) -> int:
-        """Kernel launches per forward of graph `mode` (2 = the device greedy step)."""
+        """Kernel launches per forward of graph `mode` (2 = the device greedy step, 3 = the sampled one)."""
         k, n = c_int(), c_int()
         check(lib.yalm_graph_kernels(self.h, mode, ctypes.byref(k), ctypes.byref(n)))
         return k.value
