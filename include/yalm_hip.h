@@ -33,6 +33,25 @@ extern "C" {
 
 /* DType codes follow the reference enum order (codec.h:15-25). */
 enum { YALM_F32 = 0, YALM_F16 = 1, YALM_BF16 = 2, YALM_F8E5M2 = 3 };
+/* ---------------- q4: 4-bit group-quantised weights ----------------
+ * A storage format of this engine alone (code 16: outside the reference's DType range 0..8;
+ * the reference rejects such a file). Symmetric 4-bit, one f16 scale per group of 32
+ * consecutive elements of a weight row: an element is (u - 8) * s, u the nibble 0..15, s the
+ * group's scale, whose low 3 mantissa bits are zero -- so every value is an exact f16 and a
+ * q4 model has an exact f16 twin (the device the tests pin fp8 with). A matrix [rows][n],
+ * n % 32 == 0, is rows rows of yalm_row_bytes(YALM_Q4, n) = round_up(n / 2 + n / 16, 16)
+ * bytes: n / 32 16-byte nibble blocks (block b = elements 32 b .. 32 b + 31), then n / 32
+ * f16 scales, then zero padding. A block is 4 little-endian 32-bit words; word j holds
+ * elements 8 j .. 8 j + 7, element 8 j + i in the nibble at bits 4 * ((i >> 1) + 4 * (i & 1))
+ * (models.q4_pack / q4_unpack). Every weight matrix of a q4 model, the embedding included,
+ * has this layout; norms stay f32. Dense one-GPU decoders only: yalm_decoder_create,
+ * yalm_forward, the greedy / sampled loops, yalm_block, yalm_prefill (through a per-layer
+ * exact f16 upcast, as fp8), yalm_matmul, yalm_ffn, yalm_time_kernel, yalm_set_gemv_config.
+ * Attention and Wo run as separate launches (yalm_attn_wo_plan returns 0).
+ * YALM_ERR_UNSUPPORTED, with a yalm_last_error naming q4: yalm_decoder_create_moe,
+ * yalm_decoder_create_tp, yalm_decoder_create_tp_ipc, yalm_moe_ffn, yalm_moe_ffn_rows.
+ * YALM_ERR_ARG: a q4 config whose dim, hidden_dim or n_heads * head_dim is no multiple of 32. */
+enum { YALM_Q4 = 16 };
 /* ActivationType (model.h:14-17) */
 enum { YALM_GELU = 0, YALM_SILU = 1 };
 /* InferenceMode (model.h:28-31) */
@@ -54,7 +73,7 @@ typedef struct yalm_config {
 	float norm_eps;
 	int act;          /* YALM_GELU / YALM_SILU */
 	float qkv_clip;   /* FLT_MAX when absent (model.cpp:60-61) */
-	int weight_dtype; /* YALM_F32 / YALM_F16 / YALM_F8E5M2 */
+	int weight_dtype; /* YALM_F32 / YALM_F16 / YALM_F8E5M2 / YALM_Q4 */
 } yalm_config;
 
 /* Device pointers of one block (Block private fields, model.h:286-300). If
@@ -101,6 +120,15 @@ int yalm_stream_sync(yalm_stream s);
  * Used to build random-weight models of real shapes in HBM without a PCIe
  * upload (bench.py). Same integer hash as the CPU oracle. */
 int yalm_synth(void *device, size_t n, int dtype, uint64_t seed, float scale, float offset, yalm_stream s);
+/* Bytes of one row of n elements of a weight matrix in dtype (q4: the padded row above;
+ * 0 for an unknown dtype or a q4 n that is no multiple of 32). Pure host arithmetic. */
+size_t yalm_row_bytes(int dtype, int n);
+/* yalm_synth for a q4 tensor [rows][n], which needs the row length (yalm_synth with YALM_Q4 is
+ * YALM_ERR_ARG): nibble byte i of the tensor (row-major, nibble bytes only) is bits 40..47 of
+ * the initialiser's hash of i, every scale is the restricted f16 nearest scale / 7 (the f16
+ * nearest the f32 quotient, bits + 4 with the low 3 cleared), padding zero; the values are
+ * uniform over (u - 8) * s, about [-8 / 7 scale, scale]. models.synth_q4_array is its numpy twin. */
+int yalm_synth_q4(void *device, size_t rows, int n, uint64_t seed, float scale, yalm_stream s);
 
 /* ---------------- decoder: replaces Model::_forward_cuda / Block::_block_cuda ---------------- */
 /* Creates the device state for one sequence (InferenceState::cuda,
@@ -332,7 +360,8 @@ int yalm_copy_2d(void *dst, size_t dst_pitch, const void *src, size_t src_pitch,
  * expects them, so yalm_forward / yalm_generate_greedy can continue at
  * pos0 + n. logprobs (host, n floats, may be NULL): logprobs[i] =
  * log softmax(logits at position pos0 + i)[tokens[i + 1]] for i < n - 1 (the
- * quantity main.cpp:155 sums), logprobs[n - 1] = 0. Requires f16 weights,
+ * quantity main.cpp:155 sums), logprobs[n - 1] = 0. Requires f16 weights (fp8 and q4:
+ * through an exact f16 upcast of one layer at a time),
  * dims multiple of 128, head_dim 64 | 128 and pos0 + n <= max_seq_len
  * (the sliding window past max_seq_len stays on the decode path).
  * Synchronous. Activations are rounded to f16 for the MFMA inputs: results
@@ -382,7 +411,7 @@ int yalm_set_prefill_forms(yalm_decoder d, const char *spec);
 
 /* ---------------- test API: replaces infer.cu:890-1019 (model.h:370-384) ---------------- */
 /* Host pointers in and out; synchronous. dtype selects the weight type
- * (matmul_cuda<float|half|uint8_t>). */
+ * (matmul_cuda<float|half|uint8_t>; YALM_Q4: w is d rows of yalm_row_bytes(YALM_Q4, n)). */
 int yalm_matmul(float *xout, const float *x, const void *w, int n, int d, int dtype);
 /* mha_cuda: xout (n_heads, head_dim), att (n_heads, max_seq_len) softmax
  * probabilities for t < kv_len. */

@@ -1,7 +1,7 @@
 """GEMV launch-geometry sweep (default: the row-block kernel, gpw = workgroups per CU) on the Mistral-7B-shaped synthetic model.
 Times each weight-streaming kernel (HIP events, layers rotated so weights come
 from HBM) for every (threads, unroll, gpw) candidate; prints GB/s.
-usage: python tools/sweep_gemv.py [--dtype fp16|fp8] [--iters 64]"""
+usage: python tools/sweep_gemv.py [--dtype fp16|fp8|q4] [--iters 64]"""
 import argparse
 import os
 import sys
@@ -17,18 +17,18 @@ ap.add_argument("--kinds", default="0,1,2,3,4")
 ap.add_argument("--top", type=int, default=6)
 args = ap.parse_args()
 
-cfg = M.MISTRAL_7B.with_(weight_dtype=M.F16 if args.dtype == "fp16" else M.F8E5M2)
-wb = M.DTYPE_BYTES[cfg.weight_dtype]
+cfg = M.MISTRAL_7B.with_(weight_dtype=M.DTYPE_NAMES[args.dtype])
+rb_dim, rb_q, rb_h = (M.row_bytes(cfg.weight_dtype, n) for n in (cfg.dim, cfg.q_dim, cfg.hidden_dim))
 dm = runtime.DeviceModel.synthetic(cfg)
 dec = runtime.Decoder(dm)
 dec.forward(1, 0)
 # kind -> (time_kernel id, bytes per launch, n_groups)
 KINDS = {
-    0: ("qkv", 0, (cfg.q_dim + 2 * cfg.kv_dim) * cfg.dim * wb, (cfg.q_dim + 2 * cfg.kv_dim) // 2),
-    1: ("wo", 2, cfg.dim * cfg.q_dim * wb, cfg.dim),
-    2: ("glu", 3, 2 * cfg.hidden_dim * cfg.dim * wb, cfg.hidden_dim),
-    3: ("w2", 4, cfg.dim * cfg.hidden_dim * wb, cfg.dim),
-    4: ("cls", 5, cfg.vocab_size * cfg.dim * wb, cfg.vocab_size // 2),
+    0: ("qkv", 0, (cfg.q_dim + 2 * cfg.kv_dim) * rb_dim, (cfg.q_dim + 2 * cfg.kv_dim) // 2),
+    1: ("wo", 2, cfg.dim * rb_q, cfg.dim),
+    2: ("glu", 3, 2 * cfg.hidden_dim * rb_dim, cfg.hidden_dim),
+    3: ("w2", 4, cfg.dim * rb_h, cfg.dim),
+    4: ("cls", 5, cfg.vocab_size * rb_dim, cfg.vocab_size // 2),
 }
 for kind in [int(k) for k in args.kinds.split(",")]:
     name, kid, nbytes, groups = KINDS[kind]

@@ -7,7 +7,9 @@ with sentencepiece '▁' -> ' ' or GPT-2 byte decoding and NUL -> BEL
 (permute_reverse, convert.py:145-158), f32 norms, weights cast to fp32 /
 fp16 (round-to-nearest-even) / fp8 E5M2 (torch's fp8e5m2_from_fp32_value:
 RNE, >= 2^16 -> inf), tied classifier when ``tie_word_embeddings`` is not
-False (convert.py:200). Mixtral checkpoints (convert.py:54-56, 78-80, 188-193): the
+False (convert.py:200). q4 (this engine's own format, models.q4_quantize): every weight
+matrix, the embedding included, is quantised from its fp16 conversion and stored as a U8
+tensor [rows, row_bytes(n)]; dense models only. Mixtral checkpoints (convert.py:54-56, 78-80, 188-193): the
 router gate becomes ``moegate``, each layer's experts are stacked along a new
 leading axis, and n_experts / n_experts_active go into the metadata.
 
@@ -22,10 +24,11 @@ import os
 
 import numpy as np
 
+from . import models as M
 from .yalmfile import read_yalm, write_yalm
 
 SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM"]
-SUPPORTED_DTYPES = ["fp32", "fp16", "fp8"]
+SUPPORTED_DTYPES = ["fp32", "fp16", "fp8", "q4"]
 
 
 def metadata_from_config(config: dict, dtype: str) -> dict:
@@ -34,6 +37,8 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
         raise ValueError(f"Architecture {arch} is not supported, must be one of {SUPPORTED_ARCHITECTURES}")
     if dtype not in SUPPORTED_DTYPES:
         raise ValueError(f"Data type {dtype} is not supported, must be one of {SUPPORTED_DTYPES}")
+    if arch == "MixtralForCausalLM" and dtype == "q4":
+        raise ValueError("q4 has no mixture-of-experts form")
     head_dim = config.get("head_dim", config["hidden_size"] // config["num_attention_heads"])
     if config.get("attention_bias", False) or config.get("mlp_bias", False):
         raise ValueError("attention/mlp bias is not supported")
@@ -168,6 +173,8 @@ def convert(hf_dir: str, out_path: str, dtype: str = "fp16") -> None:
             return a, "F32"
         if dtype == "fp16":
             return a.astype(np.float16), "F16"
+        if dtype == "q4":  # from the fp16 conversion: |fp16 value - q4 value| <= scale / 2
+            return M.q4_quantize(a.astype(np.float16).reshape(-1, a.shape[-1])), "U8"
         return f32_to_e5m2(a), "F8_E5M2"
 
     tensors, dtypes = {}, {}

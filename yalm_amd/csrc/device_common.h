@@ -129,10 +129,18 @@ __device__ __forceinline__ uint16_t f2h(float x) { // round to nearest even
 	return h;
 }
 
-// Weight element types. EPL = elements per 16-byte lane load.
+// Weight element types. EPL = elements per 16-byte lane load. Every type streams rows in
+// 64-lane chunks of 16-byte pieces (WT_CHUNK_BYTES, lane l at 16 l); row_off(r, n) is the
+// byte offset of row r of a [rows][n] matrix. Scale / load_scale: the side value a piece
+// needs beside its 16 bytes (nothing but for q4: its group's f16 scale).
+#define WT_CHUNK_BYTES ((size_t)YALM_WAVE * 16)
+struct NoScale {};
 struct WF32 {
 	static constexpr int EPL = 4;
 	static constexpr int BYTES = 4;
+	static constexpr bool Q4 = false;
+	using Scale = NoScale;
+	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * n * BYTES; }
 	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
@@ -146,6 +154,9 @@ struct WF32 {
 struct WF16 {
 	static constexpr int EPL = 8;
 	static constexpr int BYTES = 2;
+	static constexpr bool Q4 = false;
+	using Scale = NoScale;
+	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * n * BYTES; }
 	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
@@ -164,6 +175,9 @@ typedef float float2_t __attribute__((ext_vector_type(2)));
 struct WF8 {
 	static constexpr int EPL = 16;
 	static constexpr int BYTES = 1;
+	static constexpr bool Q4 = false;
+	using Scale = NoScale;
+	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * n * BYTES; }
 	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
 #pragma unroll
 		for (int i = 0; i < 4; ++i) {
@@ -177,6 +191,103 @@ struct WF8 {
 		}
 	}
 };
+
+// q4: symmetric 4-bit, one f16 scale per group of 32 consecutive elements of a row; the value
+// of an element is (u - 8) * s (u the nibble 0..15, s the group's scale, whose low 3 mantissa
+// bits are zero: every value is an exact f16). A row of n elements (n % 32 == 0) is n / 32
+// 16-byte nibble blocks, then n / 32 f16 scales, then zero padding to a multiple of 16 bytes
+// (q4_row_bytes). A block is 4 little-endian 32-bit words; word j holds elements 8 j .. 8 j + 7,
+// element 8 j + i in the nibble at bits 4 * ((i >> 1) + 4 * (i & 1)): the two nibbles that one
+// mask of a word extracts into the halves of a register are adjacent elements (2 k, 2 k + 1).
+// No BYTES: code that multiplies by an element size does not compile for it.
+__host__ __device__ static __forceinline__ size_t q4_row_bytes(int n) {
+	return ((size_t)(n >> 1) + (size_t)(n >> 4) + 15) & ~(size_t)15;
+}
+// the four f16 pairs {u(2k) - 8, u(2k + 1) - 8}, k < 4, of one word. (w & 0x000F000F) |
+// 0x64006400 is the f16 pair {1024 + u, 1024 + u'}; the nibbles one position up give
+// 1024 + 16 u, and (1024 + 16 u) / 16 - 72 = u - 8: every step is exact in f16.
+__device__ __forceinline__ uint32_t q4_and_or(uint32_t w, uint32_t mask, uint32_t magic) {
+	uint32_t r; // (w & mask) | magic as one VALU op (hipcc emits v_and + v_or: gfx950's VOP3 takes no literals)
+	asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(w), "s"(mask), "v"(magic));
+	return r;
+}
+__device__ __forceinline__ void q4_pairs(uint32_t w, half2_t (&h)[4]) {
+	const half2_t c1032 = {(_Float16)1032.0f, (_Float16)1032.0f}, c72 = {(_Float16)72.0f, (_Float16)72.0f};
+	const half2_t c16th = {(_Float16)0.0625f, (_Float16)0.0625f};
+	const uint32_t w8 = w >> 8;
+	h[0] = __builtin_bit_cast(half2_t, q4_and_or(w, 0x000F000Fu, 0x64006400u)) - c1032;
+	h[1] = __builtin_bit_cast(half2_t, q4_and_or(w, 0x00F000F0u, 0x64006400u)) * c16th - c72;
+	h[2] = __builtin_bit_cast(half2_t, q4_and_or(w8, 0x000F000Fu, 0x64006400u)) - c1032;
+	h[3] = __builtin_bit_cast(half2_t, q4_and_or(w8, 0x00F000F0u, 0x64006400u)) * c16th - c72;
+}
+struct WQ4 {
+	static constexpr int EPL = 32; // a lane's 16-byte load is one group
+	static constexpr bool Q4 = true;
+	// the group's f16 scale, as bits in a register of its own: 16-bit values in flight are
+	// packed two to a register by hipcc, and the merge waits for each scale load at once (vmcnt(0))
+	using Scale = uint32_t;
+	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * q4_row_bytes(n); }
+	// byte offset of group gi's scale inside a row of n elements
+	__host__ __device__ static __forceinline__ size_t scale_off(int n, int gi) { return (size_t)(n >> 1) + 2 * (size_t)gi; }
+	__device__ static __forceinline__ Scale load_scale(const void *p) {
+		return (uint32_t)__builtin_nontemporal_load((const uint16_t *)p);
+	}
+	// the 32 exact values of one block
+	__device__ static __forceinline__ void unpack(const u32x4_t &w, Scale s, float *o) {
+		const float sf = h2f((uint16_t)s);
+#pragma unroll
+		for (int j = 0; j < 4; ++j) {
+			const uint32_t v = w[j];
+			half2_t h[4];
+			q4_pairs(v, h);
+#pragma unroll
+			for (int k = 0; k < 4; ++k) {
+				o[8 * j + 2 * k] = (float)h[k][0] * sf;
+				o[8 * j + 2 * k + 1] = (float)h[k][1] * sf;
+			}
+		}
+	}
+};
+// acc += s * sum_e (u_e - 8) * x_e over one q4 block: the (u - 8) pairs go to v_fma_mix_f32
+// (the f16 operand widened exactly, f32 accumulation, as dot16_mix), two chains; the scale is
+// applied once per group.
+__device__ __forceinline__ float q4_dot32(float acc, const u32x4_t &w, uint32_t s, const float (&x)[32]) {
+	float a0 = 0.0f, a1 = 0.0f;
+#pragma unroll
+	for (int j = 0; j < 4; ++j) {
+		const uint32_t v = w[j];
+		half2_t h[4];
+		q4_pairs(v, h);
+#pragma unroll
+		for (int k = 0; k < 4; k += 2) {
+			const uint32_t p = __builtin_bit_cast(uint32_t, h[k]), q = __builtin_bit_cast(uint32_t, h[k + 1]);
+			asm("v_fma_mix_f32 %0, %2, %4, %0 op_sel_hi:[1,0,0]\n\t"
+			    "v_fma_mix_f32 %1, %2, %5, %1 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
+			    "v_fma_mix_f32 %0, %3, %6, %0 op_sel_hi:[1,0,0]\n\t"
+			    "v_fma_mix_f32 %1, %3, %7, %1 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
+			    : "+v"(a0), "+v"(a1)
+			    : "v"(p), "v"(q), "v"(x[8 * j + 2 * k]), "v"(x[8 * j + 2 * k + 1]), "v"(x[8 * j + 2 * k + 2]),
+			      "v"(x[8 * j + 2 * k + 3]));
+		}
+	}
+	return __builtin_fmaf(h2f((uint16_t)s), a0 + a1, acc);
+}
+
+// x[0, dim) = one embedding row widened exactly, by the workgroup's threads: piece k of the
+// row is its bytes [16 k, 16 k + 16) = elements [EPL k, EPL k + EPL) (q4: times the group's scale).
+template <class WT>
+__device__ __forceinline__ void embed_row(const char *row, int dim, float *__restrict__ x) {
+	for (int k = threadIdx.x; k * WT::EPL < dim; k += blockDim.x) {
+		float f[WT::EPL];
+		if constexpr (WT::Q4)
+			WT::unpack(load16(row + (size_t)k * 16), (uint32_t) * (const uint16_t *)(row + WT::scale_off(dim, k)), f);
+		else
+			WT::unpack(load16(row + (size_t)k * 16), f);
+#pragma unroll
+		for (int e = 0; e < WT::EPL; ++e)
+			x[k * WT::EPL + e] = f[e];
+	}
+}
 
 // acc += w . x over one 16-byte weight piece, two independent chains (a0: even
 // elements, a1: odd). f16: v_fma_mix_f32 widens the f16 operand exactly and

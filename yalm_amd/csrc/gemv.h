@@ -35,7 +35,7 @@ struct PStore {
 	int n_groups;
 	__device__ __forceinline__ void prologue() const {}
 	__device__ __forceinline__ const char *row(int g, int r) const {
-		return W + (size_t)(g * R + r) * n * WT::BYTES;
+		return W + WT::row_off((size_t)(g * R + r), n);
 	}
 	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
 		if (lane < R)
@@ -57,7 +57,7 @@ struct PResidual {
 	int n_groups;
 	__device__ __forceinline__ void prologue() const {}
 	__device__ __forceinline__ const char *row(int g, int r) const {
-		return W + (size_t)(g * R + r) * n * WT::BYTES;
+		return W + WT::row_off((size_t)(g * R + r), n);
 	}
 	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
 		if (lane < R)
@@ -136,7 +136,7 @@ struct PAddTo {
 	int n_groups;
 	__device__ __forceinline__ void prologue() const {}
 	__device__ __forceinline__ const char *row(int g, int r) const {
-		return W + (size_t)(g * R + r) * n * WT::BYTES;
+		return W + WT::row_off((size_t)(g * R + r), n);
 	}
 	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
 		if (lane < R)
@@ -164,7 +164,7 @@ struct PPush {
 	mutable unsigned xg = 0; // this launch's exchange index (read in prologue, ahead of the stream's end)
 	__device__ __forceinline__ void prologue() const { xg = t.g(); }
 	__device__ __forceinline__ const char *row(int g, int r) const {
-		return W + (size_t)(g * R + r) * n * WT::BYTES;
+		return W + WT::row_off((size_t)(g * R + r), n);
 	}
 	static constexpr bool PRE = true;
 	__device__ __forceinline__ float pre(int g, int r) const { return base ? base[g * R + r] : 0.0f; }
@@ -237,12 +237,12 @@ struct PQKV {
 	__device__ __forceinline__ const char *row(int g, int r) const {
 		int vr = 2 * g + r;
 		if (vr < q_dim)
-			return wq + (size_t)vr * n * WT::BYTES;
+			return wq + WT::row_off((size_t)vr, n);
 		vr -= q_dim;
 		if (vr < kv_dim)
-			return wk + (size_t)vr * n * WT::BYTES;
+			return wk + WT::row_off((size_t)vr, n);
 		vr -= kv_dim;
-		return wv + (size_t)vr * n * WT::BYTES;
+		return wv + WT::row_off((size_t)vr, n);
 	}
 	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
 		if (lane != 0)
@@ -284,7 +284,7 @@ struct PGlu {
 	int n_groups;
 	__device__ __forceinline__ void prologue() const {}
 	__device__ __forceinline__ const char *row(int g, int r) const {
-		return (r == 0 ? w1 : w3) + (size_t)g * n * WT::BYTES;
+		return (r == 0 ? w1 : w3) + WT::row_off((size_t)g, n);
 	}
 	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
 		if (lane == 0)
@@ -293,16 +293,36 @@ struct PGlu {
 	__device__ __forceinline__ void finish_all(int g, const float *acc) const { finish(g, acc, 0); }
 };
 
+// The LDS layout of x. Plain (XQ4 = false): element i at xs[i]. q4: a lane reads the 32
+// consecutive elements of its group as 8 float4, 128 bytes from its neighbour's -- every
+// ds_read_b128 of a wave would hit 2 of the 8 bank groups. So inside each 2048-element chunk
+// float4 j of lane l's group lies at (j * 64 + l) * 4: one read of a wave is 1 KB contiguous.
+// xs_at: the place of the float4 at element i (i % 4 == 0); xs_len: floats x occupies.
+template <bool XQ4>
+__device__ __forceinline__ int xs_at(int i) {
+	if constexpr (XQ4)
+		return (i & ~2047) + ((i >> 2) & 7) * 256 + ((i >> 5) & 63) * 4;
+	else
+		return i;
+}
+template <bool XQ4>
+__host__ __device__ __forceinline__ int xs_len(int n) {
+	if constexpr (XQ4)
+		return (n + 2047) & ~2047;
+	else
+		return (n + 3) & ~3;
+}
+
 // Stage x (n floats) into LDS, optionally as rmsnorm(x) * w (infer.cpp:134-144
 // statement order: scale = 1/sqrt(sum/n + eps); o = x * scale * w).
-template <bool NORM>
+template <bool NORM, bool XQ4 = false>
 __device__ __forceinline__ void stage_x(float *xs, const float *__restrict__ x, const float *__restrict__ normw, int n,
                                         float eps) {
 	const int tid = threadIdx.x;
 	const int nthreads = blockDim.x;
 	float scale = 1.0f;
 	if constexpr (NORM) {
-		float *red = xs + ((n + 3) & ~3); // scratch after x (one aligned LDS region, G17)
+		float *red = xs + xs_len<XQ4>(n); // scratch after x (one aligned LDS region, G17)
 		float ss = 0.0f;
 		for (int i = tid * 4; i < n; i += nthreads * 4) {
 			float4_t v = *(const float4_t *)(x + i);
@@ -327,7 +347,7 @@ __device__ __forceinline__ void stage_x(float *xs, const float *__restrict__ x, 
 			v[2] = v[2] * scale * w[2];
 			v[3] = v[3] * scale * w[3];
 		}
-		*(float4_t *)(xs + i) = v;
+		*(float4_t *)(xs + xs_at<XQ4>(i)) = v;
 	}
 	__syncthreads();
 }
@@ -361,13 +381,13 @@ __device__ __forceinline__ void prefetch_x(XPre<NORM, THREADS> &r, const float *
 	}
 }
 // infer.cpp:134-144 statement order, as stage_x
-template <bool NORM, int THREADS>
+template <bool NORM, int THREADS, bool XQ4 = false>
 __device__ __forceinline__ void stage_x_regs(float *xs, const XPre<NORM, THREADS> &r, int n, float eps) {
 	const int tid = threadIdx.x;
 	const int nthreads = blockDim.x;
 	float scale = 1.0f;
 	if constexpr (NORM) {
-		float *red = xs + ((n + 3) & ~3);
+		float *red = xs + xs_len<XQ4>(n);
 		float ss = 0.0f;
 #pragma unroll
 		for (int k = 0; k < xpre_n<NORM, THREADS>(); ++k) {
@@ -398,7 +418,7 @@ __device__ __forceinline__ void stage_x_regs(float *xs, const XPre<NORM, THREADS
 				v[2] = v[2] * scale * w[2];
 				v[3] = v[3] * scale * w[3];
 			}
-			*(float4_t *)(xs + i) = v;
+			*(float4_t *)(xs + xs_at<XQ4>(i)) = v;
 		}
 	}
 	__syncthreads();
@@ -426,6 +446,24 @@ __device__ __forceinline__ void fma_chunk(float (&acc)[R], const u32x4_t (&w)[R]
 	}
 }
 
+// q4: each row's 16-byte block with its group's scale (device_common.h q4_dot32); xs_lane:
+// the chunk's x + lane * 4 in the q4 layout of x (xs_at<true>)
+template <int R>
+__device__ __forceinline__ void fma_chunk_q4(float (&acc)[R], const u32x4_t (&w)[R], const uint32_t (&s)[R],
+                                             const float *xs_lane) {
+	float xv[32];
+#pragma unroll
+	for (int e = 0; e < 32; e += 4) {
+		float4_t t = *(const float4_t *)(xs_lane + e * 64);
+		xv[e] = t[0];
+		xv[e + 1] = t[1];
+		xv[e + 2] = t[2];
+		xv[e + 3] = t[3];
+	}
+#pragma unroll
+	for (int r = 0; r < R; ++r)
+		acc[r] = q4_dot32(acc[r], w[r], s[r], xv);
+}
 // n must be a multiple of WT::EPL (the reference asserts n % 16 == 0,
 // infer.cpp:66) and of 4. Each wave processes `gpw` consecutive row groups.
 template <class WT, class P, int U, bool NORM>
@@ -440,7 +478,7 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(P p, const float *__
 	if constexpr (gemv_prepared<P>::value)
 		prep = p.prepare();
 	p.prologue();
-	stage_x<NORM>(xs, x, normw, n, eps);
+	stage_x<NORM, WT::Q4>(xs, x, normw, n, eps);
 
 	const int lane = threadIdx.x & 63;
 	const int wave = threadIdx.x >> 6;
@@ -454,43 +492,71 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(P p, const float *__
 		if (g >= p.n_groups)
 			break;
 		const char *rp[R];
+		[[maybe_unused]] const char *sp[R]; // q4: the scale of this lane's group of chunk 0
 #pragma unroll
 		for (int r = 0; r < R; ++r) {
 			if constexpr (gemv_prepared<P>::value)
-				rp[r] = p.row(g, r, prep) + (size_t)lane * EPL * WT::BYTES;
+				rp[r] = p.row(g, r, prep) + (size_t)lane * 16;
 			else
-				rp[r] = p.row(g, r) + (size_t)lane * EPL * WT::BYTES;
+				rp[r] = p.row(g, r) + (size_t)lane * 16;
+			if constexpr (WT::Q4)
+				sp[r] = rp[r] - (size_t)lane * 16 + WT::scale_off(n, lane);
 		}
 		float acc[R];
 #pragma unroll
 		for (int r = 0; r < R; ++r)
 			acc[r] = 0.0f;
+		// chunk c of row r: its 16-byte piece and (q4) its scale, issued together
+		auto lscale = [&](int r, int c) {
+			if constexpr (WT::Q4)
+				return WT::load_scale(sp[r] + (size_t)c * (2 * YALM_WAVE));
+			else
+				return NoScale{};
+		};
 
 		int c = 0;
 		for (; c + U <= nfull; c += U) {
 			u32x4_t w[U][R];
+			typename WT::Scale s[U][R];
 #pragma unroll
 			for (int u = 0; u < U; ++u)
 #pragma unroll
-				for (int r = 0; r < R; ++r)
-					w[u][r] = load_nt16(rp[r] + (size_t)(c + u) * CH * WT::BYTES);
+				for (int r = 0; r < R; ++r) {
+					w[u][r] = load_nt16(rp[r] + (size_t)(c + u) * WT_CHUNK_BYTES);
+					s[u][r] = lscale(r, c + u);
+				}
 #pragma unroll
 			for (int u = 0; u < U; ++u)
-				fma_chunk<WT, R>(acc, w[u], xs + (c + u) * CH + lane * EPL);
+				if constexpr (WT::Q4)
+					fma_chunk_q4<R>(acc, w[u], s[u], xs + (c + u) * CH + lane * 4);
+				else
+					fma_chunk<WT, R>(acc, w[u], xs + (c + u) * CH + lane * EPL);
 		}
 		for (; c < nfull; ++c) {
 			u32x4_t w[R];
+			typename WT::Scale s[R];
 #pragma unroll
-			for (int r = 0; r < R; ++r)
-				w[r] = load_nt16(rp[r] + (size_t)c * CH * WT::BYTES);
-			fma_chunk<WT, R>(acc, w, xs + c * CH + lane * EPL);
+			for (int r = 0; r < R; ++r) {
+				w[r] = load_nt16(rp[r] + (size_t)c * WT_CHUNK_BYTES);
+				s[r] = lscale(r, c);
+			}
+			if constexpr (WT::Q4)
+				fma_chunk_q4<R>(acc, w, s, xs + c * CH + lane * 4);
+			else
+				fma_chunk<WT, R>(acc, w, xs + c * CH + lane * EPL);
 		}
 		if (rem > 0 && lane * EPL < rem) {
 			u32x4_t w[R];
+			typename WT::Scale s[R];
 #pragma unroll
-			for (int r = 0; r < R; ++r)
-				w[r] = load_nt16(rp[r] + (size_t)nfull * CH * WT::BYTES);
-			fma_chunk<WT, R>(acc, w, xs + nfull * CH + lane * EPL);
+			for (int r = 0; r < R; ++r) {
+				w[r] = load_nt16(rp[r] + (size_t)nfull * WT_CHUNK_BYTES);
+				s[r] = lscale(r, nfull);
+			}
+			if constexpr (WT::Q4)
+				fma_chunk_q4<R>(acc, w, s, xs + nfull * CH + lane * 4);
+			else
+				fma_chunk<WT, R>(acc, w, xs + nfull * CH + lane * EPL);
 		}
 #pragma unroll
 		for (int r = 0; r < R; ++r)
@@ -534,7 +600,7 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 	constexpr int R = P::R;
 	constexpr int EPL = WT::EPL;
 	constexpr int CH = YALM_WAVE * EPL;
-	constexpr size_t CHB = (size_t)CH * WT::BYTES;
+	constexpr size_t CHB = WT_CHUNK_BYTES;
 	constexpr int W = THREADS / YALM_WAVE;
 	const int n = p.n;
 	typename prep_of<P>::type prep{};
@@ -549,8 +615,8 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 	const int items = ngl * R * nch;
 	const int mine = ROWS ? (ngl * R > wave ? ((ngl * R - 1 - wave) / W + 1) * nch : 0) // rows wave, wave + W, ...
 	                      : (items > wave ? (items - 1 - wave) / W + 1 : 0);            // items wave, wave + W, ...
-	float *part = xs + ((n + 3) & ~3) + 64;                         // [ngl * R][W]
-	const size_t lane_off = (size_t)lane * EPL * WT::BYTES;
+	float *part = xs + xs_len<WT::Q4>(n) + 64;                      // [ngl * R][W]
+	const size_t lane_off = (size_t)lane * 16;
 	const char *dummy = (const char *)x + lane * 16;
 #ifdef YALM_WG_TRACE
 	const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -579,6 +645,16 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 		else
 			return p.row(b + gl * NB, r) + (size_t)c * CHB + lane_off;
 	};
+	// q4: the scale of this lane's group of item (vr, c), loaded beside the item's 16 bytes --
+	// unconditionally too (past the end: two bytes of x), so the vmcnt order stays static
+	[[maybe_unused]] auto iscale = [&](bool live, int vr, int c) {
+		if constexpr (WT::Q4) {
+			const int gl = vr / R, r = vr - gl * R;
+			return WT::load_scale(live ? p.row(b + gl * NB, r) + WT::scale_off(n, c * YALM_WAVE + lane) : dummy);
+		} else {
+			return NoScale{};
+		}
+	};
 	auto pslot = [&](int vr) { return vr * W + wave; }; // LDS partial slot of item row vr
 
 	int ivr = ROWS ? wave : wave / nch, ic = ROWS ? 0 : wave - (wave / nch) * nch; // issue cursor
@@ -606,9 +682,12 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 	if constexpr (gemv_early<P>::value)
 		ek = p.early();
 	u32x4_t buf[U];
+	[[maybe_unused]] typename WT::Scale sbuf[U];
 #pragma unroll
 	for (int u = 0; u < U; ++u) {
 		buf[u] = load_nt16(u < mine ? iaddr(ivr, ic) : dummy);
+		if constexpr (WT::Q4)
+			sbuf[u] = iscale(u < mine, ivr, ic);
 		advance(ivr, ic);
 	}
 	if constexpr (!gemv_early<P>::value)
@@ -618,9 +697,9 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 	if constexpr (TIN)
 		tpx_stage_x<NORM, THREADS, TPRE>(xs, tin, tview, tpre, normw, n, eps);
 	else if (xregs)
-		stage_x_regs<NORM, THREADS>(xs, xp, n, eps);
+		stage_x_regs<NORM, THREADS, WT::Q4>(xs, xp, n, eps);
 	else
-		stage_x<NORM>(xs, x, normw, n, eps);
+		stage_x<NORM, WT::Q4>(xs, x, normw, n, eps);
 
 	if (mine > 0) {
 		int cvr = vr0, cc = c0, cur = vr0; // consume cursor, row being accumulated
@@ -638,10 +717,17 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 						cur = cvr;
 					}
 					const u32x4_t wv[1] = {buf[u]};
-					fma_chunk<WT, 1>(acc, wv, xs + cc * CH + lane * EPL);
+					if constexpr (WT::Q4) { // (direct calls: a forwarding wrapper reordered the plain types' code)
+						const uint32_t sv[1] = {sbuf[u]};
+						fma_chunk_q4<1>(acc, wv, sv, xs + cc * CH + lane * 4);
+					} else {
+						fma_chunk<WT, 1>(acc, wv, xs + cc * CH + lane * EPL);
+					}
 					advance(cvr, cc);
 				}
 				buf[u] = load_nt16(j + U < mine ? iaddr(ivr, ic) : dummy);
+				if constexpr (WT::Q4)
+					sbuf[u] = iscale(j + U < mine, ivr, ic);
 				advance(ivr, ic);
 			}
 		}

@@ -65,14 +65,7 @@ __global__ __launch_bounds__(256) void step_begin_kernel(StepState *st, const vo
 	const int token = st->token;
 	const int pos = st->pos;
 	step_rope(st, pos, inv_freq, half);
-	const char *row = (const char *)emb + (size_t)token * dim * WT::BYTES;
-	for (int i = threadIdx.x * WT::EPL; i < dim; i += blockDim.x * WT::EPL) {
-		float f[WT::EPL];
-		WT::unpack(load16(row + (size_t)i * WT::BYTES), f);
-#pragma unroll
-		for (int e = 0; e < WT::EPL; ++e)
-			x[i + e] = f[e];
-	}
+	embed_row<WT>((const char *)emb + WT::row_off((size_t)token, dim), dim, x);
 	if (threadIdx.x == 0) {
 		const int kv_sink = pos >= max_seq_len ? 2 : 0;
 		st->kv_sink = kv_sink;
@@ -285,6 +278,32 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 	x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
 	x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
 	return x ^ (x >> 31);
+}
+
+// A q4 tensor [rows][n] (device_common.h WQ4) of the synthetic model: nibble byte i of the
+// tensor (counting nibble bytes only, row-major) is bits 40..47 of hash i, every scale is
+// `sbits`, the row padding is zero. One 16-byte piece per thread step.
+__global__ void synth_q4_kernel(u32x4_t *dst, size_t rows, int n, uint64_t seed, uint16_t sbits) {
+	const size_t rp = q4_row_bytes(n) / 16, nib = (size_t)n / 32; // pieces per row; of them nibble blocks
+	const size_t send = (size_t)(n >> 1) + (size_t)(n >> 4);      // end of the scales, in row bytes
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * rp; i += (size_t)gridDim.x * blockDim.x) {
+		const size_t r = i / rp, k = i - r * rp;
+		u32x4_t v = {0u, 0u, 0u, 0u};
+		if (k < nib) {
+			const uint64_t b0 = (r * nib + k) * 16;
+#pragma unroll
+			for (int j = 0; j < 16; ++j) {
+				const uint64_t h = splitmix64(seed ^ ((b0 + j) * 0xD1B54A32D192ED03ull));
+				v[j >> 2] |= (uint32_t)((h >> 40) & 0xFFu) << (8 * (j & 3));
+			}
+		} else {
+#pragma unroll
+			for (int j = 0; j < 8; ++j)
+				if (k * 16 + 2 * j < send)
+					v[j >> 1] |= (uint32_t)sbits << (16 * (j & 1));
+		}
+		dst[i] = v;
+	}
 }
 
 __global__ void synth_kernel(void *dst, size_t n, int dtype, uint64_t seed, float scale, float offset) {

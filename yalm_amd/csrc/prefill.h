@@ -325,14 +325,7 @@ template <class WT>
 __global__ __launch_bounds__(256) void embed_rows_kernel(const int *__restrict__ tokens, const void *__restrict__ emb,
                                                          int dim, float *__restrict__ X) {
 	const int t = blockIdx.x;
-	const char *row = (const char *)emb + (size_t)tokens[t] * dim * WT::BYTES;
-	for (int i = threadIdx.x * WT::EPL; i < dim; i += blockDim.x * WT::EPL) {
-		float f[WT::EPL];
-		WT::unpack(load16(row + (size_t)i * WT::BYTES), f);
-#pragma unroll
-		for (int e = 0; e < WT::EPL; ++e)
-			X[(size_t)t * dim + i + e] = f[e];
-	}
+	embed_row<WT>((const char *)emb + WT::row_off((size_t)tokens[t], dim), dim, X + (size_t)t * dim);
 }
 
 // E5M2 weights -> f16 for the prefill of an fp8 model: the byte b is the f16 with bits
@@ -370,6 +363,54 @@ __global__ __launch_bounds__(256) void e5m2_to_f16_kernel(DqSegs s) {
 		u32x4_t *d = (u32x4_t *)(dp + 16 * j);
 		d[0] = o[0];
 		d[1] = o[1];
+	}
+}
+
+// q4 weights (device_common.h WQ4) -> f16 for the prefill of a q4 model: every value
+// (u - 8) * s is an exact f16 (the scales carry 8 significant bits), so the f16 GEMMs over the
+// copy compute exactly what they compute for the f16 twin model. Up to 8 tensors per launch;
+// one 16-byte block (32 elements) and its scale in, 64 bytes out per thread step.
+struct DqSegsQ4 {
+	const uint8_t *src[8];
+	uint16_t *dst[8];
+	size_t end[8]; // cumulative blocks
+	int nb[8];     // blocks per row (n / 32)
+	int n;
+};
+__global__ __launch_bounds__(256) void q4_to_f16_kernel(DqSegsQ4 s) {
+	const size_t total = s.end[s.n - 1];
+	for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+		const uint8_t *sp = s.src[0];
+		uint16_t *dp = s.dst[0];
+		size_t base = 0;
+		int nb = s.nb[0];
+#pragma unroll
+		for (int m = 1; m < 8; ++m) // constant indices: the kernel-argument arrays stay in SGPRs
+			if (m < s.n && i >= s.end[m - 1]) {
+				sp = s.src[m];
+				dp = s.dst[m];
+				base = s.end[m - 1];
+				nb = s.nb[m];
+			}
+		const size_t j = i - base, r = j / (size_t)nb;
+		const int b = (int)(j - r * nb), n = nb * 32;
+		const uint8_t *row = sp + r * q4_row_bytes(n);
+		const u32x4_t v = load_nt16(row + 16 * (size_t)b);
+		const uint16_t sb = __builtin_nontemporal_load((const uint16_t *)(row + WQ4::scale_off(n, b)));
+		const _Float16 sh = __builtin_bit_cast(_Float16, sb);
+		const half2_t s2 = {sh, sh};
+		u32x4_t *d = (u32x4_t *)(dp + r * (size_t)n + 32 * (size_t)b);
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			const uint32_t w = v[q];
+			half2_t h[4];
+			q4_pairs(w, h);
+			u32x4_t o;
+#pragma unroll
+			for (int k = 0; k < 4; ++k)
+				o[k] = __builtin_bit_cast(uint32_t, h[k] * s2);
+			d[q] = o;
+		}
 	}
 }
 

@@ -319,9 +319,32 @@ int dequant_into(uint16_t *wdq, std::initializer_list<std::pair<const void *, si
 	return YALM_OK;
 }
 
-// Xn = f16(rmsnorm(X) * w) rows (SPLIT: [hi | lo]): one wave per row with the row in
-// registers (prefill.h rmsnorm_rows_wave_kernel) when dim <= 8192, else (or forms "wnorm:0")
-// the workgroup-per-row kernel
+// q4 models: the tensors ([rows][n] q4 rows each; t: {pointer, {rows, n}}) as their exact f16
+// values into wdq, end to end (prefill.h q4_to_f16_kernel)
+struct Q4Mat {
+	const void *p;
+	size_t rows;
+	int n;
+};
+int dequant_q4_into(uint16_t *wdq, std::initializer_list<Q4Mat> t, const uint16_t **out, hipStream_t st) {
+	pf::DqSegsQ4 s{};
+	size_t off = 0, blocks = 0;
+	for (auto &m : t) {
+		s.src[s.n] = (const uint8_t *)m.p;
+		s.dst[s.n] = wdq + off;
+		out[s.n] = s.dst[s.n];
+		s.nb[s.n] = m.n / 32;
+		blocks += m.rows * (size_t)(m.n / 32);
+		s.end[s.n] = blocks;
+		off += m.rows * (size_t)m.n;
+		++s.n;
+	}
+	const int grid = (int)std::min<size_t>((blocks + 255) / 256, (size_t)device_cu_count() * 8);
+	pf::q4_to_f16_kernel<<<grid, 256, 0, st>>>(s);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
 int dequant(yalm_decoder_s *d, std::initializer_list<std::pair<const void *, size_t>> t, const uint16_t **out,
 			hipStream_t st) {
 	return dequant_into(d->pf.wdq, t, out, st);
@@ -528,8 +551,8 @@ int alloc_moe_tabs(yalm_decoder_s *d, pf::MoeGroupTabs &t, size_t slots, int E) 
 
 int check_prefill_shape(const yalm_config &c) {
 	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
-	if (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2) {
-		set_err("yalm_prefill: f16 or fp8 (E5M2) weights only (MFMA f16 operands)");
+	if (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2 && c.weight_dtype != YALM_Q4) {
+		set_err("yalm_prefill: f16, fp8 (E5M2) or q4 weights only (MFMA f16 operands)");
 		return YALM_ERR_UNSUPPORTED;
 	}
 	if (c.dim % pf::BN || c.hidden_dim % pf::BN || q_dim % pf::BN || kv_dim % pf::BN || c.vocab_size % pf::BN ||
@@ -574,7 +597,7 @@ int ensure_bufs(yalm_decoder_s *d) {
 	TRY(pf_alloc(d, (void **)&b.lp, cap * 4));
 	TRY(pf_alloc(d, (void **)&b.rope, cap * c.head_dim * 4));
 	TRY(pf_alloc(d, (void **)&b.range, (size_t)(c.n_layers + 1) * RG_N * 4));
-	if (c.weight_dtype == YALM_F8E5M2) { // the f16 copy of one layer's weights, or of the classifier
+	if (c.weight_dtype == YALM_F8E5M2 || c.weight_dtype == YALM_Q4) { // the f16 copy of one layer's weights, or of the classifier
 		const size_t layer = ((size_t)q_dim + 2 * (size_t)c.n_kv_heads * c.head_dim) * c.dim + (size_t)c.dim * q_dim +
 							 3 * me * c.dim * c.hidden_dim + // (the stacked expert tensors
 								 (d->moe_E > 0 ? me * c.dim : 0); //  and the router's gate)
@@ -636,9 +659,11 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	PrefillBufs &b = d->pf;
 	hipStream_t st = d->stream;
 	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
-	const bool fp8 = c.weight_dtype == YALM_F8E5M2;
+	const bool fp8 = c.weight_dtype == YALM_F8E5M2, q4 = c.weight_dtype == YALM_Q4;
 	if (fp8)
 		pf::embed_rows_kernel<WF8><<<T, 256, 0, st>>>(b.tok, d->emb, c.dim, b.X);
+	else if (q4)
+		pf::embed_rows_kernel<WQ4><<<T, 256, 0, st>>>(b.tok, d->emb, c.dim, b.X);
 	else
 		pf::embed_rows_kernel<WF16><<<T, 256, 0, st>>>(b.tok, d->emb, c.dim, b.X);
 	HIPCHK(hipGetLastError());
@@ -685,6 +710,13 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 				TRY(dequant(d, {{w.wq, qd}, {w.wk, kd}, {w.wv, kd}, {w.wo, qd}, {w.w1, hd}, {w.w2, hd}, {w.w3, hd}}, p, st));
 			w.wq = p[0], w.wk = p[1], w.wv = p[2], w.wo = p[3], w.w1 = p[4], w.w2 = p[5], w.w3 = p[6];
 			gate16 = moe ? p[7] : nullptr;
+		}
+		if (q4) { // the same for a q4 layer (dense only)
+			const uint16_t *p[7];
+			const size_t qr = (size_t)q_dim, kr = (size_t)kv_dim, hr = (size_t)c.hidden_dim, dr = (size_t)c.dim;
+			TRY(dequant_q4_into(d->pf.wdq, {{w.wq, qr, c.dim}, {w.wk, kr, c.dim}, {w.wv, kr, c.dim}, {w.wo, dr, q_dim},
+			                                {w.w1, hr, c.dim}, {w.w2, dr, c.hidden_dim}, {w.w3, hr, c.dim}}, p, st));
+			w.wq = p[0], w.wk = p[1], w.wv = p[2], w.wo = p[3], w.w1 = p[4], w.w2 = p[5], w.w3 = p[6];
 		}
 		// normalised x as [hi | lo] (2 dim per row): hi is the q columns' A operand, hi + lo
 		// the k | v columns' (their cache rows then carry one f16 rounding, infer.cpp:299)
@@ -819,6 +851,11 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	if (fp8) {
 		const uint16_t *p[1];
 		TRY(dequant(d, {{d->wcls, (size_t)c.vocab_size * c.dim}}, p, st));
+		wcls = p[0];
+	}
+	if (q4) {
+		const uint16_t *p[1];
+		TRY(dequant_q4_into(d->pf.wdq, {{d->wcls, (size_t)c.vocab_size, c.dim}}, p, st));
 		wcls = p[0];
 	}
 	TRY(launch_plain(f, cls_bn, b.Xn, sp * c.dim, T, sp * c.dim, c.dim, one(wcls, c.vocab_size), c.vocab_size, e, st));
@@ -1035,6 +1072,10 @@ extern "C" int yalm_moe_ffn_rows(float *xout, int *experts, float *weights, cons
 	ARGCHK(act == YALM_SILU || act == YALM_GELU, "yalm_moe_ffn_rows: bad activation");
 	ARGCHK(n_experts >= 1 && n_experts <= MOE_MAX_EXPERTS && n_active >= 1 && n_active <= n_experts,
 	       "yalm_moe_ffn_rows: 1 <= n_experts_active <= n_experts <= 64");
+	if (dtype == YALM_Q4) {
+		set_err("yalm_moe_ffn_rows: q4 weights have no mixture-of-experts form");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	if (dtype != YALM_F16 && dtype != YALM_F8E5M2) {
 		set_err("yalm_moe_ffn_rows: f16 or fp8 (E5M2) weights only (MFMA f16 operands)");
 		return YALM_ERR_UNSUPPORTED;

@@ -141,9 +141,43 @@ extern "C" int yalm_stream_sync(yalm_stream s) {
 }
 
 extern "C" int yalm_synth(void *device, size_t n, int dtype, uint64_t seed, float scale, float offset, yalm_stream s) {
+	ARGCHK(dtype != YALM_Q4, "yalm_synth: q4 tensors need their row length (yalm_synth_q4)");
 	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_synth: bad dtype");
 	hipStream_t st = reinterpret_cast<hipStream_t>(s);
 	synth_kernel<<<4096, 256, 0, st>>>(device, n, dtype, seed, scale, offset);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+extern "C" size_t yalm_row_bytes(int dtype, int n) {
+	if (n <= 0)
+		return 0;
+	switch (dtype) {
+	case YALM_F32:
+		return (size_t)n * 4;
+	case YALM_F16:
+		return (size_t)n * 2;
+	case YALM_F8E5M2:
+		return (size_t)n;
+	case YALM_Q4:
+		return n % 32 ? 0 : q4_row_bytes(n);
+	}
+	return 0;
+}
+
+// The f16 with the low 3 mantissa bits zero nearest the f16 nearest v (bits + 4, low bits
+// cleared: a carry moves into the exponent as it should); models.q4_restrict_scale.
+static uint16_t q4_restricted_f16(float v) {
+	const _Float16 h = (_Float16)v;
+	uint16_t b;
+	memcpy(&b, &h, 2);
+	return (uint16_t)((b + 4u) & ~7u);
+}
+
+extern "C" int yalm_synth_q4(void *device, size_t rows, int n, uint64_t seed, float scale, yalm_stream s) {
+	ARGCHK(device && rows > 0 && n > 0 && n % 32 == 0, "yalm_synth_q4: rows > 0 and a row length that is a multiple of 32 (q4)");
+	hipStream_t st = reinterpret_cast<hipStream_t>(s);
+	synth_q4_kernel<<<4096, 256, 0, st>>>((u32x4_t *)device, rows, n, seed, q4_restricted_f16(scale / 7.0f));
 	HIPCHK(hipGetLastError());
 	return YALM_OK;
 }
@@ -210,7 +244,7 @@ template <class WT, class P, bool NORM, int THREADS, int U, bool ROWS>
 static int launch_rb_k(const P &p, const float *x, const float *normw, float eps, int nb, size_t lds, hipStream_t st,
                        const TpX &tin) {
 	auto kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS>;
-	if constexpr (NORM && !LocalX<P>::value) {
+	if constexpr (NORM && !LocalX<P>::value && !WT::Q4) { // (q4 has no tensor-parallel form)
 		if (tin.n > 0)
 			kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS, true>;
 	} else if (tin.n > 0) {
@@ -230,7 +264,7 @@ static int launch_rb_t(const P &p, const float *x, const float *normw, float eps
 	// an exchange consumer stages x from the exchange once per CU: one workgroup per CU
 	const int nb = std::max(1, std::min(p.n_groups, device_cu_count() * (tin.n > 0 ? 1 : std::max(1, wpc))));
 	const int ngl = (p.n_groups + nb - 1) / nb;
-	const size_t lds = ((size_t)((p.n + 3) & ~3) + 64 + (size_t)ngl * P::R * (THREADS / YALM_WAVE)) * sizeof(float);
+	const size_t lds = ((size_t)xs_len<WT::Q4>(p.n) + 64 + (size_t)ngl * P::R * (THREADS / YALM_WAVE)) * sizeof(float);
 	if constexpr (RowsMode<P>::value) {
 		// every workgroup the same number of rows and a whole number of rows, at least 2,
 		// per wave (profiles/r3_gemv_rows.txt: W1|W3 fp16 39.4-40.0 -> 36.9 us, fp8 W2 13.4 ->
@@ -246,9 +280,31 @@ static int launch_rb_t(const P &p, const float *x, const float *normw, float eps
 
 // Per-kind, per-weight-type defaults from tools/sweep_gemv.py on MI355X
 // (profiles/r1_sweep_rb*.txt): {threads, U, workgroups per CU}.
+// fp8 and q4: more ALU per byte than f16 / f32
+template <class WT>
+constexpr bool wt_narrow() {
+	if constexpr (WT::Q4)
+		return true;
+	else
+		return WT::BYTES == 1;
+}
 template <class WT>
 static GemvCfg default_rb_cfg(int kind) {
-	if constexpr (WT::BYTES == 1) { // fp8: more ALU per byte -> fewer loads in flight per lane
+	if constexpr (WT::Q4) { // tools/sweep_gemv.py --dtype q4 (profiles/q4_sweep.txt): the unpack is the work
+		switch (kind) {
+		case GK_QKV: // 7.96 us vs 8.67 for fp8's {512, 4, 1}
+			return GemvCfg{512, 2, 1};
+		case GK_WO: // 5.80 vs 6.76 for {512, 2, 2}
+			return GemvCfg{512, 4, 1};
+		case GK_GLU: // 17.33 vs 20.31 for {512, 4, 1}
+			return GemvCfg{512, 2, 2};
+		case GK_W2: // 11.33 vs 11.63 for {512, 4, 1}
+			return GemvCfg{512, 2, 1};
+		default: // logits: 20.63 vs 22.44 for {512, 2, 2}
+			return GemvCfg{512, 4, 3};
+		}
+	}
+	if constexpr (wt_narrow<WT>()) { // fp8: more ALU per byte -> fewer loads in flight per lane
 		switch (kind) {
 		case GK_W2:
 			return GemvCfg{512, 4, 1};
@@ -306,7 +362,7 @@ static int launch_rb(const P &p, const float *x, const float *normw, float eps, 
 template <class WT, class P, bool NORM>
 static int launch_gemv(const P &p, const float *x, const float *normw, float eps, int kind, GemvCfg want,
                        hipStream_t st, const TpX &tin = TpX{}) {
-	const size_t lds = (size_t)((p.n + 3) & ~3) * sizeof(float) + 64 * sizeof(float);
+	const size_t lds = (size_t)xs_len<WT::Q4>(p.n) * sizeof(float) + 64 * sizeof(float);
 	constexpr int CH = YALM_WAVE * WT::EPL;
 	if (p.n % CH != 0) { // ragged K: generic kernel (tests / unusual shapes)
 		if (tin.n > 0) {
@@ -644,6 +700,14 @@ static TpX tpx_ex(const yalm_decoder_s *d, int ex) {
 	return t;
 }
 
+// weight types with a fused attention + Wo kernel (attn_wo.h): f16 and fp8
+template <class WT>
+constexpr bool wt_fused_wo() {
+	if constexpr (WT::Q4)
+		return false;
+	else
+		return WT::BYTES == 2 || WT::BYTES == 1;
+}
 template <class WT, int GT, int KB>
 static void launch_attn_wo_k(yalm_decoder_s *d, const yalm_block_weights &w, const AttnWoArgs &p) {
 	attn_wo_kernel<WT, GT, KB><<<d->awo_nb, ATTN_THREADS, 0, d->stream>>>(d->q, w.key_cache, w.value_cache, d->step, p);
@@ -688,7 +752,7 @@ static int launch_attn_wo(yalm_decoder_s *d, const yalm_block_weights &w, int la
 	p.delay = d->awo_delay_short >= 0 && d->awo_kv_hint >= 0 && d->awo_kv_hint <= AWO_SHORT_KV ? d->awo_delay_short
 	                                                                                         : d->awo_delay;
 	const int G = c.n_heads / c.n_kv_heads;
-	if constexpr (WT::BYTES == 2 || WT::BYTES == 1) {
+	if constexpr (wt_fused_wo<WT>()) {
 		switch (p.q_dim * WT::BYTES) {
 		case 1024:
 			launch_attn_wo_g<WT, 1>(d, w, p, G);
@@ -744,45 +808,54 @@ template <class WT>
 static int enqueue_residual_gemv(yalm_decoder_s *d, const void *W, int n, const float *v, int kind, int ex) {
 	const yalm_config &c = d->c;
 	hipStream_t st = d->stream;
-	if (d->ipc && ex >= 0) {
-		PPush<WT, 1> p;
-		p.W = (const char *)W;
-		p.n = n;
-		p.base = d->tp_rank == 0 ? d->x : nullptr;
-		p.t = tpx_ex(d, ex);
-		p.offset = 0;
-		p.n_groups = c.dim;
-		return launch_gemv<WT, PPush<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st);
-	}
-	if (!d->comm) { // one GPU (or the unread IPC case above)
+	if constexpr (WT::Q4) { // one GPU only: yalm_decoder_create_tp / _tp_ipc refuse q4
 		PResidual<WT, 1> p;
 		p.W = (const char *)W;
 		p.n = n;
 		p.out = d->x;
 		p.n_groups = c.dim;
 		return launch_gemv_d<WT, PResidual<WT, 1>, false>(d, p, v, nullptr, 0.f, kind);
-	}
-	if (d->tp_rank == 0) {
-		PAddTo<WT, 1> p;
-		p.W = (const char *)W;
-		p.n = n;
-		p.out = d->xs;
-		p.base = d->x;
-		p.n_groups = c.dim;
-		TRY((launch_gemv<WT, PAddTo<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st)));
 	} else {
-		PStore<WT, 1> p;
-		p.W = (const char *)W;
-		p.n = n;
-		p.out = d->xs;
-		p.n_groups = c.dim;
-		TRY((launch_gemv<WT, PStore<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st)));
+		if (d->ipc && ex >= 0) {
+			PPush<WT, 1> p;
+			p.W = (const char *)W;
+			p.n = n;
+			p.base = d->tp_rank == 0 ? d->x : nullptr;
+			p.t = tpx_ex(d, ex);
+			p.offset = 0;
+			p.n_groups = c.dim;
+			return launch_gemv<WT, PPush<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st);
+		}
+		if (!d->comm) { // one GPU (or the unread IPC case above)
+			PResidual<WT, 1> p;
+			p.W = (const char *)W;
+			p.n = n;
+			p.out = d->x;
+			p.n_groups = c.dim;
+			return launch_gemv_d<WT, PResidual<WT, 1>, false>(d, p, v, nullptr, 0.f, kind);
+		}
+		if (d->tp_rank == 0) {
+			PAddTo<WT, 1> p;
+			p.W = (const char *)W;
+			p.n = n;
+			p.out = d->xs;
+			p.base = d->x;
+			p.n_groups = c.dim;
+			TRY((launch_gemv<WT, PAddTo<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st)));
+		} else {
+			PStore<WT, 1> p;
+			p.W = (const char *)W;
+			p.n = n;
+			p.out = d->xs;
+			p.n_groups = c.dim;
+			TRY((launch_gemv<WT, PStore<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st)));
+		}
+		if (ncclAllReduce(d->xs, d->x, c.dim, ncclFloat, ncclSum, (ncclComm_t)d->comm, st) != ncclSuccess) {
+			set_err("ncclAllReduce failed");
+			return YALM_ERR_HIP;
+		}
+		return YALM_OK;
 	}
-	if (ncclAllReduce(d->xs, d->x, c.dim, ncclFloat, ncclSum, (ncclComm_t)d->comm, st) != ncclSuccess) {
-		set_err("ncclAllReduce failed");
-		return YALM_ERR_HIP;
-	}
-	return YALM_OK;
 }
 
 // The exchange descriptor for a consumer launch (tp_exchange.h). Up to TPX_STAGE_MAX_RANKS
@@ -838,18 +911,20 @@ static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, 
 		TRY((launch_gemv_d<WT, PQKV<WT>, true>(d, p, d->x, w.rms_att, c.norm_eps, GK_QKV,
 		                                         d->ipc && x_exchanged ? tpx_consume(d, ex0 - 1, c.dim) : none)));
 	}
-	if (d->attn_wo && WT::BYTES <= 2) {
+	if (d->attn_wo && wt_fused_wo<WT>()) {
 		TRY(launch_attn_wo<WT>(d, w, l, ex0));
 	} else {
 		TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, d->q, w.key_cache, w.value_cache, d->step, c.max_seq_len,
 		                d->part, l, c.n_layers, d->awo_err, nullptr, d->xb2, st));
 		TRY(enqueue_residual_gemv<WT>(d, w.wo, q_dim, d->xb2, GK_WO, ex0));
 	}
-	if (d->moe_E > 0) { // router, then the selected experts' FFN (never tensor parallel)
-		const MoeArgs a = moe_layer_args(d, l);
-		TRY((launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, st)));
-		TRY((launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], st)));
-		return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], st);
+	if constexpr (!WT::Q4) { // (no q4 experts: yalm_decoder_create_moe refuses)
+		if (d->moe_E > 0) { // router, then the selected experts' FFN (never tensor parallel)
+			const MoeArgs a = moe_layer_args(d, l);
+			TRY((launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, st)));
+			TRY((launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], st)));
+			return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], st);
+		}
 	}
 	// the GLU consumes the Wo exchange under IPC tensor parallelism
 	if (c.act == YALM_SILU) {
@@ -879,16 +954,18 @@ template <class WT>
 static int enqueue_logits_t(yalm_decoder_s *d, int consume_ex, int push_ex) {
 	const yalm_config &c = d->c;
 	const TpX tin = consume_ex >= 0 ? tpx_consume(d, consume_ex, c.dim) : TpX{};
-	if (push_ex >= 0) {
-		PPush<WT, 1> p;
-		p.W = (const char *)d->wcls;
-		p.n = c.dim;
-		p.base = nullptr;
-		p.t = tpx_ex(d, push_ex);
-		p.offset = 0;
-		p.n_groups = c.vocab_size;
-		return launch_gemv<WT, PPush<WT, 1>, true>(p, d->x, d->rms_final, c.norm_eps, GK_CLS, d->gemv[GK_CLS],
-		                                           d->stream, tin);
+	if constexpr (!WT::Q4) {
+		if (push_ex >= 0) {
+			PPush<WT, 1> p;
+			p.W = (const char *)d->wcls;
+			p.n = c.dim;
+			p.base = nullptr;
+			p.t = tpx_ex(d, push_ex);
+			p.offset = 0;
+			p.n_groups = c.vocab_size;
+			return launch_gemv<WT, PPush<WT, 1>, true>(p, d->x, d->rms_final, c.norm_eps, GK_CLS, d->gemv[GK_CLS],
+			                                           d->stream, tin);
+		}
 	}
 	if (c.vocab_size % 2 == 0) {
 		PStore<WT, 2> p;
@@ -915,6 +992,12 @@ static int enqueue_begin_t(yalm_decoder_s *d, int n_ex) {
 }
 
 #define DISPATCH_WT(dtype, FN, ...)                                                                                    \
+	((dtype) == YALM_F32   ? FN<WF32>(__VA_ARGS__)                                                                     \
+	 : (dtype) == YALM_F16 ? FN<WF16>(__VA_ARGS__)                                                                     \
+	 : (dtype) == YALM_Q4  ? FN<WQ4>(__VA_ARGS__)                                                                      \
+	                       : FN<WF8>(__VA_ARGS__))
+// the element-typed formats alone (the expert kernels)
+#define DISPATCH_WT_EL(dtype, FN, ...)                                                                                 \
 	((dtype) == YALM_F32   ? FN<WF32>(__VA_ARGS__)                                                                     \
 	 : (dtype) == YALM_F16 ? FN<WF16>(__VA_ARGS__)                                                                     \
 	                       : FN<WF8>(__VA_ARGS__))
@@ -1007,10 +1090,14 @@ static int validate_config(const yalm_config *c) {
 	           c->vocab_size > 0 && c->max_seq_len > 2,
 	       "config: non-positive dimension");
 	ARGCHK(c->n_heads % c->n_kv_heads == 0, "config: n_heads % n_kv_heads != 0");
-	ARGCHK(c->weight_dtype == YALM_F32 || c->weight_dtype == YALM_F16 || c->weight_dtype == YALM_F8E5M2,
-	       "config: weight_dtype must be F32, F16 or F8E5M2");
+	ARGCHK(c->weight_dtype == YALM_F32 || c->weight_dtype == YALM_F16 || c->weight_dtype == YALM_F8E5M2 ||
+	           c->weight_dtype == YALM_Q4,
+	       "config: weight_dtype must be F32, F16, F8E5M2 or Q4");
 	ARGCHK(c->dim % 16 == 0 && c->hidden_dim % 16 == 0 && (c->n_heads * c->head_dim) % 16 == 0,
 	       "config: dim, hidden_dim and n_heads*head_dim must be multiples of 16 (infer.cpp:66)");
+	ARGCHK(c->weight_dtype != YALM_Q4 ||
+	           (c->dim % 32 == 0 && c->hidden_dim % 32 == 0 && (c->n_heads * c->head_dim) % 32 == 0),
+	       "config: q4 needs dim, hidden_dim and n_heads*head_dim multiples of 32 (its scale group)");
 	ARGCHK(c->rotary_dim <= c->head_dim && c->rotary_dim % 2 == 0, "config: bad rotary_dim");
 	if (!attn_supported(c->head_dim, c->n_heads / c->n_kv_heads)) {
 		set_err("config: attention kernel needs head_dim in {16,32,64,128,256} and n_heads/n_kv_heads <= 8");
@@ -1186,6 +1273,11 @@ extern "C" int yalm_decoder_create_moe(const yalm_config *config, const yalm_moe
                                        const yalm_model_weights *weights, const void *const *moegate, yalm_stream s,
                                        yalm_decoder *out) {
 	ARGCHK(config && moe && moegate, "yalm_decoder_create_moe: null argument");
+	if (config->weight_dtype == YALM_Q4) {
+		set_err("yalm_decoder_create_moe: q4 weights have no mixture-of-experts form (the expert kernels address "
+		        "their own chunks)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	for (int l = 0; l < config->n_layers; ++l)
 		ARGCHK(moegate[l], "yalm_decoder_create_moe: null moegate pointer");
 	return create_decoder(config, weights, s, out, nullptr, 0, 1, config->vocab_size, moe, moegate);
@@ -1240,6 +1332,11 @@ extern "C" int yalm_decoder_create_tp(const yalm_config *config, const yalm_mode
                                       int tp_size, const void *unique_id, yalm_stream s, yalm_decoder *out) {
 	ARGCHK(config && weights && unique_id && out, "yalm_decoder_create_tp: null argument");
 	ARGCHK(tp_size >= 1 && tp_rank >= 0 && tp_rank < tp_size, "yalm_decoder_create_tp: bad rank / size");
+	if (config->weight_dtype == YALM_Q4) {
+		set_err("yalm_decoder_create_tp: q4 weights have no tensor-parallel form (a column shard of a q4 row is "
+		        "two strided pieces)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	const yalm_config &f = *config;
 	yalm_config lc;
 	TRY(tp_local_config(f, tp_size, lc));
@@ -1298,6 +1395,11 @@ extern "C" int yalm_decoder_create_tp_ipc(const yalm_config *config, const yalm_
                                           yalm_decoder *out) {
 	ARGCHK(config && weights && own_buf && handles && out, "yalm_decoder_create_tp_ipc: null argument");
 	ARGCHK(tp_size >= 1 && tp_size <= 8 && tp_rank >= 0 && tp_rank < tp_size, "bad rank / size (1..8 ranks)");
+	if (config->weight_dtype == YALM_Q4) {
+		set_err("yalm_decoder_create_tp_ipc: q4 weights have no tensor-parallel form (a column shard of a q4 row is "
+		        "two strided pieces)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	yalm_config lc;
 	TRY(tp_local_config(*config, tp_size, lc));
 	ARGCHK(config->dim % (64 * (config->weight_dtype == YALM_F32 ? 4 : config->weight_dtype == YALM_F16 ? 8 : 16)) == 0,
@@ -1563,13 +1665,15 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	const yalm_config &c = d->c;
 	const yalm_block_weights &w = d->b[l];
 	const int q_dim = c.n_heads * c.head_dim;
-	if (d->moe_E > 0 && (kernel_id == 3 || kernel_id == 4 || kernel_id == 9)) { // the layer's last routing
-		const MoeArgs a = moe_layer_args(d, l);
-		if (kernel_id == 9)
-			return launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->stream);
-		if (kernel_id == 3)
-			return launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], d->stream);
-		return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], d->stream);
+	if constexpr (!WT::Q4) {
+		if (d->moe_E > 0 && (kernel_id == 3 || kernel_id == 4 || kernel_id == 9)) { // the layer's last routing
+			const MoeArgs a = moe_layer_args(d, l);
+			if (kernel_id == 9)
+				return launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->stream);
+			if (kernel_id == 3)
+				return launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], d->stream);
+			return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], d->stream);
+		}
 	}
 	switch (kernel_id) {
 	case 0:
@@ -1620,7 +1724,7 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	case 6:
 		return enqueue_exchange(d);
 	case 8: // fused attention + Wo (IPC: pushing exchange 0 of the bumped sequence, unread)
-		if constexpr (WT::BYTES <= 2)
+		if constexpr (wt_fused_wo<WT>())
 			return launch_attn_wo<WT>(d, w, l, 0);
 		break;
 	case 10: // the sampling launch on the current logits; commits into a scratch step state
@@ -1758,7 +1862,10 @@ extern "C" int yalm_set_gemv_config(yalm_decoder d, int kind, int threads, int u
 extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 	if (!d)
 		return "";
-	const char *wt = d->c.weight_dtype == YALM_F32 ? "WF32" : d->c.weight_dtype == YALM_F16 ? "WF16" : "WF8";
+	const char *wt = d->c.weight_dtype == YALM_F32   ? "WF32"
+	                 : d->c.weight_dtype == YALM_F16 ? "WF16"
+	                 : d->c.weight_dtype == YALM_Q4  ? "WQ4"
+	                                                 : "WF8";
 	const std::string gk = std::string("gemv_rb_kernel<") + wt;
 	std::string s;
 	switch (kernel_id) {
@@ -1919,11 +2026,12 @@ static int matmul_t(float *out, const float *x, const void *w, int n, int d) {
 
 extern "C" int yalm_matmul(float *xout, const float *x, const void *w, int n, int d, int dtype) {
 	ARGCHK(xout && x && w && n > 0 && d > 0, "bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "bad dtype");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4, "bad dtype");
 	ARGCHK(n % 16 == 0, "n must be a multiple of 16 (infer.cpp:66)");
+	ARGCHK(dtype != YALM_Q4 || n % 32 == 0, "q4: n must be a multiple of 32");
 	DevBuf dx, dw, dout;
 	TRY(up(dx, x, sizeof(float) * n));
-	TRY(up(dw, w, wbytes(dtype) * (size_t)n * d));
+	TRY(up(dw, w, yalm_row_bytes(dtype, n) * (size_t)d));
 	TRY(up(dout, nullptr, sizeof(float) * d));
 	TRY(DISPATCH_WT(dtype, matmul_t, (float *)dout.p, (const float *)dx.p, dw.p, n, d));
 	HIPCHK(hipDeviceSynchronize());
@@ -2050,13 +2158,15 @@ static int ffn_t(float *out, const float *x, const void *w1, const void *w2, con
 extern "C" int yalm_ffn(float *xout, const float *x, const void *w1, const void *w2, const void *w3, int hidden_dim,
                         int dim, int act, int dtype) {
 	ARGCHK(xout && x && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "bad dtype");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4, "bad dtype");
 	ARGCHK(dim % 16 == 0 && hidden_dim % 16 == 0, "dims must be multiples of 16");
-	const size_t wb = wbytes(dtype) * (size_t)hidden_dim * dim;
+	ARGCHK(dtype != YALM_Q4 || (dim % 32 == 0 && hidden_dim % 32 == 0), "q4: dims must be multiples of 32");
+	const size_t wb = yalm_row_bytes(dtype, dim) * (size_t)hidden_dim;   // w1, w3: hidden_dim rows of dim
+	const size_t wb2 = yalm_row_bytes(dtype, hidden_dim) * (size_t)dim;  // w2: dim rows of hidden_dim
 	DevBuf dx, d1, d2, d3, dhb, dout;
 	TRY(up(dx, x, sizeof(float) * dim));
 	TRY(up(d1, w1, wb));
-	TRY(up(d2, w2, wb));
+	TRY(up(d2, w2, wb2));
 	TRY(up(d3, w3, wb));
 	TRY(up(dhb, nullptr, sizeof(float) * hidden_dim));
 	TRY(up(dout, nullptr, sizeof(float) * dim));
@@ -2078,6 +2188,10 @@ extern "C" int yalm_moe_ffn(float *xout, int *experts, float *weights, const flo
                             const void *w1, const void *w2, const void *w3, int n_experts, int n_active, int hidden_dim,
                             int dim, int act, int dtype) {
 	ARGCHK(xout && x && moegate && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "bad argument");
+	if (dtype == YALM_Q4) {
+		set_err("yalm_moe_ffn: q4 weights have no mixture-of-experts form");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "bad dtype");
 	ARGCHK(dim % 16 == 0 && hidden_dim % 16 == 0, "dims must be multiples of 16");
 	ARGCHK(act == YALM_SILU || act == YALM_GELU, "bad activation");
@@ -2095,7 +2209,7 @@ extern "C" int yalm_moe_ffn(float *xout, int *experts, float *weights, const flo
 	TRY(up(dwts, nullptr, sizeof(float) * n_active));
 	const MoeArgs a{dg.p, d1.p, d2.p, d3.p, n_experts, n_active, hidden_dim, dim, act, (int *)dsel.p, (float *)dwts.p,
 	                (float *)dhb.p};
-	TRY(DISPATCH_WT(dtype, moe_ffn_t, a, (float *)dout.p, (const float *)dx.p));
+	TRY(DISPATCH_WT_EL(dtype, moe_ffn_t, a, (float *)dout.p, (const float *)dx.p));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(xout, dout.p, sizeof(float) * dim, hipMemcpyDeviceToHost));
 	if (experts)

@@ -21,6 +21,7 @@ std::string dtype_to_string(DType dtype) {
 	case DType::I16: return "I16";
 	case DType::I8: return "I8";
 	case DType::U8: return "U8";
+	case DType::Q4: return "Q4";
 	}
 	return "UNKNOWN";
 }
@@ -36,6 +37,7 @@ size_t dtype_size(DType dtype) {
 	case DType::F8E4M3:
 	case DType::I8:
 	case DType::U8: return 1;
+	case DType::Q4: return 0; // no element size: rows are yalm_row_bytes(YALM_Q4, n)
 	}
 	return 0;
 }

@@ -26,6 +26,10 @@ enum class DType {
 	I16,
 	I8,
 	U8,
+	// Appended after the reference's values (codec.h:15-25 keeps its order): the 4-bit
+	// group-quantised WEIGHT format of a model ("dtype": "q4"), never a tensor's dtype -- its
+	// matrices are U8 tensors [rows, yalm_row_bytes(YALM_Q4, n)] (include/yalm_hip.h).
+	Q4,
 };
 std::string dtype_to_string(DType dtype);
 size_t dtype_size(DType dtype);

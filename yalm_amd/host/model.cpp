@@ -55,27 +55,45 @@ void Config::from_yalm(YALMData &yalm, int context) {
 		weight_dtype = DType::F16;
 	else if (dtype == "fp8")
 		weight_dtype = DType::F8E5M2;
+	else if (dtype == "q4")
+		weight_dtype = DType::Q4;
 	else
 		throw std::runtime_error("FATAL: unsupported dtype: " + dtype);
 	if (n_experts > 0 && !(n_experts_active >= 1 && n_experts_active <= n_experts && n_experts <= 64))
 		throw std::runtime_error("FATAL: mixture of experts needs 1 <= n_experts_active <= n_experts <= 64");
+	if (weight_dtype == DType::Q4 && n_experts > 0)
+		throw std::runtime_error("FATAL: q4 weights have no mixture-of-experts form");
+	if (weight_dtype == DType::Q4 && (dim % 32 || hidden_dim % 32 || (n_heads * head_dim) % 32))
+		throw std::runtime_error("FATAL: q4 needs dim, hidden_dim and n_heads * head_dim multiples of 32");
+}
+
+// the C ABI's code of a weight dtype (the reference's enum order, but q4)
+static int dtype_code(DType dt) {
+	return dt == DType::Q4 ? YALM_Q4 : (int)dt;
+}
+
+// bytes of one row of n weights (q4: nibble blocks + scales + padding)
+static size_t weight_row_bytes(DType dt, size_t n) {
+	return yalm_row_bytes(dtype_code(dt), (int)n);
 }
 
 size_t Config::active_bytes(size_t pos) const {
-	const size_t wsz = dtype_size(weight_dtype);
+	const size_t q_dim = (size_t)n_heads * head_dim;
+	const size_t rb_dim = weight_row_bytes(weight_dtype, dim), rb_q = weight_row_bytes(weight_dtype, q_dim),
+	             rb_h = weight_row_bytes(weight_dtype, hidden_dim);
 	size_t per_block = 2 * dim * sizeof(float);
-	per_block += (size_t)n_heads * head_dim * dim * wsz;
-	per_block += 2 * (size_t)n_kv_heads * head_dim * dim * wsz;
-	per_block += (size_t)n_heads * head_dim * dim * wsz;
+	per_block += q_dim * rb_dim;
+	per_block += 2 * (size_t)n_kv_heads * head_dim * rb_dim;
+	per_block += (size_t)dim * rb_q;
 	if (n_experts > 0) { // model.cpp:85-87: the router and the active experts
-		per_block += (size_t)n_experts * dim * wsz;
-		per_block += (size_t)n_experts_active * 3 * dim * hidden_dim * wsz;
+		per_block += (size_t)n_experts * rb_dim;
+		per_block += (size_t)n_experts_active * (2 * hidden_dim * rb_dim + dim * rb_h);
 	} else {
-		per_block += 3 * (size_t)dim * hidden_dim * wsz;
+		per_block += 2 * (size_t)hidden_dim * rb_dim + (size_t)dim * rb_h;
 	}
 	const size_t kv_len = std::min((size_t)max_seq_len, pos + 1);
 	per_block += 2 * kv_len * n_kv_heads * head_dim * sizeof(f16_t);
-	return dim * wsz + n_layers * per_block + dim * sizeof(float) + (size_t)vocab_size * dim * wsz;
+	return rb_dim + n_layers * per_block + dim * sizeof(float) + (size_t)vocab_size * rb_dim;
 }
 
 yalm_config Config::to_c() const {
@@ -93,7 +111,7 @@ yalm_config Config::to_c() const {
 	c.norm_eps = norm_eps;
 	c.act = act == ActivationType::SILU ? YALM_SILU : YALM_GELU;
 	c.qkv_clip = qkv_clip;
-	c.weight_dtype = (int)weight_dtype;
+	c.weight_dtype = dtype_code(weight_dtype);
 	return c;
 }
 
@@ -105,6 +123,13 @@ static const void *check_tensor(const Tensor *t, DType dt, std::array<int, 4> sh
 		throw std::runtime_error("FATAL: tensor mismatch for " + t->name + " (got " + dtype_to_string(t->dtype) +
 		                         ", expected " + dtype_to_string(dt) + ")");
 	return t->data;
+}
+
+// a weight matrix [rows][n] in the model's weight dtype; q4: a U8 tensor [rows, row bytes]
+static const void *check_weight(const Tensor *t, DType dt, int rows, int n) {
+	if (dt == DType::Q4)
+		return check_tensor(t, DType::U8, {rows, (int)weight_row_bytes(dt, n), 0, 0});
+	return check_tensor(t, dt, {rows, n, 0, 0});
 }
 
 static const Tensor *get_tensor(const YALMData &y, const std::string &key) {
@@ -142,19 +167,19 @@ Block::Block(int layer_i, std::shared_ptr<Config> config, const Tensor *rms_att_
 	const DType dt = c.weight_dtype;
 	_rms_att = check_tensor(rms_att_weight, DType::F32, {c.dim, 0, 0, 0});
 	_rms_ffn = check_tensor(rms_ffn_weight, DType::F32, {c.dim, 0, 0, 0});
-	_wq = check_tensor(wq, dt, {c.n_heads * c.head_dim, c.dim, 0, 0});
-	_wk = check_tensor(wk, dt, {c.n_kv_heads * c.head_dim, c.dim, 0, 0});
-	_wv = check_tensor(wv, dt, {c.n_kv_heads * c.head_dim, c.dim, 0, 0});
-	_wo = check_tensor(wo, dt, {c.dim, c.n_heads * c.head_dim, 0, 0});
+	_wq = check_weight(wq, dt, c.n_heads * c.head_dim, c.dim);
+	_wk = check_weight(wk, dt, c.n_kv_heads * c.head_dim, c.dim);
+	_wv = check_weight(wv, dt, c.n_kv_heads * c.head_dim, c.dim);
+	_wo = check_weight(wo, dt, c.dim, c.n_heads * c.head_dim);
 	if (c.n_experts > 0) { // model.cpp:160-164
 		_moegate = check_tensor(moegate, dt, {c.n_experts, c.dim, 0, 0});
 		_w1 = check_tensor(w1, dt, {c.n_experts, c.hidden_dim, c.dim, 0});
 		_w2 = check_tensor(w2, dt, {c.n_experts, c.dim, c.hidden_dim, 0});
 		_w3 = check_tensor(w3, dt, {c.n_experts, c.hidden_dim, c.dim, 0});
 	} else {
-		_w1 = check_tensor(w1, dt, {c.hidden_dim, c.dim, 0, 0});
-		_w2 = check_tensor(w2, dt, {c.dim, c.hidden_dim, 0, 0});
-		_w3 = check_tensor(w3, dt, {c.hidden_dim, c.dim, 0, 0});
+		_w1 = check_weight(w1, dt, c.hidden_dim, c.dim);
+		_w2 = check_weight(w2, dt, c.dim, c.hidden_dim);
+		_w3 = check_weight(w3, dt, c.hidden_dim, c.dim);
 	}
 }
 
@@ -175,20 +200,21 @@ void Block::cuda() {
 	if (_device != Device::CPU)
 		return;
 	const Config &c = *_config;
-	const size_t wsz = dtype_size(c.weight_dtype);
 	const size_t q_dim = (size_t)c.n_heads * c.head_dim, kv_dim = (size_t)c.n_kv_heads * c.head_dim;
+	const size_t rb_dim = weight_row_bytes(c.weight_dtype, c.dim), rb_q = weight_row_bytes(c.weight_dtype, q_dim),
+	             rb_h = weight_row_bytes(c.weight_dtype, c.hidden_dim);
 	_rms_att = upload(_owned, _rms_att, c.dim * sizeof(float));
 	_rms_ffn = upload(_owned, _rms_ffn, c.dim * sizeof(float));
-	_wq = upload(_owned, _wq, q_dim * c.dim * wsz);
-	_wk = upload(_owned, _wk, kv_dim * c.dim * wsz);
-	_wv = upload(_owned, _wv, kv_dim * c.dim * wsz);
-	_wo = upload(_owned, _wo, c.dim * q_dim * wsz);
+	_wq = upload(_owned, _wq, q_dim * rb_dim);
+	_wk = upload(_owned, _wk, kv_dim * rb_dim);
+	_wv = upload(_owned, _wv, kv_dim * rb_dim);
+	_wo = upload(_owned, _wo, c.dim * rb_q);
 	const size_t ne = c.n_experts > 0 ? c.n_experts : 1; // the whole expert stacks (the reference uploads none)
-	_w1 = upload(_owned, _w1, ne * c.hidden_dim * c.dim * wsz);
-	_w2 = upload(_owned, _w2, ne * c.dim * c.hidden_dim * wsz);
-	_w3 = upload(_owned, _w3, ne * c.hidden_dim * c.dim * wsz);
+	_w1 = upload(_owned, _w1, ne * c.hidden_dim * rb_dim);
+	_w2 = upload(_owned, _w2, ne * c.dim * rb_h);
+	_w3 = upload(_owned, _w3, ne * c.hidden_dim * rb_dim);
 	if (_moegate)
-		_moegate = upload(_owned, _moegate, (size_t)c.n_experts * c.dim * wsz);
+		_moegate = upload(_owned, _moegate, (size_t)c.n_experts * rb_dim);
 	_device = Device::HIP;
 	// The KV cache is allocated (zeroed) by the decoder in HBM: no host copy
 	// to upload (model.cpp:208-210 uploads a zero host array).
@@ -213,8 +239,7 @@ Model::Model(YALMData &yalm, int context) {
 	config->from_yalm(yalm, context);
 	std::cout << "loading model with dtype: " << dtype_to_string(config->weight_dtype) << std::endl;
 	const Config &c = *config;
-	token_embedding_table = check_tensor(get_tensor(yalm, "model.embed.weight"), c.weight_dtype,
-	                                     {c.vocab_size, c.dim, 0, 0});
+	token_embedding_table = check_weight(get_tensor(yalm, "model.embed.weight"), c.weight_dtype, c.vocab_size, c.dim);
 	for (int i = 0; i < c.n_layers; ++i) {
 		const std::string p = "model.layers." + std::to_string(i) + ".";
 		blocks.emplace_back(std::make_shared<Block>(
@@ -227,7 +252,7 @@ Model::Model(YALMData &yalm, int context) {
 	rms_final_weight = check_tensor(get_tensor(yalm, "model.norm.weight"), DType::F32, {c.dim, 0, 0, 0});
 	_tied = yalm.tensors.count("model.output.weight") == 0;
 	wcls = _tied ? token_embedding_table
-	             : check_tensor(get_tensor(yalm, "model.output.weight"), c.weight_dtype, {c.vocab_size, c.dim, 0, 0});
+	             : check_weight(get_tensor(yalm, "model.output.weight"), c.weight_dtype, c.vocab_size, c.dim);
 }
 
 Model::~Model() {
@@ -241,13 +266,13 @@ void Model::cuda() {
 		return;
 	check(yalm_set_device(0), "set device");
 	const Config &c = *config;
-	const size_t wsz = dtype_size(c.weight_dtype);
-	token_embedding_table = upload(_owned, token_embedding_table, (size_t)c.vocab_size * c.dim * wsz);
+	const size_t emb_bytes = (size_t)c.vocab_size * weight_row_bytes(c.weight_dtype, c.dim);
+	token_embedding_table = upload(_owned, token_embedding_table, emb_bytes);
 	for (auto &b : blocks)
 		b->cuda();
 	rms_final_weight = upload(_owned, rms_final_weight, c.dim * sizeof(float));
 	// tied classifier: alias the uploaded embedding (the reference uploads it twice, model.cpp:388/393)
-	wcls = _tied ? token_embedding_table : upload(_owned, wcls, (size_t)c.vocab_size * c.dim * wsz);
+	wcls = _tied ? token_embedding_table : upload(_owned, wcls, emb_bytes);
 	_device = Device::HIP;
 }
 

@@ -10,13 +10,30 @@ import dataclasses
 import numpy as np
 
 F32, F16, BF16, F8E5M2 = 0, 1, 2, 3
+Q4 = 16  # YALM_Q4: 4-bit groups of 32 with an f16 scale (this engine's own format; "q4" below)
 GELU, SILU = 0, 1
 FLT_MAX = 3.4028234663852886e38
 KV_SINKS = 2  # model.h:12
 
-DTYPE_NAMES = {"fp32": F32, "fp16": F16, "fp8": F8E5M2}
-DTYPE_STRINGS = {F32: "F32", F16: "F16", F8E5M2: "F8_E5M2"}
-DTYPE_BYTES = {F32: 4, F16: 2, F8E5M2: 1}
+DTYPE_NAMES = {"fp32": F32, "fp16": F16, "fp8": F8E5M2, "q4": Q4}
+DTYPE_STRINGS = {F32: "F32", F16: "F16", F8E5M2: "F8_E5M2", Q4: "U8"}  # q4 rows are stored as U8 tensors
+DTYPE_BYTES = {F32: 4, F16: 2, F8E5M2: 1}  # per element; q4 has no element size: row_bytes
+Q4_GROUP = 32
+
+
+def row_bytes(dtype: int, n: int) -> int:
+    """Bytes of one row of n elements of a weight matrix (yalm_row_bytes). q4: n / 32 16-byte
+    nibble blocks, n / 32 f16 scales, zero padding to a multiple of 16."""
+    if dtype == Q4:
+        if n % Q4_GROUP:
+            raise ValueError(f"q4: row length {n} is not a multiple of {Q4_GROUP}")
+        return (n // 2 + n // 16 + 15) // 16 * 16
+    return n * DTYPE_BYTES[dtype]
+
+
+def matrix_bytes(dtype: int, shape) -> int:
+    """Bytes of a stored weight tensor of logical shape (..., rows, n)."""
+    return int(np.prod(shape[:-1])) * row_bytes(dtype, int(shape[-1]))
 
 
 @dataclasses.dataclass
@@ -62,16 +79,16 @@ class ModelConfig:
         """Algorithmic HBM bytes read per decode token, excluding the KV cache
         (SURVEY.md §8d): every layer's weights + norms, one embedding row, the
         final norm and the classifier."""
-        wb = DTYPE_BYTES[self.weight_dtype]
+        rb_dim, rb_q, rb_h = (row_bytes(self.weight_dtype, n) for n in (self.dim, self.q_dim, self.hidden_dim))
         per_layer = 2 * self.dim * 4
-        per_layer += (self.q_dim + 2 * self.kv_dim) * self.dim * wb  # wq wk wv
-        per_layer += self.dim * self.q_dim * wb  # wo
+        per_layer += (self.q_dim + 2 * self.kv_dim) * rb_dim  # wq wk wv
+        per_layer += self.dim * rb_q  # wo
         if self.n_experts > 0:  # model.cpp:85-87: the router + the active experts
-            per_layer += self.n_experts * self.dim * wb
-            per_layer += self.n_experts_active * 3 * self.dim * self.hidden_dim * wb
+            per_layer += self.n_experts * rb_dim
+            per_layer += self.n_experts_active * (2 * self.hidden_dim * rb_dim + self.dim * rb_h)
         else:
-            per_layer += 3 * self.dim * self.hidden_dim * wb  # w1 w2 w3
-        return self.n_layers * per_layer + self.dim * wb + self.dim * 4 + self.vocab_size * self.dim * wb
+            per_layer += 2 * self.hidden_dim * rb_dim + self.dim * rb_h  # w1 w3, w2
+        return self.n_layers * per_layer + rb_dim + self.dim * 4 + self.vocab_size * rb_dim
 
     def kv_bytes_per_token(self, kv_len: int) -> int:
         """fp16 K and V rows read by attention at kv_len (2 * 2 B * kv_dim per row, per layer)."""
@@ -361,19 +378,113 @@ def realistic_names(c: ModelConfig) -> list:
     return out
 
 
-def decode_weights(a: np.ndarray, dtype: int) -> np.ndarray:
-    """Stored weights (f32 / f16 / E5M2 bytes) -> float32, exactly."""
+# ---- q4: symmetric 4-bit groups of 32 with a restricted f16 scale (include/yalm_hip.h) ----
+# value = (u - 8) * s. The scale's low 3 mantissa bits are zero (8 significant bits), so every
+# value is an exact f16: a q4 model has an exact f16 twin (q4_twin), as fp8 has.
+def q4_restrict_scale(bits: np.ndarray) -> np.ndarray:
+    """f16 bit patterns -> the nearest restricted ones (low 3 mantissa bits zero; ties up)."""
+    return ((np.asarray(bits).astype(np.uint32) + 4) & ~np.uint32(7)).astype(np.uint16)
+
+
+def q4_scales(amax: np.ndarray) -> np.ndarray:
+    """Per group: the smallest restricted f16 scale s with 7 s >= amax (0 for amax 0), as f16 bits."""
+    amax = np.asarray(amax, np.float64)
+    with np.errstate(over="ignore"):
+        h = (amax / 7.0).astype(np.float16)
+    b = h.view(np.uint16).astype(np.uint32) & ~np.uint32(7)  # a restricted value at or below amax / 7
+    b = np.minimum(b, 0x7BF8)  # the largest finite restricted f16 (65024)
+    for _ in range(3):  # step up (8 in the bit pattern is the next restricted value) until 7 s >= amax
+        s = b.astype(np.uint16).view(np.float16).astype(np.float64)
+        b = np.where((7.0 * s < amax) & (b < 0x7BF8), b + 8, b)
+    # ... and down while the one below still covers amax (h rounded up past a restricted value)
+    lo = np.maximum(b.astype(np.int64) - 8, 0).astype(np.uint32)
+    s_lo = lo.astype(np.uint16).view(np.float16).astype(np.float64)
+    b = np.where((b >= 8) & (7.0 * s_lo >= amax), lo, b)
+    return b.astype(np.uint16)
+
+
+# nibble position (4-bit field index inside a 32-bit word) of element i of the word's 8:
+# elements 2 k and 2 k + 1 sit 16 bits apart, so one mask of the word yields an adjacent pair
+Q4_NIBBLE_POS = np.array([(i >> 1) + 4 * (i & 1) for i in range(8)])
+
+
+def q4_pack(u: np.ndarray, scale_bits: np.ndarray) -> np.ndarray:
+    """Nibbles u (rows, n) in 0..15 and f16 scale bits (rows, n / 32) -> uint8 rows
+    (rows, row_bytes(Q4, n)): nibble blocks, scales, zero padding."""
+    u = np.asarray(u)
+    rows, n = u.shape
+    rb = row_bytes(Q4, n)
+    w = np.zeros((rows, n // 8), np.uint32)
+    u8 = u.reshape(rows, n // 8, 8).astype(np.uint32)
+    for i in range(8):
+        w |= (u8[:, :, i] & 15) << np.uint32(4 * Q4_NIBBLE_POS[i])
+    out = np.zeros((rows, rb), np.uint8)
+    out[:, : n // 2] = w.astype("<u4").view(np.uint8).reshape(rows, n // 2)
+    out[:, n // 2: n // 2 + n // 16] = np.ascontiguousarray(scale_bits, dtype="<u2").view(np.uint8).reshape(rows, n // 16)
+    return out
+
+
+def q4_unpack(a: np.ndarray, n: int):
+    """uint8 rows (rows, row_bytes(Q4, n)) -> (nibbles (rows, n) uint8, scale bits (rows, n / 32) uint16)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    rows = a.shape[0]
+    w = np.ascontiguousarray(a[:, : n // 2]).view("<u4").astype(np.uint32)
+    u = np.zeros((rows, n // 8, 8), np.uint8)
+    for i in range(8):
+        u[:, :, i] = (w >> np.uint32(4 * Q4_NIBBLE_POS[i])) & 15
+    sb = np.ascontiguousarray(a[:, n // 2: n // 2 + n // 16]).view("<u2").astype(np.uint16)
+    return u.reshape(rows, n), sb
+
+
+def q4_quantize(v: np.ndarray) -> np.ndarray:
+    """float matrix (rows, n), n % 32 == 0 -> q4 rows. Per group amax = max |w|, s = the smallest
+    restricted f16 with 7 s >= amax, u = clip(rint(w / s), -7, 7) + 8 (all-zero group: s = 0,
+    u = 8), so |w - (u - 8) s| <= s / 2 for every element."""
+    v = np.asarray(v, np.float64)
+    rows, n = v.shape
+    g = v.reshape(rows, n // Q4_GROUP, Q4_GROUP)
+    sb = q4_scales(np.abs(g).max(axis=2))
+    s = sb.view(np.float16).astype(np.float64)[:, :, None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(s > 0, np.rint(g / np.where(s > 0, s, 1.0)), 0.0)
+    u = (np.clip(q, -7, 7) + 8).astype(np.uint8).reshape(rows, n)
+    return q4_pack(u, sb)
+
+
+def q4_dequantize(a: np.ndarray, n: int) -> np.ndarray:
+    """q4 rows -> float32 (rows, n), exactly ((u - 8) * s; every value is an f16)."""
+    u, sb = q4_unpack(a, n)
+    s = sb.view(np.float16).astype(np.float32)
+    return ((u.astype(np.float32) - 8.0).reshape(u.shape[0], -1, Q4_GROUP) * s[:, :, None]).reshape(u.shape[0], n)
+
+
+def q4_twin(cfg: ModelConfig, tensors: dict):
+    """The exact f16 twin of a q4 model: (f16 config, tensors with every q4 matrix as float16)."""
+    out = {}
+    for name, (shape, is_norm) in tensor_shapes(cfg).items():
+        out[name] = tensors[name] if is_norm else decode_weights(tensors[name], Q4, shape).astype(np.float16)
+    return cfg.with_(weight_dtype=F16), out
+
+
+def decode_weights(a: np.ndarray, dtype: int, shape=None) -> np.ndarray:
+    """Stored weights (f32 / f16 / E5M2 bytes / q4 rows) -> float32, exactly. q4 needs the
+    logical shape (rows, n)."""
     if dtype == F8E5M2:
         return e5m2_to_f32(a)
+    if dtype == Q4:
+        return q4_dequantize(a.reshape(-1, a.shape[-1]), int(shape[-1])).reshape(shape)
     return a.astype(np.float32)
 
 
 def encode_weights(v: np.ndarray, dtype: int) -> np.ndarray:
     """float32 -> stored weights: f16 round to nearest even; E5M2 through f16, then round
-    to nearest even on the byte (the initialiser's rule, synth_array)."""
+    to nearest even on the byte (the initialiser's rule, synth_array); q4: q4_quantize on the
+    matrix (rows, n)."""
     v = np.asarray(v, np.float32)
     if dtype == F32:
         return v
+    if dtype == Q4:
+        return q4_quantize(v.reshape(-1, v.shape[-1]))
     h16 = v.astype(np.float16)
     if dtype == F16:
         return h16
@@ -438,15 +549,34 @@ def synth_array(n: int, dtype: int, seed: int, scale: float, offset: float = 0.0
     return ((hb + 0x7F + ((hb >> 8) & 1)) >> 8).astype(np.uint8)
 
 
+def synth_q4_array(rows: int, n: int, seed: int, scale: float) -> np.ndarray:
+    """numpy twin of yalm_synth_q4: nibble byte i of the tensor (row-major, nibble bytes only) is
+    bits 40..47 of hash i; every scale is the restricted f16 nearest scale / 7; padding zero."""
+    with np.errstate(over="ignore"):
+        i = np.arange(rows * (n // 2), dtype=np.uint64)
+        h = _splitmix64(np.uint64(seed) ^ (i * np.uint64(0xD1B54A32D192ED03)))
+    out = np.zeros((rows, row_bytes(Q4, n)), np.uint8)
+    out[:, : n // 2] = ((h >> np.uint64(40)) & np.uint64(0xFF)).astype(np.uint8).reshape(rows, n // 2)
+    sb = q4_restrict_scale((np.float32(scale) / np.float32(7.0)).astype(np.float16).view(np.uint16))
+    out[:, n // 2: n // 2 + n // 16] = np.full((rows, n // 32), sb, "<u2").view(np.uint8).reshape(rows, n // 16)
+    return out
+
+
 def synth_host_tensors(c: ModelConfig, seed: int = 1, peak: float = 1.0, real: Realistic = None) -> dict:
     """All tensors of a synthetic model as numpy arrays (norms f32, weights in
-    c.weight_dtype storage: f32 / f16 / uint8 E5M2 bits); real: the realistic model."""
+    c.weight_dtype storage: f32 / f16 / uint8 E5M2 bits / uint8 q4 rows); real: the realistic
+    model (not for q4: its patches address elements of the stored array)."""
+    if real is not None and c.weight_dtype == Q4:
+        raise ValueError("the realistic synthetic model has no q4 form: quantise its f16 tensors (q4_quantize)")
     out = {}
     for name, (shape, is_norm) in tensor_shapes(c).items():
         scale, offset = synth_params(name, is_norm, peak, real, c.tied)
         dt = F32 if is_norm else c.weight_dtype
         n = int(np.prod(shape))
-        out[name] = synth_array(n, dt, synth_seed(seed, name), scale, offset).reshape(shape)
+        if dt == Q4:
+            out[name] = synth_q4_array(n // shape[-1], shape[-1], synth_seed(seed, name), scale)
+        else:
+            out[name] = synth_array(n, dt, synth_seed(seed, name), scale, offset).reshape(shape)
     return apply_realistic(c, out, real) if real is not None else out
 
 
@@ -475,9 +605,8 @@ def kv_indices(max_seq_len: int, pos: int):
 
 
 def nbytes_model(c: ModelConfig) -> int:
-    wb = DTYPE_BYTES[c.weight_dtype]
     tot = 0
     for _, (shape, is_norm) in tensor_shapes(c).items():
-        tot += int(np.prod(shape)) * (4 if is_norm else wb)
+        tot += int(np.prod(shape)) * 4 if is_norm else matrix_bytes(c.weight_dtype, shape)
     return tot
 

@@ -99,6 +99,8 @@ _sig("yalm_stream_create", c_int, [ctypes.POINTER(c_void_p)])
 _sig("yalm_stream_destroy", c_int, [c_void_p])
 _sig("yalm_stream_sync", c_int, [c_void_p])
 _sig("yalm_synth", c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint64, c_float, c_float, c_void_p])
+_sig("yalm_row_bytes", c_size_t, [c_int, c_int])
+_sig("yalm_synth_q4", c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint64, c_float, c_void_p])
 _sig("yalm_decoder_create", c_int, [ctypes.POINTER(Config), ctypes.POINTER(ModelWeights), c_void_p,
                                      ctypes.POINTER(c_void_p)])
 _sig("yalm_decoder_create_moe", c_int, [ctypes.POINTER(Config), c_void_p, ctypes.POINTER(ModelWeights), c_void_p,
@@ -161,6 +163,7 @@ EXPORTED = [
     "yalm_decoder_create_moe", "yalm_moe_routing", "yalm_moe_ffn",
     "yalm_prefill_routing", "yalm_moe_gemm_f16", "yalm_moe_ffn_rows",
     "yalm_generate_sampled", "yalm_sample",
+    "yalm_row_bytes", "yalm_synth_q4",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -186,9 +189,13 @@ def _ptr(a: np.ndarray) -> int:
 
 # ------------------------------------------------------------- kernel-level test API
 def matmul(x: np.ndarray, w: np.ndarray, dtype: int) -> np.ndarray:
-    """matmul_cuda (infer.cu:937-957): W (d, n) @ x (n,)."""
+    """matmul_cuda (infer.cu:937-957): W (d, n) @ x (n,). q4: w is the uint8 rows
+    (d, row_bytes(Q4, n)) of models.q4_quantize; n is x's length."""
     d, n = w.shape
     x = np.ascontiguousarray(x, dtype=np.float32)
+    if dtype == M.Q4:
+        n = x.size
+        assert w.dtype == np.uint8 and w.shape[1] == M.row_bytes(M.Q4, n)
     w = np.ascontiguousarray(w)
     out = np.zeros(d, np.float32)
     check(lib.yalm_matmul(_ptr(out), _ptr(x), _ptr(w), n, d, dtype))
@@ -231,9 +238,13 @@ def sample(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float 
 
 
 def ffn(x, w1, w2, w3, act: int, dtype: int) -> np.ndarray:
-    """ffn_cuda (infer.cu:959-1007)."""
+    """ffn_cuda (infer.cu:959-1007). q4: w1 / w3 (hidden_dim, row_bytes(Q4, dim)) and w2
+    (dim, row_bytes(Q4, hidden_dim)) uint8 rows."""
     hidden_dim, dim = w1.shape
     x = np.ascontiguousarray(x, dtype=np.float32)
+    if dtype == M.Q4:
+        dim = x.size
+        assert w2.shape == (dim, M.row_bytes(M.Q4, hidden_dim)) and w1.shape[1] == M.row_bytes(M.Q4, dim)
     w1, w2, w3 = (np.ascontiguousarray(a) for a in (w1, w2, w3))
     out = np.zeros(dim, np.float32)
     check(lib.yalm_ffn(_ptr(out), _ptr(x), _ptr(w1), _ptr(w2), _ptr(w3), hidden_dim, dim, act, dtype))
@@ -374,6 +385,8 @@ class DeviceModel:
         upload only this rank's shards (models.tp_shard)."""
         rank, size = tp
         M.tp_check(cfg, size)
+        if cfg.weight_dtype == M.Q4 and size > 1:
+            raise ValueError("q4 models run on one GPU (no tensor-parallel form)")
         self = cls(cfg)
         self.tp = tp
         items = dict(tensors)
@@ -424,9 +437,16 @@ class DeviceModel:
         for name, (shape, is_norm) in names:
             n = int(np.prod(shape))
             dt = M.F32 if is_norm else cfg.weight_dtype
-            eb = M.DTYPE_BYTES[dt]
             src_name = "model.embed.weight" if name == "tp.wcls" else name
             scale, offset = M.synth_params(src_name, is_norm, peak, real, cfg.tied)
+            if dt == M.Q4:  # padded rows with their scales: yalm_synth_q4 (never sharded: q4 runs on one GPU)
+                if size > 1 or real is not None:
+                    raise ValueError("q4 models are synthesised for one GPU, without the realistic patches")
+                p = self._alloc(M.matrix_bytes(M.Q4, shape))
+                check(lib.yalm_synth_q4(p, n // shape[-1], shape[-1], M.synth_seed(seed, src_name), scale, None))
+                self.ptrs[name] = p
+                continue
+            eb = M.DTYPE_BYTES[dt]
             sh = M.tp_shard(cfg, name, rank, size)
             if sh is None or len(shape) != 2:  # (stacked expert tensors are never sharded: tp_check)
                 p = self._alloc(n * eb)
