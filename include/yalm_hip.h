@@ -409,6 +409,62 @@ int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms);
  * unknown key is YALM_ERR_ARG. */
 int yalm_set_prefill_forms(yalm_decoder d, const char *spec);
 
+/* ---------------- multi-row forward and speculative greedy decode ----------------
+ * Dense decoders on one GPU with f32, f16 or fp8 weights. YALM_ERR_UNSUPPORTED, with a
+ * yalm_last_error naming the reason: q4 weights, mixture-of-experts decoders
+ * (yalm_decoder_create_moe), tensor-parallel decoders (yalm_decoder_create_tp / _tp_ipc). */
+/* T tokens (1 <= T <= 4) at positions pos .. pos + T - 1 through every layer in ONE pass over
+ * the weights (csrc/gemv_rows.h: each weight matrix is streamed once for all T rows; f32
+ * activations and accumulation, as yalm_forward). Row t attends to keys 0 .. pos + t; the KV
+ * rows pos .. pos + T - 1 are written where the decoder expects them, so yalm_forward /
+ * yalm_generate_greedy can continue at pos + T. logits_host: [T][vocab_size] floats (then the
+ * call is synchronous) or NULL. The device-resident (token, pos) of the greedy loop is set to
+ * (tokens[0], pos) and does not advance, as after an OUTPUT_LOGITS forward. YALM_ERR_ARG: T
+ * outside 1..4, a token out of range, pos < 0 or pos + T > max_seq_len (a multi-row step never
+ * wraps the ring or rotates the sinks). */
+int yalm_forward_rows(yalm_decoder d, const int *tokens, int T, int pos, float *logits_host);
+/* Speculative greedy decode (csrc/spec.h). A step runs `rows` rows through yalm_forward_rows'
+ * path: row 0 the token greedy decode would feed, rows k = 1..rows-1 drafted next tokens d_k (a
+ * row without a draft is fed token 0). With m_t the first-maximum argmax of row t (the rule of
+ * yalm_argmax), the step yields a = 1 + the longest prefix of drafts with d_k == m_(k-1) tokens,
+ * m_0 .. m_(a-1): exactly the tokens of plain greedy decode. KV rows of rejected drafts are
+ * overwritten by later steps.
+ * The drafter, in integers. History H[0, m) = the caller's context followed by every token
+ * produced so far; H[m - 1] is the token to feed next. For g = ngram_max down to ngram_min: take
+ * the LARGEST i with i + g <= m - 1 and H[i, i + g) == H[m - g, m); the first g that has such an
+ * i wins, and d_k = H[i + g + k - 1] for k = 1..rows-1 while that index is < m. Later drafts, and
+ * all of them when nothing matches, are "none"; a none row is never accepted. The context is
+ * capped at its last 65536 tokens.
+ * draft_stream (test and benchmark hook): when non-NULL the drafts of a step are
+ * draft_stream[p + k - 1], p = the tokens produced so far; none past draft_stream_len. */
+typedef struct yalm_spec {
+	int rows;                  /* 2..4 */
+	int ngram_max, ngram_min;  /* 1 <= ngram_min <= ngram_max <= 4 */
+	const int *draft_stream;   /* host, or NULL = the n-gram drafter */
+	int draft_stream_len;
+} yalm_spec;
+typedef struct yalm_spec_stats {
+	int spec_steps;        /* multi-row steps run */
+	int accepted_drafts;   /* drafts whose token was delivered: spec_steps + accepted_drafts + plain_steps == n_tokens */
+	int plain_steps;       /* plain greedy steps (at and past the window's end) */
+	int launches_per_step; /* kernel launches of one multi-row step: 4 + n_layers * (4 + rows) */
+} yalm_spec_stats;
+/* The contract of yalm_generate_greedy: feeds `token` at `pos`, writes exactly n_tokens tokens to
+ * out_tokens (host), and the decoder then continues at pos + n_tokens (yalm_device_step,
+ * yalm_enqueue_greedy, yalm_device_tokens) as after the greedy call. context (host, n_context
+ * tokens, may be NULL with n_context 0 = the history starts at `token`) must end with `token`.
+ * The host enqueues the steps in batches with no per-token round trip, reads the produced count
+ * once per batch, drops what the last step accepted past n_tokens and sets the device (token,
+ * pos) accordingly. A step needs pos + rows <= max_seq_len; from the first position where that
+ * fails the call finishes with plain greedy steps, so it works at any pos. stats may be NULL.
+ * YALM_ERR_ARG: rows outside 2..4, ngram bounds outside 1 <= min <= max <= 4, n_tokens above
+ * the token buffer (65536), a context that does not end with token. */
+int yalm_generate_speculative(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
+                              const int *context, int n_context, int *out_tokens, yalm_spec_stats *stats);
+/* Test hook (host pointers, synchronous, no decoder): the drafter kernel on history[0, m),
+ * 1 <= m <= 131072; drafts_out[k - 1] = d_k for k = 1..rows-1, -1 for none. */
+int yalm_spec_draft(const int *history, int m, int rows, int ngram_max, int ngram_min, int *drafts_out);
+
 /* ---------------- test API: replaces infer.cu:890-1019 (model.h:370-384) ---------------- */
 /* Host pointers in and out; synchronous. dtype selects the weight type
  * (matmul_cuda<float|half|uint8_t>; YALM_Q4: w is d rows of yalm_row_bytes(YALM_Q4, n)). */

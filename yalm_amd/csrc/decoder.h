@@ -182,6 +182,15 @@ struct yalm_decoder_s {
 	// mixture of experts (yalm_decoder_create_moe, moe.h): b[l].w1 / w2 / w3 are stacked (n_experts, ...)
 	// tensors, hb holds moe_K * hidden_dim floats; 0 experts = a dense decoder
 	int moe_E = 0, moe_K = 0;
+	// multi-row forward and speculative greedy decode (gemv_rows.h, spec.h): allocated on first use
+	// (rows_init), so a decoder that never runs them keeps its footprint
+	StepState *rstep = nullptr;        // [4] per-row step states
+	float *rx = nullptr, *rq = nullptr, *rxb2 = nullptr, *rhb = nullptr, *rlogits = nullptr; // [4][...] activations
+	float *rlogits_pinned = nullptr;   // [4][vocab] host
+	struct SpecState *spec = nullptr;  // row tokens, drafts, counters
+	int *spec_ctx = nullptr;           // [tokens_cap] the caller's context (its last tokens_cap tokens)
+	int *spec_stream = nullptr;        // the draft_stream hook's tokens
+	int spec_stream_cap = 0;
 	std::vector<const void *> moegate; // [n_layers] router weights (n_experts, dim)
 	int *moe_sel = nullptr;            // [n_layers][moe_K] the routing of the most recent forward
 	float *moe_wts = nullptr;          // [n_layers][moe_K]

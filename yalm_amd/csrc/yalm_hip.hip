@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,9 +22,11 @@
 #include "decoder.h"
 #include "device_common.h"
 #include "gemv.h"
+#include "gemv_rows.h"
 #include "misc_kernels.h"
 #include "moe.h"
 #include "sampler.h"
+#include "spec.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local std::string g_err;
@@ -1118,6 +1121,8 @@ static void destroy_decoder(yalm_decoder_s *d) {
 		(void)hipFree(p);
 	if (d->logits_pinned)
 		(void)hipHostFree(d->logits_pinned);
+	if (d->rlogits_pinned)
+		(void)hipHostFree(d->rlogits_pinned);
 	if (d->own_stream && d->stream)
 		(void)hipStreamDestroy(d->stream);
 	delete d;
@@ -1595,6 +1600,314 @@ extern "C" int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_s
 	HIPCHK(hipMemcpyAsync(out_tokens, d->tokens, sizeof(int) * n_steps, hipMemcpyDeviceToHost, d->stream));
 	HIPCHK(hipStreamSynchronize(d->stream));
 	return awo_check(d);
+}
+
+// ------------------------------------------------------------------ multi-row forward, speculative greedy decode
+// (gemv_rows.h, spec.h) Dense decoders on one GPU, f32 / f16 / fp8 weights.
+static int rows_supported(const yalm_decoder_s *d, const char *who) {
+	const char *why = nullptr;
+	if (d->c.weight_dtype == YALM_Q4)
+		why = ": q4 weights have no multi-row form (gemv_rows.h streams element-typed rows)";
+	else if (d->moe_E > 0)
+		why = ": mixture-of-experts decoders have no multi-row form (each row routes to its own experts)";
+	else if (d->tp_size > 1 || d->comm || d->ipc)
+		why = ": tensor-parallel decoders have no multi-row form (the exchanges carry one row)";
+	if (!why)
+		return YALM_OK;
+	set_err(std::string(who) + why);
+	return YALM_ERR_UNSUPPORTED;
+}
+
+static int rows_init(yalm_decoder_s *d) {
+	if (d->rlogits_pinned)
+		return YALM_OK;
+	const yalm_config &c = d->c;
+	const int q_dim = c.n_heads * c.head_dim;
+	constexpr int T = ROWS_MAX_T;
+	static_assert(ROWS_MAX_T == SPEC_MAX_ROWS, "rows of a step");
+	TRY(dalloc(d, (void **)&d->rstep, sizeof(StepState) * T));
+	TRY(dalloc(d, (void **)&d->rx, sizeof(float) * T * c.dim));
+	TRY(dalloc(d, (void **)&d->rq, sizeof(float) * T * q_dim));
+	TRY(dalloc(d, (void **)&d->rxb2, sizeof(float) * T * q_dim));
+	TRY(dalloc(d, (void **)&d->rhb, sizeof(float) * T * c.hidden_dim));
+	TRY(dalloc(d, (void **)&d->rlogits, sizeof(float) * T * c.vocab_size));
+	TRY(dalloc(d, (void **)&d->spec, sizeof(SpecState)));
+	TRY(dalloc(d, (void **)&d->spec_ctx, sizeof(int) * d->tokens_cap));
+	d->spec_stream_cap = d->tokens_cap + 8;
+	TRY(dalloc(d, (void **)&d->spec_stream, sizeof(int) * d->spec_stream_cap));
+	HIPCHK(hipHostMalloc((void **)&d->rlogits_pinned, sizeof(float) * T * c.vocab_size, hipHostMallocDefault));
+	return YALM_OK;
+}
+
+// One launch of gemv_rows_kernel: x staged whole when T rows of it fit ROWS_X_BYTES (then a wave
+// takes several groups, about one workgroup per CU), else by K segments with one group per wave.
+template <class WT, class P, bool NORM>
+static int launch_rows(const P &p, const float *x, int xstride, const float *normw, float eps, int T, hipStream_t st) {
+	constexpr int CH = YALM_WAVE * WT::EPL;
+	constexpr int W = ROWS_THREADS / YALM_WAVE;
+	const int kcap = (int)(ROWS_X_BYTES / sizeof(float)) / T / CH * CH;
+	const int kseg = std::min((p.n + CH - 1) / CH * CH, kcap);
+	const int nseg = (p.n + kseg - 1) / kseg;
+	const int gpw = nseg > 1 ? 1 : std::max(1, p.n_groups / (W * device_cu_count()));
+	const int blocks = (p.n_groups + W * gpw - 1) / (W * gpw);
+	const size_t lds = ((size_t)T * kseg + (size_t)T * 16) * sizeof(float);
+	auto kern = T == 1   ? gemv_rows_kernel<WT, P, 1, NORM>
+	            : T == 2 ? gemv_rows_kernel<WT, P, 2, NORM>
+	            : T == 3 ? gemv_rows_kernel<WT, P, 3, NORM>
+	                     : gemv_rows_kernel<WT, P, 4, NORM>;
+	if (lds > 65536)
+		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+	hipLaunchKernelGGL(kern, dim3(blocks), dim3(ROWS_THREADS), lds, st, p, x, xstride, normw, eps, gpw, kseg);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+template <class WT, int ACT>
+static int launch_rows_glu(yalm_decoder_s *d, const yalm_block_weights &w, int T) {
+	const yalm_config &c = d->c;
+	RGlu<WT, ACT> p;
+	p.w1 = (const char *)w.w1;
+	p.w3 = (const char *)w.w3;
+	p.n = c.dim;
+	p.n_groups = c.hidden_dim;
+	p.out = d->rhb;
+	p.ostride = c.hidden_dim;
+	return launch_rows<WT, RGlu<WT, ACT>, true>(p, d->rx, c.dim, w.rms_ffn, c.norm_eps, T, d->stream);
+}
+
+// T rows through every layer: rows begin, then per layer QKV (+ clip, RoPE, KV write), one
+// attention launch per row (the decode kernel with that row's step state, q and out), Wo, W1|W3,
+// W2; then norm + logits into rlogits [T][vocab]. 2 + n_layers * (4 + T) launches.
+template <class WT>
+static int enqueue_rows_forward_t(yalm_decoder_s *d, int T, int from_step) {
+	if constexpr (WT::Q4) {
+		return rows_supported(d, "multi-row forward");
+	} else {
+		const yalm_config &c = d->c;
+		hipStream_t st = d->stream;
+		const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
+		static_assert(offsetof(SpecState, tok) == 0, "SpecState begins with the row tokens");
+		rows_begin_kernel<WT><<<1, 256, 0, st>>>(d->step, d->rstep, (const int *)d->spec, T, from_step, d->emb, c.dim,
+		                                          d->rx, d->inv_freq, c.head_dim / 2);
+		HIPCHK(hipGetLastError());
+		for (int l = 0; l < c.n_layers; ++l) {
+			const yalm_block_weights &w = d->b[l];
+			{
+				RQKV<WT> p;
+				p.base.wq = (const char *)w.wq;
+				p.base.wk = (const char *)w.wk;
+				p.base.wv = (const char *)w.wv;
+				p.base.n = c.dim;
+				p.base.q_dim = q_dim;
+				p.base.kv_dim = kv_dim;
+				p.base.head_dim = c.head_dim;
+				p.base.n_groups = (q_dim + 2 * kv_dim) / 2;
+				p.base.qkv_clip = c.qkv_clip;
+				p.base.inv_freq = d->inv_freq;
+				p.base.step = d->rstep;
+				p.base.q_out = d->rq;
+				p.base.kcache = w.key_cache;
+				p.base.vcache = w.value_cache;
+				p.n = c.dim;
+				p.n_groups = p.base.n_groups;
+				p.q_stride = q_dim;
+				TRY((launch_rows<WT, RQKV<WT>, true>(p, d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
+			}
+			for (int t = 0; t < T; ++t)
+				TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, d->rq + (size_t)t * q_dim, w.key_cache,
+				                w.value_cache, d->rstep + t, c.max_seq_len, d->part, l, c.n_layers, d->awo_err, nullptr,
+				                d->rxb2 + (size_t)t * q_dim, st));
+			{
+				RResidual<WT> p;
+				p.W = (const char *)w.wo;
+				p.n = q_dim;
+				p.n_rows = c.dim;
+				p.n_groups = (c.dim + 1) / 2;
+				p.out = d->rx;
+				p.ostride = c.dim;
+				TRY((launch_rows<WT, RResidual<WT>, false>(p, d->rxb2, q_dim, nullptr, 0.f, T, st)));
+			}
+			if (c.act == YALM_SILU)
+				TRY((launch_rows_glu<WT, 1>(d, w, T)));
+			else
+				TRY((launch_rows_glu<WT, 0>(d, w, T)));
+			{
+				RResidual<WT> p;
+				p.W = (const char *)w.w2;
+				p.n = c.hidden_dim;
+				p.n_rows = c.dim;
+				p.n_groups = (c.dim + 1) / 2;
+				p.out = d->rx;
+				p.ostride = c.dim;
+				TRY((launch_rows<WT, RResidual<WT>, false>(p, d->rhb, c.hidden_dim, nullptr, 0.f, T, st)));
+			}
+		}
+		RStore<WT> p;
+		p.W = (const char *)d->wcls;
+		p.n = c.dim;
+		p.n_rows = c.vocab_size;
+		p.n_groups = (c.vocab_size + 1) / 2;
+		p.out = d->rlogits;
+		p.ostride = c.vocab_size;
+		return launch_rows<WT, RStore<WT>, true>(p, d->rx, c.dim, d->rms_final, c.norm_eps, T, st);
+	}
+}
+
+static int enqueue_rows_forward(yalm_decoder_s *d, int T, int from_step) {
+	return DISPATCH_WT(d->c.weight_dtype, enqueue_rows_forward_t, d, T, from_step);
+}
+
+extern "C" int yalm_forward_rows(yalm_decoder d, const int *tokens, int T, int pos, float *logits_host) {
+	ARGCHK(d && tokens, "yalm_forward_rows: null argument");
+	TRY(rows_supported(d, "yalm_forward_rows"));
+	ARGCHK(T >= 1 && T <= ROWS_MAX_T, "yalm_forward_rows: 1 <= T <= 4 rows");
+	for (int t = 0; t < T; ++t)
+		ARGCHK(tokens[t] >= 0 && tokens[t] < d->vocab_full, "yalm_forward_rows: token out of range");
+	ARGCHK(pos >= 0 && (long long)pos + T <= d->c.max_seq_len,
+	       "yalm_forward_rows: pos + T must not exceed max_seq_len (no ring wrap inside a multi-row step)");
+	TRY(rows_init(d));
+	int tk[ROWS_MAX_T] = {0, 0, 0, 0};
+	for (int t = 0; t < T; ++t)
+		tk[t] = tokens[t];
+	spec_set_tok_kernel<<<1, 1, 0, d->stream>>>(d->spec, tk[0], tk[1], tk[2], tk[3]);
+	set_step_kernel<<<1, 1, 0, d->stream>>>(d->step, tk[0], pos, 0);
+	HIPCHK(hipGetLastError());
+	TRY(enqueue_rows_forward(d, T, 0));
+	d->host_pos = pos; // as an OUTPUT forward: the device position does not advance
+	if (logits_host) {
+		const size_t bytes = sizeof(float) * (size_t)T * d->c.vocab_size;
+		HIPCHK(hipMemcpyAsync(d->rlogits_pinned, d->rlogits, bytes, hipMemcpyDeviceToHost, d->stream));
+		HIPCHK(hipStreamSynchronize(d->stream));
+		TRY(awo_check(d));
+		memcpy(logits_host, d->rlogits_pinned, bytes);
+	}
+	return YALM_OK;
+}
+
+extern "C" int yalm_spec_draft(const int *history, int m, int rows, int ngram_max, int ngram_min, int *drafts_out) {
+	ARGCHK(history && drafts_out, "yalm_spec_draft: null argument");
+	ARGCHK(m >= 1 && m <= 2 * 65536, "yalm_spec_draft: history of 1..131072 tokens");
+	ARGCHK(rows >= 2 && rows <= SPEC_MAX_ROWS, "yalm_spec_draft: rows must be 2..4");
+	ARGCHK(ngram_min >= 1 && ngram_min <= ngram_max && ngram_max <= SPEC_MAX_NGRAM,
+	       "yalm_spec_draft: need 1 <= ngram_min <= ngram_max <= 4");
+	int *dh = nullptr, *dd = nullptr;
+	HIPCHK(hipMalloc((void **)&dh, sizeof(int) * m));
+	if (hipMalloc((void **)&dd, sizeof(int) * SPEC_MAX_ROWS) != hipSuccess) {
+		(void)hipFree(dh);
+		set_err("yalm_spec_draft: hipMalloc failed");
+		return YALM_ERR_HIP;
+	}
+	int out[SPEC_MAX_ROWS] = {-1, -1, -1, -1};
+	hipError_t e = hipMemcpy(dh, history, sizeof(int) * m, hipMemcpyHostToDevice);
+	if (e == hipSuccess) {
+		spec_draft_test_kernel<<<1, SPEC_DRAFT_THREADS>>>(dh, m, rows, ngram_max, ngram_min, dd);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess)
+		e = hipMemcpy(out, dd, sizeof(out), hipMemcpyDeviceToHost);
+	(void)hipFree(dh);
+	(void)hipFree(dd);
+	if (e != hipSuccess) {
+		set_err(std::string("yalm_spec_draft failed: ") + hipGetErrorString(e));
+		return YALM_ERR_HIP;
+	}
+	for (int k = 1; k < rows; ++k)
+		drafts_out[k - 1] = out[k];
+	return YALM_OK;
+}
+
+extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
+                                         const int *context, int n_context, int *out_tokens,
+                                         yalm_spec_stats *stats) {
+	ARGCHK(d && cfg && (out_tokens || n_tokens == 0), "yalm_generate_speculative: null argument");
+	TRY(rows_supported(d, "yalm_generate_speculative"));
+	ARGCHK(token >= 0 && token < d->vocab_full && pos >= 0 && n_tokens >= 0,
+	       "yalm_generate_speculative: bad token/pos/n_tokens");
+	ARGCHK(cfg->rows >= 2 && cfg->rows <= SPEC_MAX_ROWS, "yalm_generate_speculative: rows must be 2..4");
+	ARGCHK(cfg->ngram_min >= 1 && cfg->ngram_min <= cfg->ngram_max && cfg->ngram_max <= SPEC_MAX_NGRAM,
+	       "yalm_generate_speculative: need 1 <= ngram_min <= ngram_max <= 4");
+	ARGCHK(n_tokens <= d->tokens_cap, "yalm_generate_speculative: n_tokens exceeds the token buffer (65536)");
+	ARGCHK(n_context >= 0 && (n_context == 0 || context), "yalm_generate_speculative: bad context");
+	ARGCHK(n_context == 0 || context[n_context - 1] == token,
+	       "yalm_generate_speculative: the context must end with the token to feed");
+	ARGCHK(cfg->draft_stream_len >= 0 && (cfg->draft_stream || cfg->draft_stream_len == 0),
+	       "yalm_generate_speculative: bad draft_stream");
+	const int rows = cfg->rows, L = d->c.n_layers, n = n_tokens;
+	yalm_spec_stats s{};
+	s.launches_per_step = 4 + L * (4 + rows);
+	if (n == 0) {
+		if (stats)
+			*stats = s;
+		return YALM_OK;
+	}
+	TRY(rows_init(d));
+	hipStream_t st = d->stream;
+	int n_ctx = 1;
+	if (n_context == 0) {
+		HIPCHK(hipMemcpyAsync(d->spec_ctx, &token, sizeof(int), hipMemcpyHostToDevice, st));
+	} else {
+		n_ctx = std::min(n_context, d->tokens_cap);
+		HIPCHK(hipMemcpyAsync(d->spec_ctx, context + (n_context - n_ctx), sizeof(int) * n_ctx, hipMemcpyHostToDevice, st));
+	}
+	const int *stream = nullptr;
+	int stream_len = 0;
+	if (cfg->draft_stream) {
+		stream = d->spec_stream;
+		stream_len = std::min(cfg->draft_stream_len, std::min(n + rows, d->spec_stream_cap));
+		if (stream_len > 0)
+			HIPCHK(hipMemcpyAsync(d->spec_stream, cfg->draft_stream, sizeof(int) * stream_len, hipMemcpyHostToDevice, st));
+	}
+	HIPCHK(hipMemsetAsync(d->spec, 0, sizeof(SpecState), st));
+	set_step_kernel<<<1, 1, 0, st>>>(d->step, token, pos, 1);
+	HIPCHK(hipGetLastError());
+	int done = 0;
+	while (done < n) {
+		const long long p = (long long)pos + done;
+		// every step of a batch must keep its rows inside the window whatever the steps before it accepted
+		const int room = p + rows <= d->c.max_seq_len ? (int)((d->c.max_seq_len - p) / rows) : 0;
+		if (room == 0) { // the window's end (and past it): the plain greedy steps
+			TRY(replay_greedy(d, n - done, p));
+			s.plain_steps = n - done;
+			done = n;
+			break;
+		}
+		const int batch = std::min(std::min((n - done + rows - 1) / rows, room), 64);
+		for (int i = 0; i < batch; ++i) {
+			spec_draft_kernel<<<1, SPEC_DRAFT_THREADS, 0, st>>>(d->step, d->spec, d->spec_ctx, n_ctx, d->tokens,
+			                                                    d->tokens_cap, rows, cfg->ngram_max, cfg->ngram_min,
+			                                                    stream, stream_len, d->c.vocab_size);
+			HIPCHK(hipGetLastError());
+			TRY(enqueue_rows_forward(d, rows, 1));
+			spec_verify_kernel<<<1, 1024, 0, st>>>(d->rlogits, d->c.vocab_size, rows, d->step, d->spec, d->tokens,
+			                                       d->tokens_cap);
+			HIPCHK(hipGetLastError());
+		}
+		int produced = 0; // the batch's one round trip
+		HIPCHK(hipMemcpyAsync(&produced, &d->step->n_gen, sizeof(int), hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		TRY(awo_check(d));
+		if (produced <= done) {
+			set_err("yalm_generate_speculative: internal: a batch produced no token");
+			return YALM_ERR_HIP;
+		}
+		done = produced;
+	}
+	HIPCHK(hipMemcpyAsync(out_tokens, d->tokens, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+	SpecState sp;
+	HIPCHK(hipMemcpyAsync(&sp, d->spec, sizeof(sp), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	TRY(awo_check(d));
+	if (done > n) { // the last step accepted past the request: those drafts are not delivered
+		spec_fix_kernel<<<1, 1, 0, st>>>(d->step, out_tokens[n - 1], pos + n, n);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	d->host_pos = (long long)pos + n;
+	s.spec_steps = sp.steps;
+	s.accepted_drafts = sp.accepted - std::max(0, done - n);
+	if (stats)
+		*stats = s;
+	return YALM_OK;
 }
 
 extern "C" int yalm_device_step(yalm_decoder d, int *token, int *pos) {

@@ -2,7 +2,9 @@
 // /root/reference/src/main.cpp:17-428): completion, perplexity and passkey,
 // -d device switch (cpu | cuda | hip prefixes), -m -n -t -i -f -T -l.
 // -t 0 runs the greedy loop with the argmax on the device; -k / -p (top-k, top-p) select
-// device sampling for -t > 0: only the token comes back per step.
+// device sampling for -t > 0: only the token comes back per step. -s <rows> (with -t 0) runs
+// the greedy completion by speculative steps of 2..4 rows with n-gram drafts from the prompt
+// and the output so far: the same tokens, several per pass over the weights where drafts hit.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -42,6 +44,8 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -k <int>   top-k: sample among the k most likely tokens (0 - off); samples on the device\n");
 	fprintf(stderr, "  -p <float> top-p: sample from the smallest set of most likely tokens whose probability\n"
 	                "             reaches p, in (0, 1] (1 - off); samples on the device\n");
+	fprintf(stderr, "  -s <int>   speculative greedy decode with this many rows per step, 2..4 (0 - off, the default);\n"
+	                "             needs -t 0\n");
 	fprintf(stderr, "  Choose one:\n    -i <string> input prompt\n    -f <filepath> input file with prompt\n");
 	fprintf(stderr, "Passkey mode options:\n  -n <int>    number of junk lines to insert (default - 250)\n");
 	fprintf(stderr, "  -l <int>    passkey position (-1 - random)\n");
@@ -85,7 +89,7 @@ static std::vector<int> encode_prompt(const Tokenizer &tok, const std::string &p
 
 static void run_completion(const std::string &path, const std::string &device, const std::string &prompt,
                            int context, int num_steps, float temperature, bool device_sampling, int top_k,
-                           float top_p) {
+                           float top_p, int spec_rows) {
 	YALMData data;
 	if (data.from_file(path) != 0) {
 		fprintf(stderr, "error: cannot load %s\n", path.c_str());
@@ -129,6 +133,8 @@ static void run_completion(const std::string &path, const std::string &device, c
 		std::srand((unsigned)sampler_seed());
 	for (size_t pos = first; pos < encoding.size(); ++pos) {
 		const bool last = pos + 1 == encoding.size();
+		if (last && spec_rows > 0)
+			break; // the speculative loop below feeds the last prompt token itself
 		if (last && greedy)
 			next = model.forward_greedy(state, encoding[pos], (int)pos);
 		else if (last && sampled)
@@ -140,7 +146,24 @@ static void run_completion(const std::string &path, const std::string &device, c
 	}
 	const uint64_t end_hydrate = now_ms();
 	std::string ids;
-	for (int i = 0; i < num_steps || num_steps == -1; ++i) {
+	int spec_steps = 0, spec_accepted = 0, spec_plain = 0;
+	// -s: the tokens come in chunks of SPEC_CHUNK (one call each: no per-token round trip inside)
+	constexpr int SPEC_CHUNK = 16;
+	for (int done = 0, stop = 0; spec_rows > 0 && !stop && (done < num_steps || num_steps == -1);) {
+		const int chunk = num_steps == -1 ? SPEC_CHUNK : std::min(SPEC_CHUNK, num_steps - done);
+		int out[SPEC_CHUNK];
+		const int pos = (int)encoding.size() - 1;
+		model.generate_speculative(state, encoding.back(), pos, chunk, spec_rows, encoding.data(), (int)encoding.size(),
+		                           out, &spec_steps, &spec_accepted, &spec_plain);
+		for (int j = 0; j < chunk && !stop; ++j, ++done) {
+			std::cout << tokenizer.decode_one(encoding.back(), out[j]) << std::flush;
+			ids += std::to_string(out[j]) + " ";
+			read_bytes += model.config->active_bytes(encoding.size() - 1);
+			encoding.push_back(out[j]);
+			stop = out[j] == tokenizer.eos_id || out[j] == tokenizer.eot_id;
+		}
+	}
+	for (int i = 0; spec_rows == 0 && (i < num_steps || num_steps == -1); ++i) {
 		const int token = greedy || sampled ? next : sampler.sample(state, temperature);
 		std::cout << tokenizer.decode_one(encoding.back(), token) << std::flush;
 		ids += std::to_string(token) + " ";
@@ -166,6 +189,9 @@ static void run_completion(const std::string &path, const std::string &device, c
 	       "  bandwidth: %.5gGB/s\n  total: %.5gs\n\n",
 	       encoding.size(), encoding.size() / el, el / encoding.size(), (end_hydrate - start) / 1000.0,
 	       (double)read_bytes / 1e9 / el, el);
+	if (spec_rows > 0)
+		printf("  speculative: %d steps of %d rows, %d accepted drafts, %d plain steps\n\n", spec_steps, spec_rows,
+		       spec_accepted, spec_plain);
 }
 
 static void run_perplexity(const std::string &path, const std::string &device, const std::string &prompt,
@@ -305,7 +331,7 @@ static void run_passkey(const std::string &path, const std::string &device, int 
 
 int main(int argc, char *argv[]) {
 	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path;
-	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0;
+	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0, spec_rows = 0;
 	float temperature = 1.0f, top_p = 1.0f;
 	bool device_sampling = false;
 	if (argc < 2)
@@ -345,6 +371,7 @@ int main(int argc, char *argv[]) {
 			top_p = std::stof(v);
 			device_sampling = true;
 			break;
+		case 's': spec_rows = std::stoi(v); break;
 		case 'f': prompt_path = v; break;
 		case 'T': context = std::stoi(v); break;
 		case 'l': passkey_pos = std::stoi(v); break;
@@ -355,6 +382,9 @@ int main(int argc, char *argv[]) {
 		default: error_usage();
 		}
 	}
+	// -s: completion mode with -t 0 only
+	if (spec_rows != 0 && (spec_rows < 2 || spec_rows > 4 || temperature != 0.0f || mode != "completion"))
+		error_usage();
 	const int has_prompt = prompt.size() > 0, has_path = prompt_path.size() > 0;
 	if (mode == "completion" || mode == "perplexity") {
 		if (has_prompt + has_path != 1)
@@ -376,7 +406,8 @@ int main(int argc, char *argv[]) {
 	fprintf(stderr, "[yalm] Using checkpoint: %s\n", checkpoint.c_str());
 	try {
 		if (mode == "completion")
-			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p);
+			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p,
+			               spec_rows);
 		else if (mode == "passkey")
 			run_passkey(checkpoint, device, context, n_junk, passkey_pos);
 		else

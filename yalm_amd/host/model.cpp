@@ -329,6 +329,20 @@ int Model::forward_greedy(InferenceState &s, int token, int pos) {
 	return next;
 }
 
+void Model::generate_speculative(InferenceState &s, int token, int pos, int n, int rows, const int *context,
+                                 int n_context, int *out, int *steps, int *accepted, int *plain) {
+	ensure_decoder(s);
+	const yalm_spec cfg{rows, 3, 1, nullptr, 0};
+	yalm_spec_stats st{};
+	check(yalm_generate_speculative(s._decoder, token, pos, n, &cfg, context, n_context, out, &st), "speculative steps");
+	if (steps)
+		*steps += st.spec_steps;
+	if (accepted)
+		*accepted += st.accepted_drafts;
+	if (plain)
+		*plain += st.plain_steps;
+}
+
 int Model::forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u) {
 	ensure_decoder(s);
 	const yalm_sampling sp{temperature, top_k, top_p};

@@ -128,6 +128,12 @@ struct Model {
 	// top-k (0 = off) / top-p (1 = off) sampling of the logits with the uniform u in [0, 1];
 	// only the token comes back. Returns the next token.
 	int forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u);
+	// n greedy tokens by speculative steps of `rows` rows (yalm_generate_speculative, n-gram
+	// drafts of 3 down to 1 tokens from `context`, which ends with `token`): the tokens of
+	// forward_greedy, several per pass over the weights where the drafts hit. steps / accepted /
+	// plain (may be null) are incremented by the call's counts.
+	void generate_speculative(InferenceState &s, int token, int pos, int n, int rows, const int *context, int n_context,
+	                          int *out, int *steps, int *accepted, int *plain);
 	// Batched MFMA prefill of tokens[0..n) at positions pos0.. (yalm_prefill):
 	// fills the KV cache; logprobs (may be null) gets log p(tokens[i+1]) per
 	// position; split: the split-operand precision form (yalm_set_prefill_precision).

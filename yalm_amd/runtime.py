@@ -68,6 +68,20 @@ class Sampling(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float)]
 
 
+class Spec(ctypes.Structure):
+    """yalm_spec: rows 2..4, 1 <= ngram_min <= ngram_max <= 4, the draft_stream hook."""
+
+    _fields_ = [("rows", c_int), ("ngram_max", c_int), ("ngram_min", c_int), ("draft_stream", c_void_p),
+                ("draft_stream_len", c_int)]
+
+
+class SpecStats(ctypes.Structure):
+    """yalm_spec_stats."""
+
+    _fields_ = [("spec_steps", c_int), ("accepted_drafts", c_int), ("plain_steps", c_int),
+                ("launches_per_step", c_int)]
+
+
 class BlockWeights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("rms_att", "rms_ffn", "wq", "wk", "wv", "wo", "w1", "w2", "w3",
                                         "key_cache", "value_cache")]
@@ -148,6 +162,10 @@ _sig("yalm_attn_prefill", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int,
 _sig("yalm_set_prefill_forms", c_int, [c_void_p, ctypes.c_char_p])
 _sig("yalm_graph_kernels", c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
 _sig("yalm_attn_wo_plan", c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
+_sig("yalm_forward_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p])
+_sig("yalm_generate_speculative", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Spec), c_void_p, c_int, c_void_p,
+                                           ctypes.POINTER(SpecStats)])
+_sig("yalm_spec_draft", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -164,6 +182,7 @@ EXPORTED = [
     "yalm_prefill_routing", "yalm_moe_gemm_f16", "yalm_moe_ffn_rows",
     "yalm_generate_sampled", "yalm_sample",
     "yalm_row_bytes", "yalm_synth_q4",
+    "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -235,6 +254,15 @@ def sample(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float 
     q = np.zeros(max(lg.size, 1), np.uint64)
     check(lib.yalm_sample(_ptr(lg), lg.size, ctypes.byref(s), _ptr(u), u.size, _ptr(tokens), _ptr(kept), _ptr(q)))
     return tokens[:u.size], kept[:u.size], q[:lg.size]
+
+
+def spec_draft(history, rows: int, ngram_max: int = 3, ngram_min: int = 1) -> list:
+    """The n-gram drafter of the speculative loop on a given history (yalm_spec_draft: one launch
+    of its kernel): the rows - 1 drafts, -1 for none."""
+    h = np.ascontiguousarray(history, dtype=np.int32).reshape(-1)
+    out = np.full(4, -1, np.int32)
+    check(lib.yalm_spec_draft(_ptr(h) if h.size else None, h.size, rows, ngram_max, ngram_min, _ptr(out)))
+    return out[:rows - 1].tolist()
 
 
 def ffn(x, w1, w2, w3, act: int, dtype: int) -> np.ndarray:
@@ -616,6 +644,32 @@ class Decoder:
         out = np.zeros(max(n, 1), np.int32)
         check(lib.yalm_generate_greedy(self.h, token, pos, n, out.ctypes.data))
         return out[:n].tolist()
+
+    def forward_rows(self, tokens, pos: int, logits: bool = True):
+        """len(tokens) <= 4 tokens at positions pos.. in one pass over the weights
+        (yalm_forward_rows); returns their logits (T, vocab) or None."""
+        tok = np.ascontiguousarray(tokens, dtype=np.int32).reshape(-1)
+        out = np.empty((tok.size, self.cfg.vocab_size), np.float32) if logits else None
+        check(lib.yalm_forward_rows(self.h, _ptr(tok) if tok.size else None, tok.size, pos,
+                                    _ptr(out) if logits else None))
+        return out
+
+    def generate_speculative(self, token: int, pos: int, n: int, rows: int = 4, ngram_max: int = 3,
+                             ngram_min: int = 1, context=None, draft_stream=None):
+        """n greedy tokens by speculative steps of `rows` rows (yalm_generate_speculative):
+        (tokens, stats dict). context: the tokens before and including `token` (the n-gram
+        drafter's history); draft_stream: the test / benchmark hook replacing the drafter."""
+        ctx = np.ascontiguousarray(context if context is not None else [], dtype=np.int32).reshape(-1)
+        ds = None if draft_stream is None else np.ascontiguousarray(draft_stream, dtype=np.int32).reshape(-1)
+        keep = np.zeros(1, np.int32)  # a non-NULL pointer for an empty stream
+        spec = Spec(rows, ngram_max, ngram_min,
+                    None if ds is None else (_ptr(ds) if ds.size else _ptr(keep)), 0 if ds is None else ds.size)
+        st = SpecStats()
+        out = np.zeros(max(n, 1), np.int32)
+        check(lib.yalm_generate_speculative(self.h, token, pos, n, ctypes.byref(spec), _ptr(ctx) if ctx.size else None,
+                                            ctx.size, out.ctypes.data, ctypes.byref(st)))
+        return out[:n].tolist(), {"spec_steps": st.spec_steps, "accepted_drafts": st.accepted_drafts,
+                                  "plain_steps": st.plain_steps, "launches_per_step": st.launches_per_step}
 
     def generate_sampled(self, token: int, pos: int, n: int, temperature: float, top_k: int = 0,
                          top_p: float = 1.0, uniforms=None, seed: int = 0) -> list:
