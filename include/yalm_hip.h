@@ -269,6 +269,42 @@ int yalm_attn_wo_plan(const yalm_config *config, int slots, int *splits, int *gr
 int yalm_attn_wo_trace(yalm_decoder d, unsigned long long *host, size_t count, int *workgroups,
                        int *attention_workgroups);
 
+/* ---------------- model-family forms: scaled RoPE (Llama-3.1 / 3.2), q / k / v bias (Qwen2) ----------------
+ * Both are set on a created decoder and are off by default: a decoder on which neither is
+ * called launches exactly the kernels it launched before these entry points existed. The
+ * reference reads neither form.
+ *
+ * RoPE scaling: the decoder's frequency table (head_dim / 2 pair frequencies; the decode
+ * step's cos / sin table, the attention sinks' one-position rotation and the batched
+ * prefill's table are all built from it) is recomputed on the host and uploaded after a
+ * stream sync. type 1 = "llama3": per pair frequency f (the unscaled table's f32 value),
+ * with the wavelength w = 2 pi / f:
+ *   w < original_max_position / high_freq_factor      f stays
+ *   w > original_max_position / low_freq_factor       f / factor
+ *   otherwise  s = (original_max_position / w - low_freq_factor) / (high_freq_factor - low_freq_factor),
+ *              (1 - s) f / factor + s f
+ * in double, rounded once to f32. type 0 restores the unscaled table bit for bit. Every
+ * decoder kind takes it. YALM_ERR_ARG: factor < 1, high_freq_factor <= low_freq_factor,
+ * low_freq_factor <= 0, original_max_position <= 0, an unknown type. */
+typedef struct yalm_rope_scaling {
+	int type; /* 0 none, 1 llama3 */
+	float factor, low_freq_factor, high_freq_factor;
+	int original_max_position;
+} yalm_rope_scaling;
+int yalm_decoder_set_rope_scaling(yalm_decoder d, const yalm_rope_scaling *s);
+/* The frequency table in use: head_dim / 2 floats to `host`. */
+int yalm_decoder_get_inv_freq(yalm_decoder d, float *host);
+/* q / k / v bias: v = clip(W . rmsnorm(x) + b), then RoPE (q, k), the f16 cache write (k, v)
+ * and the q store as without a bias. bq, bk, bv: HOST arrays of n_layers DEVICE pointers to
+ * f32 vectors, 8-byte aligned and caller-owned for the decoder's lifetime: bq[l] of
+ * n_heads * head_dim, bk[l] / bv[l] of n_kv_heads * head_dim elements, in the row order of
+ * wq / wk / wv. All three NULL removes the bias. Drops the captured graphs. Dense one-GPU
+ * decoders of every weight dtype: decode, yalm_forward_rows / yalm_generate_speculative
+ * (not q4, as without a bias) and yalm_prefill; a tensor-parallel or mixture-of-experts
+ * decoder returns YALM_ERR_UNSUPPORTED. */
+int yalm_decoder_set_qkv_bias(yalm_decoder d, const float *const *bq, const float *const *bk,
+                              const float *const *bv);
+
 /* ---------------- mixture of experts (Mixtral), one GPU ----------------
  * The reference runs MoE on the CPU only (infer.cpp:100-132, 347-384; its GPU path
  * asserts, infer.cu:865-867). Per layer: a router launch (rmsnorm(x) . moegate^T, then

@@ -12,6 +12,12 @@ matrix, the embedding included, is quantised from its fp16 conversion and stored
 tensor [rows, row_bytes(n)]; dense models only. Mixtral checkpoints (convert.py:54-56, 78-80, 188-193): the
 router gate becomes ``moegate``, each layer's experts are stacked along a new
 leading axis, and n_experts / n_experts_active go into the metadata.
+Two forms the reference's converter and engine do not read (such a file is this engine's
+alone, as q4 is): Qwen2 / Qwen2.5 (``Qwen2ForCausalLM``: the Llama block plus a bias on q, k
+and v, written F32 as ``attn.{wq,wk,wv}.bias`` with the q / k rows permuted as their weights'
+rows are; metadata ``qkv_bias``), and Llama-3.1 / 3.2 ``rope_scaling`` of type ``llama3``
+(metadata ``rope_scaling_type`` / ``rope_scaling_factor`` / ``rope_low_freq_factor`` /
+``rope_high_freq_factor`` / ``rope_original_max_position``). Any other scaling type raises.
 
 Usage: python -m yalm_amd.convert [--dtype fp16] out.yalm hf_dir/
 """
@@ -27,7 +33,7 @@ import numpy as np
 from . import models as M
 from .yalmfile import read_yalm, write_yalm
 
-SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM"]
+SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM", "Qwen2ForCausalLM"]
 SUPPORTED_DTYPES = ["fp32", "fp16", "fp8", "q4"]
 
 
@@ -40,8 +46,13 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
     if arch == "MixtralForCausalLM" and dtype == "q4":
         raise ValueError("q4 has no mixture-of-experts form")
     head_dim = config.get("head_dim", config["hidden_size"] // config["num_attention_heads"])
+    # (Llama's attention_bias also biases o_proj; Qwen2 has no such flag: its q / k / v bias is the architecture's)
     if config.get("attention_bias", False) or config.get("mlp_bias", False):
         raise ValueError("attention/mlp bias is not supported")
+    qwen2 = arch == "Qwen2ForCausalLM"
+    if qwen2 and config.get("use_sliding_window", False):
+        raise ValueError("Qwen2 use_sliding_window is not supported")
+    rope_scaling = rope_scaling_from_config(config)
     if config["hidden_act"] not in ("gelu", "silu"):
         raise ValueError(f"unsupported hidden_act {config['hidden_act']}")
     md = {
@@ -66,8 +77,28 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
     if arch == "MixtralForCausalLM":
         md["n_experts"] = config["num_local_experts"]
         md["n_experts_active"] = config["num_experts_per_tok"]
+    if qwen2:
+        md["qkv_bias"] = 1
+    if rope_scaling is not None:
+        md.update(M.rope_scaling_metadata(rope_scaling))
     # str() of the python value, as convert.py:63-80 does (floats print as 10000.0, 1e-05)
     return {k: str(v) for k, v in md.items()}
+
+
+def rope_scaling_from_config(config: dict):
+    """HF ``rope_scaling``: None / type "default" -> None; "llama3" -> the ModelConfig tuple;
+    anything else (yarn, linear, dynamic, ...) raises instead of converting a model whose
+    logits would not be the checkpoint's."""
+    rs = config.get("rope_scaling")
+    if rs is None:
+        return None
+    kind = rs.get("rope_type") or rs.get("type")
+    if kind in (None, "default"):
+        return None
+    if kind != "llama3":
+        raise ValueError(f"rope_scaling type {kind!r} is not supported (only 'llama3')")
+    return M.check_rope_scaling(("llama3", rs["factor"], rs["low_freq_factor"], rs["high_freq_factor"],
+                                 rs["original_max_position_embeddings"]))
 
 
 def gpt2_bytes_to_unicode() -> dict:
@@ -192,7 +223,12 @@ def convert(hf_dir: str, out_path: str, dtype: str = "fp16") -> None:
             src_key = f"__perm_{key}"
             src[src_key] = _F32View(a)
             put(q + f"attn.{key}.weight", conv(src_key))
+            if md.get("qkv_bias") == "1":  # the bias rows move with their weight rows
+                bias = _to_f32(src[p + f"self_attn.{hf}.bias"]).reshape(-1, 1)
+                put(q + f"attn.{key}.bias", (np.ascontiguousarray(permute_reverse(bias, heads, rot)[:, 0]), "F32"))
         put(q + "attn.wv.weight", conv(p + "self_attn.v_proj.weight"))
+        if md.get("qkv_bias") == "1":
+            put(q + "attn.wv.bias", (_to_f32(src[p + "self_attn.v_proj.bias"]).reshape(-1), "F32"))
         put(q + "attn.wo.weight", conv(p + "self_attn.o_proj.weight"))
         put(q + "mlp.norm.weight", (_to_f32(src[p + "post_attention_layernorm.weight"]), "F32"))
         if md["arch"] == "MixtralForCausalLM":

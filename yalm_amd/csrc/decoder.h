@@ -191,6 +191,11 @@ struct yalm_decoder_s {
 	int *spec_ctx = nullptr;           // [tokens_cap] the caller's context (its last tokens_cap tokens)
 	int *spec_stream = nullptr;        // the draft_stream hook's tokens
 	int spec_stream_cap = 0;
+	// model-family forms set after creation: the RoPE frequency rule behind inv_freq
+	// (yalm_decoder_set_rope_scaling; type 0 = the plain table) and the q / k / v bias
+	// (yalm_decoder_set_qkv_bias: [n_layers] device pointers each, empty = no bias)
+	yalm_rope_scaling rope_scaling{};
+	std::vector<const float *> bq, bk, bv;
 	std::vector<const void *> moegate; // [n_layers] router weights (n_experts, dim)
 	int *moe_sel = nullptr;            // [n_layers][moe_K] the routing of the most recent forward
 	float *moe_wts = nullptr;          // [n_layers][moe_K]

@@ -275,6 +275,28 @@ struct PQKV {
 	__device__ __forceinline__ void finish_all(int g, const float *acc) const { finish(g, acc, 0); }
 };
 
+// PQKV with a bias on q, k and v (Qwen2): v = clip(W . xb + b), then PQKV's epilogue as it is.
+// bq (q_dim), bk / bv (kv_dim) f32. The pair's two bias values are one 8-byte load in the epilogue
+// of the one thread that finishes the group (lane 0 / the group's thread of gemv_rb_kernel): after
+// the weight stream, so the static vmcnt order of the stream (gemv_rb_kernel) is untouched, and
+// an L2 hit beside the rope table and kv_pos loads the epilogue already waits for.
+template <class WT>
+struct PQKVB : PQKV<WT> {
+	const float *bq, *bk, *bv;
+	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
+		if (lane != 0)
+			return;
+		const int vr = 2 * g; // even, and q_dim / kv_dim are even: the pair lies in one of q, k, v
+		const float *b = vr < this->q_dim               ? bq + vr
+		                 : vr < this->q_dim + this->kv_dim ? bk + (vr - this->q_dim)
+		                                                   : bv + (vr - this->q_dim - this->kv_dim);
+		const float2_t bb = *(const float2_t *)b;
+		const float a[2] = {acc[0] + bb[0], acc[1] + bb[1]};
+		PQKV<WT>::finish(g, a, 0);
+	}
+	__device__ __forceinline__ void finish_all(int g, const float *acc) const { finish(g, acc, 0); }
+};
+
 template <class WT, int ACT>
 struct PGlu {
 	static constexpr int R = 2;

@@ -94,6 +94,26 @@ struct RQKV {
 	}
 };
 
+// RQKV over a biased model: row t's epilogue is PQKVB::finish (the bias, then PQKV::finish).
+template <class WT>
+struct RQKVB {
+	static constexpr int R = 2;
+	PQKVB<WT> base;
+	int n, n_groups, q_stride;
+	__device__ __forceinline__ const char *row(int g, int r) const { return base.row(g, r); }
+	template <int T>
+	__device__ __forceinline__ void finish(int g, const float (&acc)[R][T]) const {
+#pragma unroll
+		for (int t = 0; t < T; ++t) {
+			PQKVB<WT> b = base;
+			b.step = base.step + t;
+			b.q_out = base.q_out + (size_t)t * q_stride;
+			const float a[2] = {acc[0][t], acc[1][t]};
+			b.finish(g, a, 0);
+		}
+	}
+};
+
 template <class WT, int ACT>
 struct RGlu {
 	static constexpr int R = 2;

@@ -731,43 +731,53 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			qkv.end[0] = q_dim;
 			qkv.end[1] = q_dim + kv_dim;
 			qkv.end[2] = q_dim + 2 * kv_dim;
-			pf::E16QKV e;
-			e.q = b.Q;
-			e.kc = w.key_cache;
-			e.vc = w.value_cache;
-			e.rope = b.rope;
-			e.M = T;
-			e.q_dim = q_dim;
-			e.kv_dim = kv_dim;
-			e.head_dim = c.head_dim;
-			e.pos0 = pos0;
-			e.clip = c.qkv_clip;
-			e.range = rg + RG_Q;
-			// QKV + clip + RoPE as two GEMMs: q (K = dim over hi) and k | v from column
-			// q_dim (K = 2 dim over hi | lo, the B rows wrapping at dim)
-			if (small) {
-				const pf::BRowsPlain bm{qkv};
-				const int np = q_dim + 2 * kv_dim;
-				TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, c.dim, c.dim, bm, q_dim, ks_qkv, 0, np, b.skp, st));
-				TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, bm, 2 * kv_dim, 2 * ks_qkv, q_dim, np, b.skp,
-				                  st));
-				TRY(launch_skinny_reduce<false>(b.skp, ks_qkv, 2 * ks_qkv, q_dim, T, np, e, st));
-			} else {
-				if (split) { // q | k | v all over [hi | lo], Q stored [hi | lo]
-					pf::E16QKVt<true> es;
+			// every QKV form over the epilogue with or without the q / k / v bias (Qwen2,
+			// yalm_decoder_set_qkv_bias): a compile-time flag, so an unbiased model runs the
+			// instantiations it always ran
+			auto qkv_gemms = [&](auto biased) -> int {
+				constexpr bool B = decltype(biased)::value;
+				pf::E16QKVt<false, B> e;
+				e.q = b.Q;
+				e.kc = w.key_cache;
+				e.vc = w.value_cache;
+				e.rope = b.rope;
+				e.M = T;
+				e.q_dim = q_dim;
+				e.kv_dim = kv_dim;
+				e.head_dim = c.head_dim;
+				e.pos0 = pos0;
+				e.clip = c.qkv_clip;
+				e.range = rg + RG_Q;
+				if constexpr (B)
+					e.bq = d->bq[l], e.bk = d->bk[l], e.bv = d->bv[l];
+				// QKV + clip + RoPE as two GEMMs: q (K = dim over hi) and k | v from column
+				// q_dim (K = 2 dim over hi | lo, the B rows wrapping at dim)
+				if (small) {
+					const pf::BRowsPlain bm{qkv};
+					const int np = q_dim + 2 * kv_dim;
+					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, c.dim, c.dim, bm, q_dim, ks_qkv, 0, np, b.skp, st));
+					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, bm, 2 * kv_dim, 2 * ks_qkv, q_dim, np, b.skp,
+					                  st));
+					TRY(launch_skinny_reduce<false>(b.skp, ks_qkv, 2 * ks_qkv, q_dim, T, np, e, st));
+				} else if (split) { // q | k | v all over [hi | lo], Q stored [hi | lo]
+					pf::E16QKVt<true, B> es;
 					es.q = e.q, es.kc = e.kc, es.vc = e.vc, es.rope = e.rope, es.M = e.M, es.q_dim = e.q_dim;
 					es.kv_dim = e.kv_dim, es.head_dim = e.head_dim, es.pos0 = e.pos0, es.clip = e.clip;
 					es.range = e.range, es.q_lo = q_dim;
+					if constexpr (B)
+						es.bq = e.bq, es.bk = e.bk, es.bv = e.bv;
 					TRY(launch_plain(f, bn_qkv_all, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, q_dim + 2 * kv_dim, es, st));
 				} else if (qkv1) { // one launch: the k | v tiles (K = 2 dim) first, then the q tiles (K = dim)
-					TRY((launch_g8p<pf::E16QKV, pf::BRowsPlain, 2, 2>(f, b.Xn, 2 * c.dim, T, c.dim, c.dim,
-					                                                   pf::BRowsPlain{qkv}, q_dim + 2 * kv_dim, e, st,
-					                                                   0, q_dim, 2 * c.dim)));
+					TRY((launch_g8p<pf::E16QKVt<false, B>, pf::BRowsPlain, 2, 2>(f, b.Xn, 2 * c.dim, T, c.dim, c.dim,
+					                                                              pf::BRowsPlain{qkv}, q_dim + 2 * kv_dim, e,
+					                                                              st, 0, q_dim, 2 * c.dim)));
 				} else {
 					TRY(launch_plain(f, bn_q, b.Xn, 2 * c.dim, T, c.dim, c.dim, qkv, q_dim, e, st));
 					TRY(launch_plain(f, bn_kv, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, 2 * kv_dim, e, st, q_dim));
 				}
-			}
+				return YALM_OK;
+			};
+			TRY(d->bq.empty() ? qkv_gemms(std::false_type{}) : qkv_gemms(std::true_type{}));
 		}
 		TRY(launch_attn_prefill(b.Q, w.key_cache, w.value_cache, T, pos0, c.n_heads, c.n_kv_heads, c.head_dim, b.O,
 								st, split));

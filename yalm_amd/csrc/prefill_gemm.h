@@ -31,6 +31,8 @@
 // C layout (column = lane & 15, row = 4 (lane >> 4) + reg).
 #pragma once
 
+#include <type_traits>
+
 #include "prefill.h"
 
 namespace pf {
@@ -198,8 +200,17 @@ struct E16Glu {
 // region / row branches hipcc waited for each table load separately (the epilogue cost
 // 71 of 172 us at Llama-3B T 4096, tools/gemm_epi_bench.hip).
 // SPLITQ (the split-operand form): Q rows [hi | lo], lo q_lo (= q_dim) columns after hi.
-template <bool SPLITQ = false>
-struct E16QKVt {
+// BIAS (Qwen2, yalm_decoder_set_qkv_bias): acc + b ahead of the clip, b the f32 bias of the
+// lane's column. Under the same rule as the table loads: one load per lane and 16-column block,
+// unconditional, issued with the block's first batch of table loads and ahead of any use. The
+// Q range guard sees the biased value. The pointers live in a base that is empty without the
+// flag, so the unbiased epilogue's arguments and code are what they were.
+struct QKVBias {
+	const float *bq, *bk, *bv; // q_dim, kv_dim, kv_dim
+};
+struct QKVNoBias {};
+template <bool SPLITQ = false, bool BIAS = false>
+struct E16QKVt : std::conditional_t<BIAS, QKVBias, QKVNoBias> {
 	static constexpr bool NEEDS_LDS = false;
 	float *red = nullptr;
 	uint16_t *q;
@@ -225,6 +236,9 @@ struct E16QKVt {
 			const bool rot = region != 2;
 			uint16_t *const dst = (region == 0 ? q : (region == 1 ? kc : vc)) + nn;
 			const int ld = region == 0 ? (SPLITQ ? 2 * q_dim : q_dim) : kv_dim, roff = region == 0 ? 0 : pos0;
+			[[maybe_unused]] float bias = 0.0f;
+			if constexpr (BIAS)
+				bias = (region == 0 ? this->bq : (region == 1 ? this->bk : this->bv))[nn];
 			constexpr int IB = FI < 4 ? FI : 4; // row fragments per batch of table loads
 #pragma unroll
 			for (int i0 = 0; i0 < FI; i0 += IB) {
@@ -241,6 +255,8 @@ struct E16QKVt {
 #pragma unroll
 					for (int r = 0; r < 4; ++r) {
 						float v = acc[i0 + i][j][r];
+						if constexpr (BIAS)
+							v += bias;
 						v = v < -clip ? -clip : (v > clip ? clip : v);
 						const float p = dpp<0xB1>(v); // partner column (n ^ 1)
 						const float ro = odd ? p * cs[i][r][1] + v * cs[i][r][0] : v * cs[i][r][0] - p * cs[i][r][1];

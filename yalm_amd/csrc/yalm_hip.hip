@@ -217,6 +217,10 @@ template <class WT>
 struct RowsMode<PQKV<WT>> {
 	static constexpr bool value = true;
 };
+template <class WT>
+struct RowsMode<PQKVB<WT>> {
+	static constexpr bool value = true;
+};
 // the expert policies (moe.h) stream as their dense counterparts do
 template <class WT, int ACT>
 struct RowsMode<PMoeGlu<WT, ACT>> {
@@ -884,6 +888,39 @@ static MoeArgs moe_layer_args(const yalm_decoder_s *d, int l) {
 	               d->moe_sel + (size_t)l * d->moe_K, d->moe_wts + (size_t)l * d->moe_K, d->hb};
 }
 
+// The QKV policy of one layer's weights on the decoder's single-row state (the multi-row verify
+// step points step / q_out at its row states).
+template <class WT>
+static PQKV<WT> make_pqkv(const yalm_decoder_s *d, const yalm_block_weights &w) {
+	const yalm_config &c = d->c;
+	PQKV<WT> p;
+	p.wq = (const char *)w.wq;
+	p.wk = (const char *)w.wk;
+	p.wv = (const char *)w.wv;
+	p.n = c.dim;
+	p.q_dim = c.n_heads * c.head_dim;
+	p.kv_dim = c.n_kv_heads * c.head_dim;
+	p.head_dim = c.head_dim;
+	p.n_groups = (p.q_dim + 2 * p.kv_dim) / 2;
+	p.qkv_clip = c.qkv_clip;
+	p.inv_freq = d->inv_freq;
+	p.step = d->step;
+	p.q_out = d->q;
+	p.kcache = w.key_cache;
+	p.vcache = w.value_cache;
+	return p;
+}
+// ... with layer l's q / k / v bias (yalm_decoder_set_qkv_bias)
+template <class WT>
+static PQKVB<WT> make_pqkvb(const yalm_decoder_s *d, int l) {
+	PQKVB<WT> p;
+	static_cast<PQKV<WT> &>(p) = make_pqkv<WT>(d, d->b[l]);
+	p.bq = d->bq[l];
+	p.bk = d->bk[l];
+	p.bv = d->bv[l];
+	return p;
+}
+
 // One layer. IPC tensor parallelism (tp_exchange.h): the Wo partial is exchange ex0 (the GLU
 // consumes it), the W2 partial exchange ex0 + 1 (push_w2; the next QKV or the logits GEMV
 // consumes it); x_exchanged: the layer's input x is exchange ex0 - 1 (the QKV GEMV consumes
@@ -893,24 +930,12 @@ static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, 
 	const yalm_config &c = d->c;
 	const yalm_block_weights &w = d->b[l];
 	hipStream_t st = d->stream;
-	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
+	const int q_dim = c.n_heads * c.head_dim;
 	const TpX none{};
-	{
-		PQKV<WT> p;
-		p.wq = (const char *)w.wq;
-		p.wk = (const char *)w.wk;
-		p.wv = (const char *)w.wv;
-		p.n = c.dim;
-		p.q_dim = q_dim;
-		p.kv_dim = kv_dim;
-		p.head_dim = c.head_dim;
-		p.n_groups = (q_dim + 2 * kv_dim) / 2;
-		p.qkv_clip = c.qkv_clip;
-		p.inv_freq = d->inv_freq;
-		p.step = d->step;
-		p.q_out = d->q;
-		p.kcache = w.key_cache;
-		p.vcache = w.value_cache;
+	if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias; never tensor parallel)
+		TRY((launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV, none)));
+	} else {
+		const PQKV<WT> p = make_pqkv<WT>(d, w);
 		TRY((launch_gemv_d<WT, PQKV<WT>, true>(d, p, d->x, w.rms_att, c.norm_eps, GK_QKV,
 		                                         d->ipc && x_exchanged ? tpx_consume(d, ex0 - 1, c.dim) : none)));
 	}
@@ -1109,6 +1134,87 @@ static int validate_config(const yalm_config *c) {
 	return YALM_OK;
 }
 
+// The RoPE frequency table (head_dim / 2). The plain table is create_decoder's powf form (see
+// there); rs.type 1 (Llama-3.1 / 3.2 "llama3") rescales each pair frequency f by its wavelength
+// w = 2 pi / f against the original context `orig`: w < orig / high keeps f, w > orig / low
+// gives f / factor, between them s = (orig / w - low) / (high - low) blends
+// (1 - s) f / factor + s f. In double from the f32 f, rounded once to f32.
+static std::vector<float> rope_inv_freq(const yalm_config &c, const yalm_rope_scaling &rs) {
+	std::vector<float> inv(c.head_dim / 2);
+	const float rinv = 1.0f / (float)c.rotary_dim;
+	for (int j = 0; j < c.head_dim; j += 2)
+		inv[j / 2] = j >= c.rotary_dim ? 0.f : powf(c.rope_theta, -((float)j * rinv));
+	if (rs.type == 1) {
+		const double orig = (double)rs.original_max_position, lo = (double)rs.low_freq_factor,
+		             hi = (double)rs.high_freq_factor, factor = (double)rs.factor;
+		for (float &fv : inv) {
+			const double f = (double)fv;
+			if (f == 0.0)
+				continue;
+			const double w = 2.0 * M_PI / f;
+			if (w < orig / hi)
+				continue;
+			if (w > orig / lo) {
+				fv = (float)(f / factor);
+			} else {
+				const double s = (orig / w - lo) / (hi - lo);
+				fv = (float)((1.0 - s) * f / factor + s * f);
+			}
+		}
+	}
+	return inv;
+}
+
+extern "C" int yalm_decoder_set_rope_scaling(yalm_decoder d, const yalm_rope_scaling *s) {
+	ARGCHK(d && s, "yalm_decoder_set_rope_scaling: null argument");
+	ARGCHK(s->type == 0 || s->type == 1, "yalm_decoder_set_rope_scaling: unknown type (0 none, 1 llama3)");
+	ARGCHK(s->type == 0 || (s->factor >= 1.0f && s->high_freq_factor > s->low_freq_factor &&
+	                        s->low_freq_factor > 0.0f && s->original_max_position > 0),
+	       "yalm_decoder_set_rope_scaling: need factor >= 1, high_freq_factor > low_freq_factor > 0 and "
+	       "original_max_position > 0");
+	yalm_rope_scaling rs{};
+	if (s->type)
+		rs = *s;
+	const std::vector<float> inv = rope_inv_freq(d->c, rs);
+	HIPCHK(hipStreamSynchronize(d->stream)); // no forward in flight reads the old table
+	HIPCHK(hipMemcpy(d->inv_freq, inv.data(), sizeof(float) * inv.size(), hipMemcpyHostToDevice));
+	d->rope_scaling = rs;
+	return YALM_OK;
+}
+
+extern "C" int yalm_decoder_get_inv_freq(yalm_decoder d, float *host) {
+	ARGCHK(d && host, "yalm_decoder_get_inv_freq: null argument");
+	HIPCHK(hipStreamSynchronize(d->stream));
+	HIPCHK(hipMemcpy(host, d->inv_freq, sizeof(float) * (d->c.head_dim / 2), hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+extern "C" int yalm_decoder_set_qkv_bias(yalm_decoder d, const float *const *bq, const float *const *bk,
+                                         const float *const *bv) {
+	ARGCHK(d, "yalm_decoder_set_qkv_bias: null decoder");
+	if (d->tp_size > 1 || d->comm || d->ipc || d->moe_E > 0) {
+		set_err("yalm_decoder_set_qkv_bias: a q / k / v bias runs on dense one-GPU decoders only (no tensor-parallel or "
+		        "mixture-of-experts form)");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const bool none = !bq && !bk && !bv;
+	ARGCHK(none || (bq && bk && bv), "yalm_decoder_set_qkv_bias: bias arrays for q, k and v, or all three NULL");
+	const int L = d->c.n_layers;
+	if (!none)
+		for (int l = 0; l < L; ++l) // (the epilogue reads a RoPE pair's two values as one 8-byte load)
+			ARGCHK(bq[l] && bk[l] && bv[l] && (uintptr_t)bq[l] % 8 == 0 && (uintptr_t)bk[l] % 8 == 0 &&
+			           (uintptr_t)bv[l] % 8 == 0,
+			       "yalm_decoder_set_qkv_bias: a layer's bias pointer is null or not 8-byte aligned");
+	HIPCHK(hipStreamSynchronize(d->stream));
+	drop_graphs(d); // captured graphs bake the QKV launches without (or with the old) bias pointers
+	if (none) {
+		d->bq.clear(), d->bk.clear(), d->bv.clear();
+	} else {
+		d->bq.assign(bq, bq + L), d->bk.assign(bk, bk + L), d->bv.assign(bv, bv + L);
+	}
+	return YALM_OK;
+}
+
 static void destroy_decoder(yalm_decoder_s *d) {
 	drop_graphs(d);
 	if (d->comm)
@@ -1229,10 +1335,7 @@ static int create_decoder(const yalm_config *config, const yalm_model_weights *w
 	// glibc powf call; the division folded into the exponent): a freq one ulp away moves
 	// the angle pos * freq by pos ulps, 2e-4 rad at pos 4095 -- tests/test_gpu_ref_glue.py
 	// measured 60 f16 ulps on a K row against the reference's own rope before this form.
-	std::vector<float> inv(c.head_dim / 2);
-	const float rinv = 1.0f / (float)c.rotary_dim;
-	for (int j = 0; j < c.head_dim; j += 2)
-		inv[j / 2] = j >= c.rotary_dim ? 0.f : powf(c.rope_theta, -((float)j * rinv));
+	const std::vector<float> inv = rope_inv_freq(c, d->rope_scaling);
 	if (hipMemcpy(d->inv_freq, inv.data(), sizeof(float) * inv.size(), hipMemcpyHostToDevice) != hipSuccess) {
 		set_err("inv_freq upload failed");
 		return fail(YALM_ERR_HIP);
@@ -1685,29 +1788,27 @@ static int enqueue_rows_forward_t(yalm_decoder_s *d, int T, int from_step) {
 	} else {
 		const yalm_config &c = d->c;
 		hipStream_t st = d->stream;
-		const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
+		const int q_dim = c.n_heads * c.head_dim;
 		static_assert(offsetof(SpecState, tok) == 0, "SpecState begins with the row tokens");
 		rows_begin_kernel<WT><<<1, 256, 0, st>>>(d->step, d->rstep, (const int *)d->spec, T, from_step, d->emb, c.dim,
 		                                          d->rx, d->inv_freq, c.head_dim / 2);
 		HIPCHK(hipGetLastError());
 		for (int l = 0; l < c.n_layers; ++l) {
 			const yalm_block_weights &w = d->b[l];
-			{
-				RQKV<WT> p;
-				p.base.wq = (const char *)w.wq;
-				p.base.wk = (const char *)w.wk;
-				p.base.wv = (const char *)w.wv;
-				p.base.n = c.dim;
-				p.base.q_dim = q_dim;
-				p.base.kv_dim = kv_dim;
-				p.base.head_dim = c.head_dim;
-				p.base.n_groups = (q_dim + 2 * kv_dim) / 2;
-				p.base.qkv_clip = c.qkv_clip;
-				p.base.inv_freq = d->inv_freq;
+			if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias)
+				RQKVB<WT> p;
+				p.base = make_pqkvb<WT>(d, l);
 				p.base.step = d->rstep;
 				p.base.q_out = d->rq;
-				p.base.kcache = w.key_cache;
-				p.base.vcache = w.value_cache;
+				p.n = c.dim;
+				p.n_groups = p.base.n_groups;
+				p.q_stride = q_dim;
+				TRY((launch_rows<WT, RQKVB<WT>, true>(p, d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
+			} else {
+				RQKV<WT> p;
+				p.base = make_pqkv<WT>(d, w);
+				p.base.step = d->rstep;
+				p.base.q_out = d->rq;
 				p.n = c.dim;
 				p.n_groups = p.base.n_groups;
 				p.q_stride = q_dim;
@@ -1995,22 +2096,9 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	case 4: {
 		// reuse the layer enqueue path for exactly one kernel
 		if (kernel_id == 0) {
-			PQKV<WT> p;
-			p.wq = (const char *)w.wq;
-			p.wk = (const char *)w.wk;
-			p.wv = (const char *)w.wv;
-			p.n = c.dim;
-			p.q_dim = q_dim;
-			p.kv_dim = c.n_kv_heads * c.head_dim;
-			p.head_dim = c.head_dim;
-			p.n_groups = (q_dim + 2 * p.kv_dim) / 2;
-			p.qkv_clip = c.qkv_clip;
-			p.inv_freq = d->inv_freq;
-			p.step = d->step;
-			p.q_out = d->q;
-			p.kcache = w.key_cache;
-			p.vcache = w.value_cache;
-			return launch_gemv_d<WT, PQKV<WT>, true>(d, p, d->x, w.rms_att, c.norm_eps, GK_QKV);
+			if (!d->bq.empty())
+				return launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV);
+			return launch_gemv_d<WT, PQKV<WT>, true>(d, make_pqkv<WT>(d, w), d->x, w.rms_att, c.norm_eps, GK_QKV);
 		}
 		if (kernel_id == 2 || kernel_id == 4) {
 			PResidual<WT, 1> p;
@@ -2183,7 +2271,7 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 	std::string s;
 	switch (kernel_id) {
 	case 0:
-		s = gk + ", PQKV<";
+		s = gk + (d->bq.empty() ? ", PQKV<" : ", PQKVB<");
 		break;
 	case 1:
 		s = "attn_decode_kernel<";

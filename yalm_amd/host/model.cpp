@@ -63,6 +63,20 @@ void Config::from_yalm(YALMData &yalm, int context) {
 		throw std::runtime_error("FATAL: mixture of experts needs 1 <= n_experts_active <= n_experts <= 64");
 	if (weight_dtype == DType::Q4 && n_experts > 0)
 		throw std::runtime_error("FATAL: q4 weights have no mixture-of-experts form");
+	const std::string qb = md.value("qkv_bias", "0");
+	qkv_bias = !(qb.empty() || qb == "0" || qb == "False" || qb == "false");
+	if (qkv_bias && n_experts > 0)
+		throw std::runtime_error("FATAL: a q / k / v bias has no mixture-of-experts form");
+	rope_scaling = yalm_rope_scaling{};
+	if (md.contains("rope_scaling_type")) {
+		if (md.at("rope_scaling_type").as_string() != "llama3")
+			throw std::runtime_error("FATAL: unsupported rope_scaling_type: " + md.at("rope_scaling_type").as_string());
+		rope_scaling.type = 1;
+		rope_scaling.factor = std::stof(md.at("rope_scaling_factor").as_string());
+		rope_scaling.low_freq_factor = std::stof(md.at("rope_low_freq_factor").as_string());
+		rope_scaling.high_freq_factor = std::stof(md.at("rope_high_freq_factor").as_string());
+		rope_scaling.original_max_position = meta_int(md, "rope_original_max_position");
+	}
 	if (weight_dtype == DType::Q4 && (dim % 32 || hidden_dim % 32 || (n_heads * head_dim) % 32))
 		throw std::runtime_error("FATAL: q4 needs dim, hidden_dim and n_heads * head_dim multiples of 32");
 }
@@ -85,6 +99,8 @@ size_t Config::active_bytes(size_t pos) const {
 	per_block += q_dim * rb_dim;
 	per_block += 2 * (size_t)n_kv_heads * head_dim * rb_dim;
 	per_block += (size_t)dim * rb_q;
+	if (qkv_bias)
+		per_block += (q_dim + 2 * (size_t)n_kv_heads * head_dim) * sizeof(float);
 	if (n_experts > 0) { // model.cpp:85-87: the router and the active experts
 		per_block += (size_t)n_experts * rb_dim;
 		per_block += (size_t)n_experts_active * (2 * hidden_dim * rb_dim + dim * rb_h);
@@ -183,6 +199,13 @@ Block::Block(int layer_i, std::shared_ptr<Config> config, const Tensor *rms_att_
 	}
 }
 
+void Block::set_qkv_bias(const Tensor *bq, const Tensor *bk, const Tensor *bv) {
+	const Config &c = *_config;
+	_bias[0] = check_tensor(bq, DType::F32, {c.n_heads * c.head_dim, 0, 0, 0});
+	_bias[1] = check_tensor(bk, DType::F32, {c.n_kv_heads * c.head_dim, 0, 0, 0});
+	_bias[2] = check_tensor(bv, DType::F32, {c.n_kv_heads * c.head_dim, 0, 0, 0});
+}
+
 Block::~Block() {
 	for (void *p : _owned)
 		yalm_free(p);
@@ -215,6 +238,11 @@ void Block::cuda() {
 	_w3 = upload(_owned, _w3, ne * c.hidden_dim * rb_dim);
 	if (_moegate)
 		_moegate = upload(_owned, _moegate, (size_t)c.n_experts * rb_dim);
+	if (_bias[0]) {
+		_bias[0] = upload(_owned, _bias[0], q_dim * sizeof(float));
+		_bias[1] = upload(_owned, _bias[1], kv_dim * sizeof(float));
+		_bias[2] = upload(_owned, _bias[2], kv_dim * sizeof(float));
+	}
 	_device = Device::HIP;
 	// The KV cache is allocated (zeroed) by the decoder in HBM: no host copy
 	// to upload (model.cpp:208-210 uploads a zero host array).
@@ -248,6 +276,9 @@ Model::Model(YALMData &yalm, int context) {
 		    get_tensor(yalm, p + "attn.wv.weight"), get_tensor(yalm, p + "attn.wo.weight"),
 		    get_tensor(yalm, p + "mlp.w1.weight"), get_tensor(yalm, p + "mlp.w2.weight"),
 		    get_tensor(yalm, p + "mlp.w3.weight"), c.n_experts > 0 ? get_tensor(yalm, p + "moegate.weight") : nullptr));
+		if (c.qkv_bias)
+			blocks.back()->set_qkv_bias(get_tensor(yalm, p + "attn.wq.bias"), get_tensor(yalm, p + "attn.wk.bias"),
+			                            get_tensor(yalm, p + "attn.wv.bias"));
 	}
 	rms_final_weight = check_tensor(get_tensor(yalm, "model.norm.weight"), DType::F32, {c.dim, 0, 0, 0});
 	_tied = yalm.tensors.count("model.output.weight") == 0;
@@ -295,9 +326,18 @@ void Model::ensure_decoder(InferenceState &s) {
 			gates.push_back(b->moegate());
 		const yalm_moe_config mc{config->n_experts, config->n_experts_active};
 		check(yalm_decoder_create_moe(&cc, &mc, &mw, gates.data(), nullptr, &s._decoder), "decoder create");
-		return;
+	} else {
+		check(yalm_decoder_create(&cc, &mw, nullptr, &s._decoder), "decoder create");
 	}
-	check(yalm_decoder_create(&cc, &mw, nullptr, &s._decoder), "decoder create");
+	if (config->rope_scaling.type)
+		check(yalm_decoder_set_rope_scaling(s._decoder, &config->rope_scaling), "rope scaling");
+	if (config->qkv_bias) {
+		std::vector<const float *> b[3];
+		for (auto &blk : blocks)
+			for (int i = 0; i < 3; ++i)
+				b[i].push_back(blk->bias(i));
+		check(yalm_decoder_set_qkv_bias(s._decoder, b[0].data(), b[1].data(), b[2].data()), "qkv bias");
+	}
 }
 
 void Model::forward(InferenceState &s, int token, int pos, InferenceMode mode) {

@@ -43,6 +43,10 @@ struct Config {
 	float qkv_clip = 3.40282347e38f;
 	int n_experts = 0, n_experts_active = 0;
 	DType weight_dtype = DType::F16;
+	// this engine's own metadata keys (absent: off): a q / k / v bias (Qwen2; tensors
+	// attn.{wq,wk,wv}.bias, F32) and the Llama-3.1 / 3.2 "llama3" RoPE scaling
+	bool qkv_bias = false;
+	yalm_rope_scaling rope_scaling{};
 
 	// model.cpp:17-75 (max_seq_len = min(meta, 4096) unless context != 0)
 	void from_yalm(YALMData &yalm, int context = 0);
@@ -95,6 +99,9 @@ struct Block {
 	void cuda(); // device weight upload (model.cpp:185-211)
 	yalm_block_weights device_weights() const;
 	const void *moegate() const { return _moegate; } // (n_experts, dim) router weights, null when dense
+	// the layer's q / k / v bias (Config::qkv_bias): checked F32 vectors, uploaded by cuda()
+	void set_qkv_bias(const Tensor *bq, const Tensor *bk, const Tensor *bv);
+	const float *bias(int i) const { return (const float *)_bias[i]; } // 0 q, 1 k, 2 v; null without a bias
 
 private:
 	int _layer_i = 0;
@@ -103,6 +110,7 @@ private:
 	const void *_rms_att = nullptr, *_rms_ffn = nullptr;
 	const void *_wq = nullptr, *_wk = nullptr, *_wv = nullptr, *_wo = nullptr, *_w1 = nullptr, *_w2 = nullptr,
 	           *_w3 = nullptr;
+	const void *_bias[3] = {nullptr, nullptr, nullptr};
 	const void *_moegate = nullptr; // with experts, _w1 / _w2 / _w3 are the stacked (n_experts, ...) tensors
 	std::vector<void *> _owned;
 };

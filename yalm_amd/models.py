@@ -59,10 +59,17 @@ class ModelConfig:
     # and a router tensor (moegate) selects n_experts_active of them per token and layer
     n_experts: int = 0
     n_experts_active: int = 0
+    # Qwen2 / Qwen2.5: a bias on the q, k and v projections (f32 tensors attn.{wq,wk,wv}.bias)
+    qkv_bias: bool = False
+    # Llama-3.1 / 3.2 "llama3" RoPE scaling: (type, factor, low_freq_factor, high_freq_factor,
+    # original_max_position) with type "llama3", or None (rope_inv_freq has the rule)
+    rope_scaling: tuple | None = None
 
     def __post_init__(self):
         if not self.rotary_dim:
             self.rotary_dim = self.head_dim
+        if self.rope_scaling is not None:
+            self.rope_scaling = check_rope_scaling(self.rope_scaling)
 
     @property
     def q_dim(self):
@@ -83,6 +90,8 @@ class ModelConfig:
         per_layer = 2 * self.dim * 4
         per_layer += (self.q_dim + 2 * self.kv_dim) * rb_dim  # wq wk wv
         per_layer += self.dim * rb_q  # wo
+        if self.qkv_bias:
+            per_layer += (self.q_dim + 2 * self.kv_dim) * 4  # f32 q / k / v bias
         if self.n_experts > 0:  # model.cpp:85-87: the router + the active experts
             per_layer += self.n_experts * rb_dim
             per_layer += self.n_experts_active * (2 * self.hidden_dim * rb_dim + self.dim * rb_h)
@@ -121,7 +130,42 @@ class ModelConfig:
         if self.n_experts > 0:  # convert.py:78-80
             md["n_experts"] = str(self.n_experts)
             md["n_experts_active"] = str(self.n_experts_active)
+        if self.n_experts == 0 and (self.qkv_bias or self.rope_scaling is not None):
+            md["arch"] = "Qwen2ForCausalLM" if self.qkv_bias else "LlamaForCausalLM"
+        if self.qkv_bias:  # this engine's own keys (the reference reads neither form)
+            md["qkv_bias"] = "1"
+        if self.rope_scaling is not None:
+            md.update(rope_scaling_metadata(self.rope_scaling))
         return md
+
+
+ROPE_SCALING_KEYS = ("rope_scaling_type", "rope_scaling_factor", "rope_low_freq_factor", "rope_high_freq_factor",
+                     "rope_original_max_position")
+
+
+def check_rope_scaling(rs) -> tuple:
+    """(type, factor, low, high, original_max_position) normalised, or ValueError (the rule of
+    yalm_decoder_set_rope_scaling: factor >= 1, high > low > 0, original_max_position > 0)."""
+    kind, factor, low, high, orig = rs
+    if kind != "llama3":
+        raise ValueError(f"unsupported rope scaling type {kind!r} (only 'llama3')")
+    factor, low, high, orig = float(factor), float(low), float(high), int(orig)
+    if not (factor >= 1.0 and high > low > 0.0 and orig > 0):
+        raise ValueError("rope scaling: need factor >= 1, high_freq_factor > low_freq_factor > 0 and "
+                         "original_max_position > 0")
+    return (kind, factor, low, high, orig)
+
+
+def rope_scaling_metadata(rs: tuple) -> dict:
+    return dict(zip(ROPE_SCALING_KEYS, (str(v) for v in rs)))
+
+
+def rope_scaling_from_metadata(md: dict):
+    if "rope_scaling_type" not in md:
+        return None
+    return check_rope_scaling((md["rope_scaling_type"], float(md["rope_scaling_factor"]),
+                               float(md["rope_low_freq_factor"]), float(md["rope_high_freq_factor"]),
+                               int(md["rope_original_max_position"])))
 
 
 def config_from_metadata(md: dict, context: int = 0, tied: bool = False) -> ModelConfig:
@@ -154,6 +198,8 @@ def config_from_metadata(md: dict, context: int = 0, tied: bool = False) -> Mode
         eos_token_id=int(md.get("eos_token_id", "2")),
         n_experts=int(md.get("n_experts", "0")),  # model.cpp:25-29
         n_experts_active=int(md.get("n_experts_active", "0")),
+        qkv_bias=md.get("qkv_bias", "0") not in ("0", "False", "false", ""),
+        rope_scaling=rope_scaling_from_metadata(md),
     )
 
 
@@ -197,6 +243,12 @@ def layer_names(l: int) -> dict:
     }
 
 
+def bias_names(l: int) -> dict:
+    """The q / k / v bias tensors of layer l (ModelConfig.qkv_bias), 1-D F32."""
+    p = f"model.layers.{l}.attn."
+    return {"bq": p + "wq.bias", "bk": p + "wk.bias", "bv": p + "wv.bias"}
+
+
 def moegate_name(l: int) -> str:
     return f"model.layers.{l}.moegate.weight"
 
@@ -214,6 +266,11 @@ def tensor_shapes(c: ModelConfig) -> dict:
         out[n["wk"]] = ((c.kv_dim, c.dim), False)
         out[n["wv"]] = ((c.kv_dim, c.dim), False)
         out[n["wo"]] = ((c.dim, c.q_dim), False)
+        if c.qkv_bias:  # stored F32, as the norms are
+            b = bias_names(l)
+            out[b["bq"]] = ((c.q_dim,), True)
+            out[b["bk"]] = ((c.kv_dim,), True)
+            out[b["bv"]] = ((c.kv_dim,), True)
         e = (c.n_experts,) if c.n_experts > 0 else ()  # model.cpp:160-164: stacked per expert
         if e:
             out[moegate_name(l)] = ((c.n_experts, c.dim), False)
@@ -275,6 +332,10 @@ def shard_array(c: ModelConfig, name: str, a, rank: int, size: int):
 # ---- deterministic synthetic init (same hash on device and in the oracle) ----
 WEIGHT_SCALE = 0.035  # uniform [-a, a): std 0.02, the usual init scale
 NORM_SCALE, NORM_OFFSET = 0.2, 1.0
+# synthetic q / k / v bias, uniform [-a, a): W . xb has a std of ~0.16 (dim 64) to ~1.3 (dim 4096)
+# with these weights (trained Qwen2.5 biases reach tens), so a model run without its bias is
+# unmistakably another model: its logits move by 1e-2 of their range or more at every shape tested
+BIAS_SCALE = 4.0
 
 
 def synth_seed(base: int, name: str) -> int:
@@ -292,6 +353,8 @@ def synth_params(name: str, is_norm: bool, peak: float = 1.0, real: "Realistic" 
     (its other features are patches, realistic_patch)."""
     if real is not None:
         peak = peak * real.final_norm
+    if name.endswith(".bias"):  # q / k / v bias: the size of the projections' own outputs
+        return BIAS_SCALE, 0.0
     if is_norm:
         k = peak if name == "model.norm.weight" else 1.0
         return NORM_SCALE * k, NORM_OFFSET * k
@@ -593,7 +656,23 @@ def rope_inv_freq(c: ModelConfig) -> np.ndarray:
     rinv = np.float32(1.0) / np.float32(c.rotary_dim)
     f = np.power(np.float32(c.rope_theta), -(j * rinv).astype(np.float32)).astype(np.float32)
     f[j >= c.rotary_dim] = 0.0
-    return f.astype(np.float32)
+    if c.rope_scaling is None:
+        return f.astype(np.float32)
+    return llama3_scale(f, c.rope_scaling)
+
+
+def llama3_scale(f: np.ndarray, rs: tuple) -> np.ndarray:
+    """The "llama3" rule on f32 pair frequencies f (yalm_decoder_set_rope_scaling): with the
+    wavelength w = 2 pi / f, w < orig / high keeps f, w > orig / low gives f / factor, between
+    them s = (orig / w - low) / (high - low) blends (1 - s) f / factor + s f; in double, rounded
+    once to f32."""
+    _, factor, low, high, orig = check_rope_scaling(rs)
+    f = np.asarray(f, np.float32).astype(np.float64)
+    with np.errstate(divide="ignore"):
+        w = 2.0 * np.pi / f
+    s = (orig / w - low) / (high - low)
+    out = np.where(w < orig / high, f, np.where(w > orig / low, f / factor, (1.0 - s) * f / factor + s * f))
+    return np.where(f == 0.0, 0.0, out).astype(np.float32)
 
 
 def kv_indices(max_seq_len: int, pos: int):

@@ -82,6 +82,21 @@ class SpecStats(ctypes.Structure):
                 ("launches_per_step", c_int)]
 
 
+class RopeScaling(ctypes.Structure):
+    """yalm_rope_scaling: type 0 none, 1 llama3."""
+
+    _fields_ = [("type", c_int), ("factor", c_float), ("low_freq_factor", c_float), ("high_freq_factor", c_float),
+                ("original_max_position", c_int)]
+
+    @classmethod
+    def from_model(cls, rs) -> "RopeScaling":
+        """From ModelConfig.rope_scaling (None: type 0)."""
+        if rs is None:
+            return cls(0, 1.0, 1.0, 4.0, 1)
+        _, factor, low, high, orig = M.check_rope_scaling(rs)
+        return cls(1, factor, low, high, orig)
+
+
 class BlockWeights(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("rms_att", "rms_ffn", "wq", "wk", "wv", "wo", "w1", "w2", "w3",
                                         "key_cache", "value_cache")]
@@ -166,6 +181,9 @@ _sig("yalm_forward_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p])
 _sig("yalm_generate_speculative", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Spec), c_void_p, c_int, c_void_p,
                                            ctypes.POINTER(SpecStats)])
 _sig("yalm_spec_draft", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+_sig("yalm_decoder_set_rope_scaling", c_int, [c_void_p, ctypes.POINTER(RopeScaling)])
+_sig("yalm_decoder_get_inv_freq", c_int, [c_void_p, c_void_p])
+_sig("yalm_decoder_set_qkv_bias", c_int, [c_void_p, c_void_p, c_void_p, c_void_p])
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -183,6 +201,7 @@ EXPORTED = [
     "yalm_generate_sampled", "yalm_sample",
     "yalm_row_bytes", "yalm_synth_q4",
     "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
+    "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -591,6 +610,33 @@ class Decoder:
         self.h = h
         if launch:
             self.set_launch(launch)
+        # the model family's forms (off unless the config has them)
+        if self.cfg.rope_scaling is not None:
+            self.set_rope_scaling(self.cfg.rope_scaling)
+        if self.cfg.qkv_bias:
+            self.set_qkv_bias(True)
+
+    def set_rope_scaling(self, rs) -> None:
+        """yalm_decoder_set_rope_scaling: rs as ModelConfig.rope_scaling, a RopeScaling (passed as it
+        is, so the tests can send bad parameters), or None = the plain table."""
+        s = rs if isinstance(rs, RopeScaling) else RopeScaling.from_model(rs)
+        check(lib.yalm_decoder_set_rope_scaling(self.h, ctypes.byref(s)))
+
+    def inv_freq(self) -> np.ndarray:
+        """The RoPE frequency table in use (yalm_decoder_get_inv_freq)."""
+        out = np.empty(self.cfg.head_dim // 2, np.float32)
+        check(lib.yalm_decoder_get_inv_freq(self.h, out.ctypes.data))
+        return out
+
+    def set_qkv_bias(self, on: bool = True) -> None:
+        """yalm_decoder_set_qkv_bias with the model's attn.{wq,wk,wv}.bias tensors, or off."""
+        if not on:
+            check(lib.yalm_decoder_set_qkv_bias(self.h, None, None, None))
+            return
+        L = self.cfg.n_layers
+        names = [M.bias_names(l) for l in range(L)]
+        self._bias = [(c_void_p * L)(*[self.model.ptrs[n[k]] for n in names]) for k in ("bq", "bk", "bv")]
+        check(lib.yalm_decoder_set_qkv_bias(self.h, *self._bias))
 
     def set_launch(self, flags: int) -> None:
         """yalm_decoder_set_launch: LAUNCH_EAGER | LAUNCH_SYNC | LAUNCH_SEPARATE_ATTN_WO (0 = default)."""
