@@ -211,7 +211,8 @@ int yalm_get_logits(yalm_decoder d, float *host);
  * timed separately and subtracted), 10 = the sampling launch of yalm_generate_sampled on
  * the decoder's current logits, with the parameters of the last such call (before any:
  * temperature 1, no truncation) and its first uniform; it commits into a scratch step
- * state, not the decoder's. Used by bench.py for the roofline of the
+ * state, not the decoder's; 11 = the q / k norm launch (yalm_decoder_set_qk_norm, which it
+ * needs) on what the last QKV launch left. Used by bench.py for the roofline of the
  * dominant kernel. */
 int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms);
 /* The same-process streaming envelope: average ms of one pure read-only pass over
@@ -304,6 +305,28 @@ int yalm_decoder_get_inv_freq(yalm_decoder d, float *host);
  * decoder returns YALM_ERR_UNSUPPORTED. */
 int yalm_decoder_set_qkv_bias(yalm_decoder d, const float *const *bq, const float *const *bk,
                               const float *const *bv);
+/* q / k norm (Qwen3): an RMSNorm over each head of q and of k, after the projection and the
+ * clip and before RoPE. With q, k, v = clip(W . rmsnorm(x)) as without it, for every head h of
+ * q and of k:
+ *   ss = sum_i a[h][i]^2 over the head's head_dim elements
+ *   a'[h][i] = a[h][i] * (1 / sqrtf(ss / head_dim + norm_eps)) * g[i]
+ * g = gq[l] for q and gk[l] for k (head_dim f32 values shared by the layer's heads; no bias),
+ * norm_eps the config's. All f32 in this statement order; the sum is one wave's fixed-order
+ * reduction, so the same input gives the same bits on every run. RoPE on a', the q store and
+ * the f16 K cache write follow as without the norm; V is untouched, and so is the attention
+ * sinks' one-position rotation (it turns rows that were normalised when they were written).
+ * gq, gk: HOST arrays of n_layers DEVICE pointers, 8-byte aligned and caller-owned for the
+ * decoder's lifetime. Both NULL removes the norm. Drops the captured graphs. Off by default:
+ * a decoder on which it was never called launches what it launched before; with it, one more
+ * launch per layer (qk_norm_rope_kernel, yalm_time_kernel id 11) between QKV and attention.
+ * Dense one-GPU decoders of every weight dtype: decode and yalm_forward_rows /
+ * yalm_generate_speculative (not q4, as without the norm), and yalm_prefill: its QKV GEMM
+ * leaves raw f32 rows and one row kernel clips, norms, rotates and stores Q and the K / V cache
+ * rows, in every precision form. YALM_ERR_UNSUPPORTED, naming the q / k
+ * norm: a tensor-parallel or mixture-of-experts decoder, a decoder that has a q / k / v bias
+ * (and yalm_decoder_set_qkv_bias on a decoder that has the norm).
+ * YALM_ERR_ARG: exactly one array NULL, a NULL or misaligned (not 8-byte) entry. */
+int yalm_decoder_set_qk_norm(yalm_decoder d, const float *const *gq, const float *const *gk);
 
 /* ---------------- mixture of experts (Mixtral), one GPU ----------------
  * The reference runs MoE on the CPU only (infer.cpp:100-132, 347-384; its GPU path

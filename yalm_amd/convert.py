@@ -18,6 +18,10 @@ and v, written F32 as ``attn.{wq,wk,wv}.bias`` with the q / k rows permuted as t
 rows are; metadata ``qkv_bias``), and Llama-3.1 / 3.2 ``rope_scaling`` of type ``llama3``
 (metadata ``rope_scaling_type`` / ``rope_scaling_factor`` / ``rope_low_freq_factor`` /
 ``rope_high_freq_factor`` / ``rope_original_max_position``). Any other scaling type raises.
+Qwen3 dense models (``Qwen3ForCausalLM``) are a third: the Llama block plus an RMSNorm over each
+head of q and k ahead of RoPE, written F32 as ``attn.{q_norm,k_norm}.weight`` (``head_dim``
+elements) with the within-head permutation of the q / k rows, so each weight stays with its
+element; metadata ``qk_norm``. Sliding-window layers and an attention bias raise.
 
 Usage: python -m yalm_amd.convert [--dtype fp16] out.yalm hf_dir/
 """
@@ -33,7 +37,8 @@ import numpy as np
 from . import models as M
 from .yalmfile import read_yalm, write_yalm
 
-SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM", "Qwen2ForCausalLM"]
+SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM", "Qwen2ForCausalLM",
+                           "Qwen3ForCausalLM"]
 SUPPORTED_DTYPES = ["fp32", "fp16", "fp8", "q4"]
 
 
@@ -50,8 +55,11 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
     if config.get("attention_bias", False) or config.get("mlp_bias", False):
         raise ValueError("attention/mlp bias is not supported")
     qwen2 = arch == "Qwen2ForCausalLM"
-    if qwen2 and config.get("use_sliding_window", False):
-        raise ValueError("Qwen2 use_sliding_window is not supported")
+    qwen3 = arch == "Qwen3ForCausalLM"
+    if (qwen2 or qwen3) and config.get("use_sliding_window", False):
+        raise ValueError(f"{arch[:5]} use_sliding_window is not supported")
+    if qwen3 and any(t != "full_attention" for t in config.get("layer_types") or []):
+        raise ValueError("Qwen3 layer_types other than full_attention are not supported")
     rope_scaling = rope_scaling_from_config(config)
     if config["hidden_act"] not in ("gelu", "silu"):
         raise ValueError(f"unsupported hidden_act {config['hidden_act']}")
@@ -79,6 +87,8 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
         md["n_experts_active"] = config["num_experts_per_tok"]
     if qwen2:
         md["qkv_bias"] = 1
+    if qwen3:
+        md["qk_norm"] = 1
     if rope_scaling is not None:
         md.update(M.rope_scaling_metadata(rope_scaling))
     # str() of the python value, as convert.py:63-80 does (floats print as 10000.0, 1e-05)
@@ -226,6 +236,9 @@ def convert(hf_dir: str, out_path: str, dtype: str = "fp16") -> None:
             if md.get("qkv_bias") == "1":  # the bias rows move with their weight rows
                 bias = _to_f32(src[p + f"self_attn.{hf}.bias"]).reshape(-1, 1)
                 put(q + f"attn.{key}.bias", (np.ascontiguousarray(permute_reverse(bias, heads, rot)[:, 0]), "F32"))
+            if md.get("qk_norm") == "1":  # one head's weights, permuted as one head's rows are
+                g = _to_f32(src[p + f"self_attn.{hf[0]}_norm.weight"]).reshape(-1, 1)
+                put(q + f"attn.{hf[0]}_norm.weight", (np.ascontiguousarray(permute_reverse(g, 1, rot)[:, 0]), "F32"))
         put(q + "attn.wv.weight", conv(p + "self_attn.v_proj.weight"))
         if md.get("qkv_bias") == "1":
             put(q + "attn.wv.bias", (_to_f32(src[p + "self_attn.v_proj.bias"]).reshape(-1), "F32"))

@@ -76,6 +76,7 @@ struct PrefillBufs {
 	float *pmax = nullptr, *psum = nullptr; // [cap][vocab / 128] logits partials
 	float *tgt_logit = nullptr, *lp = nullptr; // [cap]
 	float *rope = nullptr;                     // [cap][head_dim / 2][2]
+	float *qkraw = nullptr;                    // q / k normed models: [cap][q_dim + 2 kv_dim] f32 raw QKV (allocated on first use)
 	float *skp = nullptr;                      // split-K partials of the short-prompt GEMMs (prefill_skinny.h)
 	size_t skp_floats = 0;
 	unsigned *range = nullptr;                 // [n_layers + 1][4] f16-operand range guard (prefill.h range_note)
@@ -196,6 +197,11 @@ struct yalm_decoder_s {
 	// (yalm_decoder_set_qkv_bias: [n_layers] device pointers each, empty = no bias)
 	yalm_rope_scaling rope_scaling{};
 	std::vector<const float *> bq, bk, bv;
+	// the per-head RMSNorm on q and k (yalm_decoder_set_qk_norm: [n_layers] device pointers to
+	// head_dim weights each, empty = no norm) and the QKV GEMV's raw clipped q | k,
+	// [ROWS_MAX_T][q_dim + kv_dim] (allocated by the first set; decode uses row 0)
+	std::vector<const float *> gq, gk;
+	float *qk_raw = nullptr;
 	std::vector<const void *> moegate; // [n_layers] router weights (n_experts, dim)
 	int *moe_sel = nullptr;            // [n_layers][moe_K] the routing of the most recent forward
 	float *moe_wts = nullptr;          // [n_layers][moe_K]

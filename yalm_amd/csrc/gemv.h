@@ -297,6 +297,31 @@ struct PQKVB : PQKV<WT> {
 	__device__ __forceinline__ void finish_all(int g, const float *acc) const { finish(g, acc, 0); }
 };
 
+// PQKV ahead of a per-head RMSNorm on q and k (Qwen3; qk_norm.h): a head's 64 RoPE pairs finish
+// in different workgroups (gemv_rb_kernel deals group g to workgroup g % NB), so no epilogue has
+// the head's sum of squares. The q and k pairs are clipped and stored raw, f32, at raw[2 g]
+// ([q_dim + kv_dim], one 8-byte store); qk_norm_rope_kernel norms, rotates and stores them. V
+// pairs take PQKV's epilogue as it is, and so does the sink rotation (early / late).
+template <class WT>
+struct PQKVN : PQKV<WT> {
+	float *raw;
+	__device__ __forceinline__ void finish(int g, const float *acc, int lane) const {
+		if (lane != 0)
+			return;
+		const int vr = 2 * g;
+		if (vr >= this->q_dim + this->kv_dim) {
+			PQKV<WT>::finish(g, acc, 0);
+			return;
+		}
+		const float c = this->qkv_clip;
+		float2_t v;
+		v[0] = acc[0] < -c ? -c : (acc[0] > c ? c : acc[0]);
+		v[1] = acc[1] < -c ? -c : (acc[1] > c ? c : acc[1]);
+		*(float2_t *)(raw + vr) = v;
+	}
+	__device__ __forceinline__ void finish_all(int g, const float *acc) const { finish(g, acc, 0); }
+};
+
 template <class WT, int ACT>
 struct PGlu {
 	static constexpr int R = 2;

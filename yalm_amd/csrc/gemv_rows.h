@@ -114,6 +114,27 @@ struct RQKVB {
 	}
 };
 
+// RQKV ahead of the q / k norm: row t's epilogue is PQKVN::finish into row t of the raw buffer
+// ([T][raw_stride]); one qk_norm_rope_kernel launch then serves all T rows (qk_norm.h).
+template <class WT>
+struct RQKVN {
+	static constexpr int R = 2;
+	PQKVN<WT> base;
+	int n, n_groups, raw_stride;
+	__device__ __forceinline__ const char *row(int g, int r) const { return base.row(g, r); }
+	template <int T>
+	__device__ __forceinline__ void finish(int g, const float (&acc)[R][T]) const {
+#pragma unroll
+		for (int t = 0; t < T; ++t) {
+			PQKVN<WT> b = base;
+			b.step = base.step + t;
+			b.raw = base.raw + (size_t)t * raw_stride;
+			const float a[2] = {acc[0][t], acc[1][t]};
+			b.finish(g, a, 0);
+		}
+	}
+};
+
 template <class WT, int ACT>
 struct RGlu {
 	static constexpr int R = 2;

@@ -560,4 +560,59 @@ __global__ __launch_bounds__(256) void logprob_kernel(const float *__restrict__ 
 	}
 }
 
+// The q / k norm of a normed model (Qwen3, yalm_decoder_set_qk_norm) over the rows of a prefill:
+// raw [T][q_dim + 2 kv_dim] is the QKV GEMM's f32 output (E16StoreF32: unclipped q | k | v). One
+// wave64 per (row m, head h), h over the q heads, then the k heads, then the v heads; a lane
+// holds RoPE pair `lane` of the head (head_dim 64 or 128: check_prefill_shape). q and k heads:
+// clip, ss through wave_sum, a * (1 / sqrtf(ss / head_dim + eps)) * g (the decode kernel's
+// statement order, qk_norm.h), the rotation from the prefill's table row m, then Q as f16
+// ([hi | lo] with SPLITQ, lo q_dim columns after hi, row stride 2 q_dim) or the K cache row
+// pos0 + m. v heads: clip and the V cache row. The Q range guard sees the normalised Q.
+template <bool SPLITQ>
+__global__ __launch_bounds__(256) void qk_norm_rope_rows_kernel(
+    const float *__restrict__ raw, const float *__restrict__ gq, const float *__restrict__ gk,
+    const float *__restrict__ rope, int T, int n_heads, int n_kv_heads, int head_dim, int pos0, float clip, float eps,
+    uint16_t *__restrict__ q, uint16_t *__restrict__ kc, uint16_t *__restrict__ vc, unsigned *range) {
+	const int H = n_heads + 2 * n_kv_heads;
+	const size_t gw = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (gw >= (size_t)T * H)
+		return;
+	const int m = (int)(gw / H), h = (int)(gw % H), lane = threadIdx.x & 63;
+	const int half = head_dim >> 1, q_dim = n_heads * head_dim, kv_dim = n_kv_heads * head_dim;
+	const bool on = lane < half;
+	const int p = on ? lane : 0;
+	const float2_t a = *(const float2_t *)(raw + (size_t)m * (q_dim + 2 * kv_dim) + (size_t)h * head_dim + 2 * p);
+	float v0 = a[0] < -clip ? -clip : (a[0] > clip ? clip : a[0]);
+	float v1 = a[1] < -clip ? -clip : (a[1] > clip ? clip : a[1]);
+	if (h >= n_heads + n_kv_heads) { // V: no norm, no rotation
+		if (on)
+			*(uint32_t *)(vc + (size_t)(pos0 + m) * kv_dim + (size_t)(h - n_heads - n_kv_heads) * head_dim + 2 * p) =
+			    (uint32_t)f2h(v0) | ((uint32_t)f2h(v1) << 16);
+		return;
+	}
+	const bool is_q = h < n_heads;
+	const float2_t w = *(const float2_t *)((is_q ? gq : gk) + 2 * p);
+	const float2_t cs = *(const float2_t *)(rope + ((size_t)m * half + p) * 2);
+	const float ss = wave_sum(on ? __builtin_fmaf(v1, v1, v0 * v0) : 0.0f);
+	const float scale = 1.0f / sqrtf(ss / head_dim + eps);
+	const float a0 = v0 * scale * w[0], a1 = v1 * scale * w[1];
+	const float r0 = a0 * cs[0] - a1 * cs[1], r1 = a0 * cs[1] + a1 * cs[0];
+	if (!is_q) {
+		if (on)
+			*(uint32_t *)(kc + (size_t)(pos0 + m) * kv_dim + (size_t)(h - n_heads) * head_dim + 2 * p) =
+			    (uint32_t)f2h(r0) | ((uint32_t)f2h(r1) << 16);
+		return;
+	}
+	float qmax = 0.0f;
+	if (on) {
+		const uint16_t b0 = f2h(r0), b1 = f2h(r1);
+		uint16_t *dst = q + (size_t)m * (SPLITQ ? 2 * q_dim : q_dim) + (size_t)h * head_dim + 2 * p;
+		*(uint32_t *)dst = (uint32_t)b0 | ((uint32_t)b1 << 16);
+		if constexpr (SPLITQ)
+			*(uint32_t *)(dst + q_dim) = (uint32_t)f2h(r0 - h2f(b0)) | ((uint32_t)f2h(r1 - h2f(b1)) << 16);
+		qmax = fmaxf(fabsf(r0), fabsf(r1));
+	}
+	range_note(range, qmax, qmax);
+}
+
 } // namespace pf

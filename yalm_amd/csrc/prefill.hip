@@ -563,6 +563,16 @@ int check_prefill_shape(const yalm_config &c) {
 	return YALM_OK;
 }
 
+// A q / k normed decoder (yalm_decoder_set_qk_norm): the f32 scratch its QKV GEMM stores raw
+// q | k | v rows into, ahead of qk_norm_rope_rows_kernel (prefill.h), allocated on first use.
+int ensure_qk_raw(yalm_decoder_s *d) {
+	if (d->gq.empty() || d->pf.qkraw)
+		return YALM_OK;
+	const yalm_config &c = d->c;
+	return pf_alloc(d, (void **)&d->pf.qkraw,
+	                (size_t)c.max_seq_len * (c.n_heads + 2 * c.n_kv_heads) * c.head_dim * sizeof(float));
+}
+
 int ensure_bufs(yalm_decoder_s *d) {
 	PrefillBufs &b = d->pf;
 	if (b.cap)
@@ -777,7 +787,37 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 				}
 				return YALM_OK;
 			};
-			TRY(d->bq.empty() ? qkv_gemms(std::false_type{}) : qkv_gemms(std::true_type{}));
+			// a q / k normed model (Qwen3; never biased): every form leaves raw f32 q | k | v rows --
+			// the large tiles as ONE GEMM over [hi | lo] (the split form's launch; q too, so the
+			// fast form's Q comes from the more exact operand), the skinny path through its own
+			// two GEMMs and reduce -- and one row kernel clips, norms, rotates and stores
+			auto qkv_normed = [&]() -> int {
+				const int np = q_dim + 2 * kv_dim;
+				pf::E16StoreF32 e;
+				e.c = b.qkraw;
+				e.ldc = np;
+				e.M = T;
+				if (small) {
+					const pf::BRowsPlain bm{qkv};
+					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, c.dim, c.dim, bm, q_dim, ks_qkv, 0, np, b.skp, st));
+					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, bm, 2 * kv_dim, 2 * ks_qkv, q_dim, np, b.skp,
+					                  st));
+					TRY(launch_skinny_reduce<false>(b.skp, ks_qkv, 2 * ks_qkv, q_dim, T, np, e, st));
+				} else {
+					TRY(launch_plain(f, bn_qkv_all, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, np, e, st));
+				}
+				const size_t waves = (size_t)T * (c.n_heads + 2 * c.n_kv_heads);
+				auto kern = split ? pf::qk_norm_rope_rows_kernel<true> : pf::qk_norm_rope_rows_kernel<false>;
+				hipLaunchKernelGGL(kern, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, b.qkraw, d->gq[l], d->gk[l],
+				                   b.rope, T, c.n_heads, c.n_kv_heads, c.head_dim, pos0, c.qkv_clip, c.norm_eps, b.Q,
+				                   w.key_cache, w.value_cache, rg + RG_Q);
+				HIPCHK(hipGetLastError());
+				return YALM_OK;
+			};
+			if (!d->gq.empty())
+				TRY(qkv_normed());
+			else
+				TRY(d->bq.empty() ? qkv_gemms(std::false_type{}) : qkv_gemms(std::true_type{}));
 		}
 		TRY(launch_attn_prefill(b.Q, w.key_cache, w.value_cache, T, pos0, c.n_heads, c.n_kv_heads, c.head_dim, b.O,
 								st, split));
@@ -897,6 +937,7 @@ extern "C" int yalm_prefill(yalm_decoder d, const int *tokens, int n, int pos0, 
 	const yalm_config &c = d->c;
 	ARGCHK(pos0 + n <= c.max_seq_len, "yalm_prefill: pos0 + n must be <= max_seq_len (no sliding window in prefill)");
 	TRY(check_prefill_shape(c));
+	TRY(ensure_qk_raw(d));
 	TRY(ensure_bufs(d));
 	PrefillBufs &b = d->pf;
 	std::vector<int> tgt(n);
@@ -968,6 +1009,7 @@ extern "C" int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms
 	const yalm_config &c = d->c;
 	ARGCHK(n <= c.max_seq_len, "yalm_prefill_time: n > max_seq_len");
 	TRY(check_prefill_shape(c));
+	TRY(ensure_qk_raw(d));
 	TRY(ensure_bufs(d));
 	std::vector<int> tok(n);
 	for (int i = 0; i < n; ++i)

@@ -25,6 +25,7 @@
 #include "gemv_rows.h"
 #include "misc_kernels.h"
 #include "moe.h"
+#include "qk_norm.h"
 #include "sampler.h"
 #include "spec.h"
 
@@ -219,6 +220,10 @@ struct RowsMode<PQKV<WT>> {
 };
 template <class WT>
 struct RowsMode<PQKVB<WT>> {
+	static constexpr bool value = true;
+};
+template <class WT>
+struct RowsMode<PQKVN<WT>> {
 	static constexpr bool value = true;
 };
 // the expert policies (moe.h) stream as their dense counterparts do
@@ -921,6 +926,28 @@ static PQKVB<WT> make_pqkvb(const yalm_decoder_s *d, int l) {
 	return p;
 }
 
+// ... ahead of layer l's q / k norm (yalm_decoder_set_qk_norm): q and k raw into qk_raw
+template <class WT>
+static PQKVN<WT> make_pqkvn(const yalm_decoder_s *d, int l) {
+	PQKVN<WT> p;
+	static_cast<PQKV<WT> &>(p) = make_pqkv<WT>(d, d->b[l]);
+	p.raw = d->qk_raw;
+	return p;
+}
+// The q / k norm launch of layer l over `rows` rows (qk_norm.h): raw rows of qk_raw, the step
+// states step[0 .. rows), q rows of q_dim at q_out. One wave per workgroup, n_heads + n_kv_heads
+// workgroups per row: four waves per workgroup over a quarter as many CUs measured the same at
+// the Qwen3-8B shape (profiles/qknorm_bench.txt: no difference outside the repeat spread).
+static int launch_qk_norm(yalm_decoder_s *d, int l, int rows, const StepState *step, float *q_out) {
+	const yalm_config &c = d->c;
+	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim, heads = c.n_heads + c.n_kv_heads;
+	qk_norm_rope_kernel<1><<<dim3(heads, rows), YALM_WAVE, 0, d->stream>>>(
+	    d->qk_raw, q_dim + kv_dim, d->gq[l], d->gk[l], c.n_heads, c.n_kv_heads, c.head_dim, c.norm_eps, step, q_out,
+	    q_dim, d->b[l].key_cache);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
 // One layer. IPC tensor parallelism (tp_exchange.h): the Wo partial is exchange ex0 (the GLU
 // consumes it), the W2 partial exchange ex0 + 1 (push_w2; the next QKV or the logits GEMV
 // consumes it); x_exchanged: the layer's input x is exchange ex0 - 1 (the QKV GEMV consumes
@@ -932,7 +959,10 @@ static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, 
 	hipStream_t st = d->stream;
 	const int q_dim = c.n_heads * c.head_dim;
 	const TpX none{};
-	if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias; never tensor parallel)
+	if (!d->gq.empty()) { // a q / k normed model (yalm_decoder_set_qk_norm; never tensor parallel, never biased)
+		TRY((launch_gemv_d<WT, PQKVN<WT>, true>(d, make_pqkvn<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV, none)));
+		TRY(launch_qk_norm(d, l, 1, d->step, d->q));
+	} else if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias; never tensor parallel)
 		TRY((launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV, none)));
 	} else {
 		const PQKV<WT> p = make_pqkv<WT>(d, w);
@@ -1199,6 +1229,11 @@ extern "C" int yalm_decoder_set_qkv_bias(yalm_decoder d, const float *const *bq,
 	}
 	const bool none = !bq && !bk && !bv;
 	ARGCHK(none || (bq && bk && bv), "yalm_decoder_set_qkv_bias: bias arrays for q, k and v, or all three NULL");
+	if (!none && !d->gq.empty()) {
+		set_err("yalm_decoder_set_qkv_bias: the decoder has a q / k norm (yalm_decoder_set_qk_norm); no form runs a "
+		        "bias together with the q / k norm");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	const int L = d->c.n_layers;
 	if (!none)
 		for (int l = 0; l < L; ++l) // (the epilogue reads a RoPE pair's two values as one 8-byte load)
@@ -1212,6 +1247,40 @@ extern "C" int yalm_decoder_set_qkv_bias(yalm_decoder d, const float *const *bq,
 	} else {
 		d->bq.assign(bq, bq + L), d->bk.assign(bk, bk + L), d->bv.assign(bv, bv + L);
 	}
+	return YALM_OK;
+}
+
+extern "C" int yalm_decoder_set_qk_norm(yalm_decoder d, const float *const *gq, const float *const *gk) {
+	ARGCHK(d, "yalm_decoder_set_qk_norm: null decoder");
+	const char *why = nullptr;
+	if (d->tp_size > 1 || d->comm || d->ipc)
+		why = "a tensor-parallel decoder";
+	else if (d->moe_E > 0)
+		why = "a mixture-of-experts decoder";
+	else if (!d->bq.empty())
+		why = "a decoder that has a q / k / v bias (yalm_decoder_set_qkv_bias)";
+	if (why) {
+		set_err(std::string("yalm_decoder_set_qk_norm: the q / k norm runs on dense one-GPU decoders without a bias, not on ") +
+		        why);
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const bool none = !gq && !gk;
+	ARGCHK(none || (gq && gk), "yalm_decoder_set_qk_norm: q / k norm arrays for q and k, or both NULL");
+	const int L = d->c.n_layers;
+	if (!none)
+		for (int l = 0; l < L; ++l) // (the kernel reads a RoPE pair's two weights as one 8-byte load)
+			ARGCHK(gq[l] && gk[l] && (uintptr_t)gq[l] % 8 == 0 && (uintptr_t)gk[l] % 8 == 0,
+			       "yalm_decoder_set_qk_norm: a layer's q / k norm pointer is null or not 8-byte aligned");
+	HIPCHK(hipStreamSynchronize(d->stream));
+	drop_graphs(d); // captured graphs bake the launch sequence without (or with the old) norm
+	if (none) {
+		d->gq.clear(), d->gk.clear();
+		return YALM_OK;
+	}
+	if (!d->qk_raw)
+		TRY(dalloc(d, (void **)&d->qk_raw,
+		           sizeof(float) * ROWS_MAX_T * (size_t)(d->c.n_heads + d->c.n_kv_heads) * d->c.head_dim));
+	d->gq.assign(gq, gq + L), d->gk.assign(gk, gk + L);
 	return YALM_OK;
 }
 
@@ -1780,7 +1849,8 @@ static int launch_rows_glu(yalm_decoder_s *d, const yalm_block_weights &w, int T
 
 // T rows through every layer: rows begin, then per layer QKV (+ clip, RoPE, KV write), one
 // attention launch per row (the decode kernel with that row's step state, q and out), Wo, W1|W3,
-// W2; then norm + logits into rlogits [T][vocab]. 2 + n_layers * (4 + T) launches.
+// W2; then norm + logits into rlogits [T][vocab]. 2 + n_layers * (4 + T) launches, one more per
+// layer with the q / k norm.
 template <class WT>
 static int enqueue_rows_forward_t(yalm_decoder_s *d, int T, int from_step) {
 	if constexpr (WT::Q4) {
@@ -1795,7 +1865,16 @@ static int enqueue_rows_forward_t(yalm_decoder_s *d, int T, int from_step) {
 		HIPCHK(hipGetLastError());
 		for (int l = 0; l < c.n_layers; ++l) {
 			const yalm_block_weights &w = d->b[l];
-			if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias)
+			if (!d->gq.empty()) { // a q / k normed model: raw rows, then one norm launch for all T rows
+				RQKVN<WT> p;
+				p.base = make_pqkvn<WT>(d, l);
+				p.base.step = d->rstep;
+				p.n = c.dim;
+				p.n_groups = p.base.n_groups;
+				p.raw_stride = q_dim + c.n_kv_heads * c.head_dim;
+				TRY((launch_rows<WT, RQKVN<WT>, true>(p, d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
+				TRY(launch_qk_norm(d, l, T, d->rstep, d->rq));
+			} else if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias)
 				RQKVB<WT> p;
 				p.base = make_pqkvb<WT>(d, l);
 				p.base.step = d->rstep;
@@ -1935,7 +2014,7 @@ extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int
 	       "yalm_generate_speculative: bad draft_stream");
 	const int rows = cfg->rows, L = d->c.n_layers, n = n_tokens;
 	yalm_spec_stats s{};
-	s.launches_per_step = 4 + L * (4 + rows);
+	s.launches_per_step = 4 + L * ((d->gq.empty() ? 4 : 5) + rows);
 	if (n == 0) {
 		if (stats)
 			*stats = s;
@@ -2096,6 +2175,8 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	case 4: {
 		// reuse the layer enqueue path for exactly one kernel
 		if (kernel_id == 0) {
+			if (!d->gq.empty())
+				return launch_gemv_d<WT, PQKVN<WT>, true>(d, make_pqkvn<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV);
 			if (!d->bq.empty())
 				return launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV);
 			return launch_gemv_d<WT, PQKV<WT>, true>(d, make_pqkv<WT>(d, w), d->x, w.rms_att, c.norm_eps, GK_QKV);
@@ -2128,6 +2209,8 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 		if constexpr (wt_fused_wo<WT>())
 			return launch_attn_wo<WT>(d, w, l, 0);
 		break;
+	case 11: // the q / k norm launch on whatever the last QKV launch left in qk_raw
+		return launch_qk_norm(d, l, 1, d->step, d->q);
 	case 10: // the sampling launch on the current logits; commits into a scratch step state
 		sample_kernel<<<1, SMP_THREADS, 0, d->stream>>>(d->logits, c.vocab_size, d->smp_params, d->smp_u, 1,
 		                                                d->smp_step, nullptr, 0, nullptr, nullptr);
@@ -2221,8 +2304,9 @@ static int time_loop(yalm_decoder_s *d, int kernel_id, int iters, bool bump, boo
 }
 
 extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms) {
-	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 10 && kernel_id != 7,
-	       "bad argument (kernel ids 0-6, 8, 9, 10)");
+	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 11 && kernel_id != 7,
+	       "bad argument (kernel ids 0-6, 8, 9, 10, 11)");
+	ARGCHK(kernel_id != 11 || !d->gq.empty(), "kernel 11 (q / k norm) needs yalm_decoder_set_qk_norm");
 	ARGCHK(kernel_id != 10 || (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
 	       "kernel 10 (device sampling) needs a one-GPU decoder and a vocabulary of at most 131072");
 	ARGCHK(kernel_id != 9 || d->moe_E > 0, "kernel 9 (expert router) needs a mixture-of-experts decoder");
@@ -2271,7 +2355,7 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 	std::string s;
 	switch (kernel_id) {
 	case 0:
-		s = gk + (d->bq.empty() ? ", PQKV<" : ", PQKVB<");
+		s = gk + (!d->gq.empty() ? ", PQKVN<" : d->bq.empty() ? ", PQKV<" : ", PQKVB<");
 		break;
 	case 1:
 		s = "attn_decode_kernel<";
@@ -2297,6 +2381,9 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 		break;
 	case 10:
 		s = "sample_kernel";
+		break;
+	case 11:
+		s = d->gq.empty() ? "" : "qk_norm_rope_kernel<";
 		break;
 	default:
 		s = "";

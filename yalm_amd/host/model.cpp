@@ -67,6 +67,12 @@ void Config::from_yalm(YALMData &yalm, int context) {
 	qkv_bias = !(qb.empty() || qb == "0" || qb == "False" || qb == "false");
 	if (qkv_bias && n_experts > 0)
 		throw std::runtime_error("FATAL: a q / k / v bias has no mixture-of-experts form");
+	const std::string qn = md.value("qk_norm", "0");
+	qk_norm = !(qn.empty() || qn == "0" || qn == "False" || qn == "false");
+	if (qk_norm && n_experts > 0)
+		throw std::runtime_error("FATAL: the q / k norm has no mixture-of-experts form");
+	if (qk_norm && qkv_bias)
+		throw std::runtime_error("FATAL: the q / k norm does not run together with a q / k / v bias");
 	rope_scaling = yalm_rope_scaling{};
 	if (md.contains("rope_scaling_type")) {
 		if (md.at("rope_scaling_type").as_string() != "llama3")
@@ -101,6 +107,8 @@ size_t Config::active_bytes(size_t pos) const {
 	per_block += (size_t)dim * rb_q;
 	if (qkv_bias)
 		per_block += (q_dim + 2 * (size_t)n_kv_heads * head_dim) * sizeof(float);
+	if (qk_norm)
+		per_block += 2 * (size_t)head_dim * sizeof(float);
 	if (n_experts > 0) { // model.cpp:85-87: the router and the active experts
 		per_block += (size_t)n_experts * rb_dim;
 		per_block += (size_t)n_experts_active * (2 * hidden_dim * rb_dim + dim * rb_h);
@@ -206,6 +214,12 @@ void Block::set_qkv_bias(const Tensor *bq, const Tensor *bk, const Tensor *bv) {
 	_bias[2] = check_tensor(bv, DType::F32, {c.n_kv_heads * c.head_dim, 0, 0, 0});
 }
 
+void Block::set_qk_norm(const Tensor *gq, const Tensor *gk) {
+	const Config &c = *_config;
+	_qk_norm[0] = check_tensor(gq, DType::F32, {c.head_dim, 0, 0, 0});
+	_qk_norm[1] = check_tensor(gk, DType::F32, {c.head_dim, 0, 0, 0});
+}
+
 Block::~Block() {
 	for (void *p : _owned)
 		yalm_free(p);
@@ -243,6 +257,10 @@ void Block::cuda() {
 		_bias[1] = upload(_owned, _bias[1], kv_dim * sizeof(float));
 		_bias[2] = upload(_owned, _bias[2], kv_dim * sizeof(float));
 	}
+	if (_qk_norm[0]) {
+		_qk_norm[0] = upload(_owned, _qk_norm[0], c.head_dim * sizeof(float));
+		_qk_norm[1] = upload(_owned, _qk_norm[1], c.head_dim * sizeof(float));
+	}
 	_device = Device::HIP;
 	// The KV cache is allocated (zeroed) by the decoder in HBM: no host copy
 	// to upload (model.cpp:208-210 uploads a zero host array).
@@ -279,6 +297,8 @@ Model::Model(YALMData &yalm, int context) {
 		if (c.qkv_bias)
 			blocks.back()->set_qkv_bias(get_tensor(yalm, p + "attn.wq.bias"), get_tensor(yalm, p + "attn.wk.bias"),
 			                            get_tensor(yalm, p + "attn.wv.bias"));
+		if (c.qk_norm)
+			blocks.back()->set_qk_norm(get_tensor(yalm, p + "attn.q_norm.weight"), get_tensor(yalm, p + "attn.k_norm.weight"));
 	}
 	rms_final_weight = check_tensor(get_tensor(yalm, "model.norm.weight"), DType::F32, {c.dim, 0, 0, 0});
 	_tied = yalm.tensors.count("model.output.weight") == 0;
@@ -337,6 +357,13 @@ void Model::ensure_decoder(InferenceState &s) {
 			for (int i = 0; i < 3; ++i)
 				b[i].push_back(blk->bias(i));
 		check(yalm_decoder_set_qkv_bias(s._decoder, b[0].data(), b[1].data(), b[2].data()), "qkv bias");
+	}
+	if (config->qk_norm) {
+		std::vector<const float *> g[2];
+		for (auto &blk : blocks)
+			for (int i = 0; i < 2; ++i)
+				g[i].push_back(blk->qk_norm(i));
+		check(yalm_decoder_set_qk_norm(s._decoder, g[0].data(), g[1].data()), "q / k norm");
 	}
 }
 

@@ -47,6 +47,9 @@ struct Config {
 	// attn.{wq,wk,wv}.bias, F32) and the Llama-3.1 / 3.2 "llama3" RoPE scaling
 	bool qkv_bias = false;
 	yalm_rope_scaling rope_scaling{};
+	// ... and the per-head RMSNorm on q and k ahead of RoPE (Qwen3; tensors
+	// attn.{q_norm,k_norm}.weight, F32 of head_dim)
+	bool qk_norm = false;
 
 	// model.cpp:17-75 (max_seq_len = min(meta, 4096) unless context != 0)
 	void from_yalm(YALMData &yalm, int context = 0);
@@ -102,6 +105,9 @@ struct Block {
 	// the layer's q / k / v bias (Config::qkv_bias): checked F32 vectors, uploaded by cuda()
 	void set_qkv_bias(const Tensor *bq, const Tensor *bk, const Tensor *bv);
 	const float *bias(int i) const { return (const float *)_bias[i]; } // 0 q, 1 k, 2 v; null without a bias
+	// the layer's q / k norm weights (Config::qk_norm): checked F32 vectors of head_dim, uploaded by cuda()
+	void set_qk_norm(const Tensor *gq, const Tensor *gk);
+	const float *qk_norm(int i) const { return (const float *)_qk_norm[i]; } // 0 q, 1 k; null without the norm
 
 private:
 	int _layer_i = 0;
@@ -111,6 +117,7 @@ private:
 	const void *_wq = nullptr, *_wk = nullptr, *_wv = nullptr, *_wo = nullptr, *_w1 = nullptr, *_w2 = nullptr,
 	           *_w3 = nullptr;
 	const void *_bias[3] = {nullptr, nullptr, nullptr};
+	const void *_qk_norm[2] = {nullptr, nullptr};
 	const void *_moegate = nullptr; // with experts, _w1 / _w2 / _w3 are the stacked (n_experts, ...) tensors
 	std::vector<void *> _owned;
 };

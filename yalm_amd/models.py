@@ -64,6 +64,9 @@ class ModelConfig:
     # Llama-3.1 / 3.2 "llama3" RoPE scaling: (type, factor, low_freq_factor, high_freq_factor,
     # original_max_position) with type "llama3", or None (rope_inv_freq has the rule)
     rope_scaling: tuple | None = None
+    # Qwen3: an RMSNorm over each head of q and of k ahead of RoPE (f32 tensors
+    # attn.{q_norm,k_norm}.weight of head_dim elements, shared by the layer's heads)
+    qk_norm: bool = False
 
     def __post_init__(self):
         if not self.rotary_dim:
@@ -92,6 +95,8 @@ class ModelConfig:
         per_layer += self.dim * rb_q  # wo
         if self.qkv_bias:
             per_layer += (self.q_dim + 2 * self.kv_dim) * 4  # f32 q / k / v bias
+        if self.qk_norm:
+            per_layer += 2 * self.head_dim * 4  # f32 q / k norm weights
         if self.n_experts > 0:  # model.cpp:85-87: the router + the active experts
             per_layer += self.n_experts * rb_dim
             per_layer += self.n_experts_active * (2 * self.hidden_dim * rb_dim + self.dim * rb_h)
@@ -132,8 +137,12 @@ class ModelConfig:
             md["n_experts_active"] = str(self.n_experts_active)
         if self.n_experts == 0 and (self.qkv_bias or self.rope_scaling is not None):
             md["arch"] = "Qwen2ForCausalLM" if self.qkv_bias else "LlamaForCausalLM"
-        if self.qkv_bias:  # this engine's own keys (the reference reads neither form)
+        if self.n_experts == 0 and self.qk_norm:
+            md["arch"] = "Qwen3ForCausalLM"
+        if self.qkv_bias:  # this engine's own keys (the reference reads none of these forms)
             md["qkv_bias"] = "1"
+        if self.qk_norm:
+            md["qk_norm"] = "1"
         if self.rope_scaling is not None:
             md.update(rope_scaling_metadata(self.rope_scaling))
         return md
@@ -200,6 +209,7 @@ def config_from_metadata(md: dict, context: int = 0, tied: bool = False) -> Mode
         n_experts_active=int(md.get("n_experts_active", "0")),
         qkv_bias=md.get("qkv_bias", "0") not in ("0", "False", "false", ""),
         rope_scaling=rope_scaling_from_metadata(md),
+        qk_norm=md.get("qk_norm", "0") not in ("0", "False", "false", ""),
     )
 
 
@@ -211,6 +221,12 @@ MISTRAL_7B = ModelConfig(
 LLAMA_32_3B = ModelConfig(
     dim=3072, hidden_dim=8192, head_dim=128, n_layers=28, n_heads=24, n_kv_heads=8, vocab_size=128256,
     max_seq_len=4096, rope_theta=5e5, norm_eps=1e-5, act=SILU, weight_dtype=F16, tied=True,
+)
+# Qwen3-8B: the Llama block plus the q / k norm; every dimension a whole number of fp16, fp8
+# and q4 chunks, an 8 KiB Wo row (the row-block GEMVs and the fused attention + Wo launch run)
+QWEN3_8B = ModelConfig(
+    dim=4096, hidden_dim=12288, head_dim=128, n_layers=36, n_heads=32, n_kv_heads=8, vocab_size=151936,
+    max_seq_len=4096, rope_theta=1e6, norm_eps=1e-6, act=SILU, weight_dtype=F16, tied=False, qk_norm=True,
 )
 TINY = ModelConfig(
     dim=64, hidden_dim=128, head_dim=16, n_layers=2, n_heads=4, n_kv_heads=2, vocab_size=384, max_seq_len=64,
@@ -224,7 +240,7 @@ SMALL = ModelConfig(
 MIXTRAL_8X7B = MISTRAL_7B.with_(n_experts=8, n_experts_active=2)
 TINY_MOE = TINY.with_(n_experts=4, n_experts_active=2)
 SMALL_MOE = SMALL.with_(n_experts=8, n_experts_active=2)
-PRESETS = {"mistral-7b": MISTRAL_7B, "llama-3.2-3b": LLAMA_32_3B, "tiny": TINY, "small": SMALL,
+PRESETS = {"mistral-7b": MISTRAL_7B, "llama-3.2-3b": LLAMA_32_3B, "qwen3-8b": QWEN3_8B, "tiny": TINY, "small": SMALL,
            "mixtral-8x7b": MIXTRAL_8X7B, "tiny-moe": TINY_MOE, "small-moe": SMALL_MOE}
 
 
@@ -249,6 +265,12 @@ def bias_names(l: int) -> dict:
     return {"bq": p + "wq.bias", "bk": p + "wk.bias", "bv": p + "wv.bias"}
 
 
+def qk_norm_names(l: int) -> dict:
+    """The q / k norm weights of layer l (ModelConfig.qk_norm), 1-D F32 of head_dim."""
+    p = f"model.layers.{l}.attn."
+    return {"gq": p + "q_norm.weight", "gk": p + "k_norm.weight"}
+
+
 def moegate_name(l: int) -> str:
     return f"model.layers.{l}.moegate.weight"
 
@@ -271,6 +293,10 @@ def tensor_shapes(c: ModelConfig) -> dict:
             out[b["bq"]] = ((c.q_dim,), True)
             out[b["bk"]] = ((c.kv_dim,), True)
             out[b["bv"]] = ((c.kv_dim,), True)
+        if c.qk_norm:
+            g = qk_norm_names(l)
+            out[g["gq"]] = ((c.head_dim,), True)
+            out[g["gk"]] = ((c.head_dim,), True)
         e = (c.n_experts,) if c.n_experts > 0 else ()  # model.cpp:160-164: stacked per expert
         if e:
             out[moegate_name(l)] = ((c.n_experts, c.dim), False)
@@ -336,6 +362,9 @@ NORM_SCALE, NORM_OFFSET = 0.2, 1.0
 # with these weights (trained Qwen2.5 biases reach tens), so a model run without its bias is
 # unmistakably another model: its logits move by 1e-2 of their range or more at every shape tested
 BIAS_SCALE = 4.0
+# synthetic q / k norm weights, uniform [0.5, 2.5): trained ones are far from 1, and at the other
+# norms' [0.8, 1.2) a kernel that exchanged gq and gk moved TINY's logits by only 1.3e-2
+QKNORM_SCALE, QKNORM_OFFSET = 1.0, 1.5
 
 
 def synth_seed(base: int, name: str) -> int:
@@ -355,6 +384,8 @@ def synth_params(name: str, is_norm: bool, peak: float = 1.0, real: "Realistic" 
         peak = peak * real.final_norm
     if name.endswith(".bias"):  # q / k / v bias: the size of the projections' own outputs
         return BIAS_SCALE, 0.0
+    if name.endswith((".attn.q_norm.weight", ".attn.k_norm.weight")):
+        return QKNORM_SCALE, QKNORM_OFFSET
     if is_norm:
         k = peak if name == "model.norm.weight" else 1.0
         return NORM_SCALE * k, NORM_OFFSET * k

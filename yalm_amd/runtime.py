@@ -184,6 +184,7 @@ _sig("yalm_spec_draft", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 _sig("yalm_decoder_set_rope_scaling", c_int, [c_void_p, ctypes.POINTER(RopeScaling)])
 _sig("yalm_decoder_get_inv_freq", c_int, [c_void_p, c_void_p])
 _sig("yalm_decoder_set_qkv_bias", c_int, [c_void_p, c_void_p, c_void_p, c_void_p])
+_sig("yalm_decoder_set_qk_norm", c_int, [c_void_p, c_void_p, c_void_p])
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -202,6 +203,7 @@ EXPORTED = [
     "yalm_row_bytes", "yalm_synth_q4",
     "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
     "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
+    "yalm_decoder_set_qk_norm",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -615,6 +617,8 @@ class Decoder:
             self.set_rope_scaling(self.cfg.rope_scaling)
         if self.cfg.qkv_bias:
             self.set_qkv_bias(True)
+        if self.cfg.qk_norm:
+            self.set_qk_norm(True)
 
     def set_rope_scaling(self, rs) -> None:
         """yalm_decoder_set_rope_scaling: rs as ModelConfig.rope_scaling, a RopeScaling (passed as it
@@ -637,6 +641,16 @@ class Decoder:
         names = [M.bias_names(l) for l in range(L)]
         self._bias = [(c_void_p * L)(*[self.model.ptrs[n[k]] for n in names]) for k in ("bq", "bk", "bv")]
         check(lib.yalm_decoder_set_qkv_bias(self.h, *self._bias))
+
+    def set_qk_norm(self, on: bool = True) -> None:
+        """yalm_decoder_set_qk_norm with the model's attn.{q_norm,k_norm}.weight tensors, or off."""
+        if not on:
+            check(lib.yalm_decoder_set_qk_norm(self.h, None, None))
+            return
+        L = self.cfg.n_layers
+        names = [M.qk_norm_names(l) for l in range(L)]
+        self._qk_norm = [(c_void_p * L)(*[self.model.ptrs[n[k]] for n in names]) for k in ("gq", "gk")]
+        check(lib.yalm_decoder_set_qk_norm(self.h, *self._qk_norm))
 
     def set_launch(self, flags: int) -> None:
         """yalm_decoder_set_launch: LAUNCH_EAGER | LAUNCH_SYNC | LAUNCH_SEPARATE_ATTN_WO (0 = default)."""
