@@ -108,7 +108,8 @@ def _attn_ref(q, kc, vc, T, pos0, nh, nkv, D):
 
 
 @pytest.mark.parametrize("T,pos0", [(1, 0), (37, 0), (128, 0), (200, 0), (70, 50)])
-@pytest.mark.parametrize("nh,nkv,D", [(8, 2, 64), (4, 4, 128), (6, 2, 128)])
+@pytest.mark.parametrize("nh,nkv,D", [(8, 2, 64), (4, 4, 128), (6, 2, 128),
+                                      (14, 2, 64), (10, 2, 128), (12, 2, 128)])  # G = 7, 5, 6 (Qwen2.5 / Qwen3)
 def test_attn_prefill(T, pos0, nh, nkv, D):
     rng = np.random.default_rng(T * 31 + pos0 + D)
     q = rng.standard_normal((T, nh * D)).astype(np.float16)
