@@ -528,6 +528,28 @@ int yalm_spec_draft(const int *history, int m, int rows, int ngram_max, int ngra
 /* Host pointers in and out; synchronous. dtype selects the weight type
  * (matmul_cuda<float|half|uint8_t>; YALM_Q4: w is d rows of yalm_row_bytes(YALM_Q4, n)). */
 int yalm_matmul(float *xout, const float *x, const void *w, int n, int d, int dtype);
+/* The geometry of one multi-row GEMV launch (gemv_rows.h: every weight matrix of yalm_forward_rows
+ * and of the speculative verify step) over rows of n elements, n_groups wave groups (pairs of
+ * output rows; GLU: one w1 / w3 row pair each) and T = 1..4 activation rows on `cus` CUs (0 =
+ * this device's): kseg floats of x staged per row and segment (a whole number of the type's
+ * 64-lane chunks, T * kseg * 4 <= 128 KiB), nseg segments, gpw groups per wave (1 when
+ * segmented), the grid and the dynamic LDS bytes. Pure host arithmetic with cus > 0; outputs may
+ * be NULL. YALM_ERR_UNSUPPORTED for YALM_Q4. */
+int yalm_rows_plan(int dtype, int n, int n_groups, int T, int cus, int *kseg, int *nseg, int *gpw, int *blocks,
+                   size_t *lds);
+/* One multi-row GEMV launch, the decoder's own, at the plan of yalm_rows_plan: x [T][xstride]
+ * (row t's n elements first), w d rows of n elements, out [T][ostride], uploaded as given and
+ * returned whole (what the kernel does not write comes back as it went in). normw (n floats)
+ * non-NULL: each x row is rmsnorm'ed with eps while it is staged. epilogue YALM_ROWS_STORE: out[t][j] =
+ * w[j] . x[t]; YALM_ROWS_RESIDUAL: out[t][j] += w[j] . x[t]; YALM_ROWS_GLU: out[t][j] =
+ * act(w[j] . x[t]) * (w3[j] . x[t]) (w3 and act are ignored otherwise). YALM_ERR_ARG: T outside
+ * 1..4, n no multiple of 16, a stride below its row's length or no multiple of 4;
+ * YALM_ERR_UNSUPPORTED for YALM_Q4. */
+#define YALM_ROWS_STORE 0
+#define YALM_ROWS_RESIDUAL 1
+#define YALM_ROWS_GLU 2
+int yalm_matmul_rows(float *out, const float *x, const void *w, const void *w3, const float *normw, float eps, int T,
+                     int n, int d, int xstride, int ostride, int dtype, int epilogue, int act);
 /* mha_cuda: xout (n_heads, head_dim), att (n_heads, max_seq_len) softmax
  * probabilities for t < kv_len. */
 int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint16_t *vb, const float *q, int head_dim, int kv_len,

@@ -1776,10 +1776,11 @@ extern "C" int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_s
 
 // ------------------------------------------------------------------ multi-row forward, speculative greedy decode
 // (gemv_rows.h, spec.h) Dense decoders on one GPU, f32 / f16 / fp8 weights.
+static const char *const ROWS_Q4_WHY = ": q4 weights have no multi-row form (gemv_rows.h streams element-typed rows)";
 static int rows_supported(const yalm_decoder_s *d, const char *who) {
 	const char *why = nullptr;
 	if (d->c.weight_dtype == YALM_Q4)
-		why = ": q4 weights have no multi-row form (gemv_rows.h streams element-typed rows)";
+		why = ROWS_Q4_WHY;
 	else if (d->moe_E > 0)
 		why = ": mixture-of-experts decoders have no multi-row form (each row routes to its own experts)";
 	else if (d->tp_size > 1 || d->comm || d->ipc)
@@ -1811,18 +1812,55 @@ static int rows_init(yalm_decoder_s *d) {
 	return YALM_OK;
 }
 
-// One launch of gemv_rows_kernel: x staged whole when T rows of it fit ROWS_X_BYTES (then a wave
-// takes several groups, about one workgroup per CU), else by K segments with one group per wave.
+// The geometry of one gemv_rows_kernel launch over rows of n elements in chunks of CH, n_groups
+// groups and T activation rows on `cus` CUs: x staged whole when T rows of it fit ROWS_X_BYTES
+// (then a wave takes several groups, about one workgroup per CU), else by K segments with one
+// group per wave. Pure host arithmetic.
+struct RowsPlan {
+	int kseg, nseg, gpw, blocks;
+	size_t lds;
+};
+static RowsPlan rows_plan(int CH, int n, int n_groups, int T, int cus) {
+	constexpr int W = ROWS_THREADS / YALM_WAVE;
+	RowsPlan r;
+	const int kcap = (int)(ROWS_X_BYTES / sizeof(float)) / T / CH * CH;
+	r.kseg = std::min((n + CH - 1) / CH * CH, kcap);
+	r.nseg = (n + r.kseg - 1) / r.kseg;
+	r.gpw = r.nseg > 1 ? 1 : std::max(1, n_groups / (W * cus));
+	r.blocks = (n_groups + W * r.gpw - 1) / (W * r.gpw);
+	r.lds = ((size_t)T * r.kseg + (size_t)T * 16) * sizeof(float);
+	return r;
+}
+
+extern "C" int yalm_rows_plan(int dtype, int n, int n_groups, int T, int cus, int *kseg, int *nseg, int *gpw,
+                              int *blocks, size_t *lds) {
+	if (dtype == YALM_Q4) {
+		set_err(std::string("yalm_rows_plan") + ROWS_Q4_WHY);
+		return YALM_ERR_UNSUPPORTED;
+	}
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_rows_plan: bad dtype");
+	ARGCHK(n > 0 && n_groups > 0 && cus >= 0 && T >= 1 && T <= ROWS_MAX_T, "yalm_rows_plan: bad argument");
+	const int EPL = dtype == YALM_F32 ? WF32::EPL : dtype == YALM_F16 ? WF16::EPL : WF8::EPL;
+	const RowsPlan r = rows_plan(YALM_WAVE * EPL, n, n_groups, T, cus ? cus : device_cu_count());
+	if (kseg)
+		*kseg = r.kseg;
+	if (nseg)
+		*nseg = r.nseg;
+	if (gpw)
+		*gpw = r.gpw;
+	if (blocks)
+		*blocks = r.blocks;
+	if (lds)
+		*lds = r.lds;
+	return YALM_OK;
+}
+
+// One launch of gemv_rows_kernel at the geometry of rows_plan.
 template <class WT, class P, bool NORM>
 static int launch_rows(const P &p, const float *x, int xstride, const float *normw, float eps, int T, hipStream_t st) {
-	constexpr int CH = YALM_WAVE * WT::EPL;
-	constexpr int W = ROWS_THREADS / YALM_WAVE;
-	const int kcap = (int)(ROWS_X_BYTES / sizeof(float)) / T / CH * CH;
-	const int kseg = std::min((p.n + CH - 1) / CH * CH, kcap);
-	const int nseg = (p.n + kseg - 1) / kseg;
-	const int gpw = nseg > 1 ? 1 : std::max(1, p.n_groups / (W * device_cu_count()));
-	const int blocks = (p.n_groups + W * gpw - 1) / (W * gpw);
-	const size_t lds = ((size_t)T * kseg + (size_t)T * 16) * sizeof(float);
+	const RowsPlan pl = rows_plan(YALM_WAVE * WT::EPL, p.n, p.n_groups, T, device_cu_count());
+	const int kseg = pl.kseg, gpw = pl.gpw, blocks = pl.blocks;
+	const size_t lds = pl.lds;
 	auto kern = T == 1   ? gemv_rows_kernel<WT, P, 1, NORM>
 	            : T == 2 ? gemv_rows_kernel<WT, P, 2, NORM>
 	            : T == 3 ? gemv_rows_kernel<WT, P, 3, NORM>
@@ -2524,6 +2562,64 @@ extern "C" int yalm_matmul(float *xout, const float *x, const void *w, int n, in
 	TRY(DISPATCH_WT(dtype, matmul_t, (float *)dout.p, (const float *)dx.p, dw.p, n, d));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(xout, dout.p, sizeof(float) * d, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+// One launch_rows call (the decoder's own) over device buffers; NORM on with a norm weight.
+template <class WT, class P>
+static int matmul_rows_launch(const P &p, const float *x, int xstride, const float *normw, float eps, int T) {
+	return normw ? launch_rows<WT, P, true>(p, x, xstride, normw, eps, T, nullptr)
+	             : launch_rows<WT, P, false>(p, x, xstride, nullptr, 0.f, T, nullptr);
+}
+template <class WT>
+static int matmul_rows_t(float *out, const float *x, const void *w, const void *w3, const float *normw, float eps,
+                         int T, int n, int d, int xstride, int ostride, int epilogue, int act) {
+	if (epilogue == YALM_ROWS_GLU) {
+		if (act == YALM_SILU) {
+			RGlu<WT, 1> p{(const char *)w, (const char *)w3, n, d, out, ostride};
+			return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
+		}
+		RGlu<WT, 0> p{(const char *)w, (const char *)w3, n, d, out, ostride};
+		return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
+	}
+	if (epilogue == YALM_ROWS_RESIDUAL) {
+		RResidual<WT> p{(const char *)w, n, d, (d + 1) / 2, out, ostride};
+		return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
+	}
+	RStore<WT> p{(const char *)w, n, d, (d + 1) / 2, out, ostride};
+	return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
+}
+
+extern "C" int yalm_matmul_rows(float *out, const float *x, const void *w, const void *w3, const float *normw,
+                                float eps, int T, int n, int d, int xstride, int ostride, int dtype, int epilogue,
+                                int act) {
+	if (dtype == YALM_Q4) {
+		set_err(std::string("yalm_matmul_rows") + ROWS_Q4_WHY);
+		return YALM_ERR_UNSUPPORTED;
+	}
+	ARGCHK(out && x && w && n > 0 && d > 0, "yalm_matmul_rows: bad argument");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_matmul_rows: bad dtype");
+	ARGCHK(T >= 1 && T <= ROWS_MAX_T, "yalm_matmul_rows: 1 <= T <= 4 rows");
+	ARGCHK(n % 16 == 0, "yalm_matmul_rows: n must be a multiple of 16 (infer.cpp:66)");
+	ARGCHK(xstride >= n && xstride % 4 == 0, "yalm_matmul_rows: xstride must be at least n and a multiple of 4");
+	ARGCHK(ostride >= d && ostride % 4 == 0, "yalm_matmul_rows: ostride must be at least d and a multiple of 4");
+	ARGCHK(epilogue == YALM_ROWS_STORE || epilogue == YALM_ROWS_RESIDUAL || epilogue == YALM_ROWS_GLU,
+	       "yalm_matmul_rows: bad epilogue");
+	ARGCHK(epilogue != YALM_ROWS_GLU || (w3 && (act == YALM_SILU || act == YALM_GELU)),
+	       "yalm_matmul_rows: the GLU epilogue needs w3 and act GELU or SILU");
+	const size_t wb = yalm_row_bytes(dtype, n) * (size_t)d;
+	DevBuf dx, dw, dw3, dn, dout;
+	TRY(up(dx, x, sizeof(float) * (size_t)T * xstride));
+	TRY(up(dw, w, wb));
+	if (epilogue == YALM_ROWS_GLU)
+		TRY(up(dw3, w3, wb));
+	if (normw)
+		TRY(up(dn, normw, sizeof(float) * n));
+	TRY(up(dout, out, sizeof(float) * (size_t)T * ostride));
+	TRY(DISPATCH_WT_EL(dtype, matmul_rows_t, (float *)dout.p, (const float *)dx.p, dw.p, dw3.p, (const float *)dn.p, eps,
+	                   T, n, d, xstride, ostride, epilogue, act));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(out, dout.p, sizeof(float) * (size_t)T * ostride, hipMemcpyDeviceToHost));
 	return YALM_OK;
 }
 

@@ -185,6 +185,8 @@ _sig("yalm_decoder_set_rope_scaling", c_int, [c_void_p, ctypes.POINTER(RopeScali
 _sig("yalm_decoder_get_inv_freq", c_int, [c_void_p, c_void_p])
 _sig("yalm_decoder_set_qkv_bias", c_int, [c_void_p, c_void_p, c_void_p, c_void_p])
 _sig("yalm_decoder_set_qk_norm", c_int, [c_void_p, c_void_p, c_void_p])
+_sig("yalm_rows_plan", c_int, [c_int] * 5 + [ctypes.POINTER(c_int)] * 4 + [ctypes.POINTER(c_size_t)])
+_sig("yalm_matmul_rows", c_int, [c_void_p] * 5 + [c_float] + [c_int] * 8)
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -204,6 +206,7 @@ EXPORTED = [
     "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
     "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
     "yalm_decoder_set_qk_norm",
+    "yalm_rows_plan", "yalm_matmul_rows",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -397,6 +400,41 @@ def attn_wo_plan(cfg: M.ModelConfig, slots: int):
     s, g = c_int(), c_int()
     ok = lib.yalm_attn_wo_plan(ctypes.byref(c), slots, ctypes.byref(s), ctypes.byref(g))
     return bool(ok), s.value, g.value
+
+
+ROWS_STORE, ROWS_RESIDUAL, ROWS_GLU = 0, 1, 2  # yalm_matmul_rows epilogues
+
+
+def rows_plan(dtype: int, n: int, n_groups: int, T: int, cus: int = 0) -> dict:
+    """kseg, nseg, gpw, blocks and lds of one multi-row GEMV launch (yalm_rows_plan: host
+    arithmetic; cus = 0 asks for this device's CU count)."""
+    k, s, g, b, l = c_int(), c_int(), c_int(), c_int(), c_size_t()
+    check(lib.yalm_rows_plan(dtype, n, n_groups, T, cus, ctypes.byref(k), ctypes.byref(s), ctypes.byref(g),
+                             ctypes.byref(b), ctypes.byref(l)))
+    return dict(kseg=k.value, nseg=s.value, gpw=g.value, blocks=b.value, lds=l.value)
+
+
+def matmul_rows(out, x, w, dtype: int, epilogue: int = ROWS_STORE, w3=None, normw=None, eps: float = 0.0,
+                act: int = M.SILU, n=None) -> np.ndarray:
+    """One multi-row GEMV launch (yalm_matmul_rows): x (T, xstride) f32, w (d, n) stored weights
+    (w3 too for ROWS_GLU), out (T, ostride) f32 as it stands before the launch (sentinels, the
+    residual's start). n defaults to w's row length. Returns the whole out after the launch; the
+    argument is not written."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    out = np.array(out, dtype=np.float32, order="C")
+    w = np.ascontiguousarray(w)
+    d = w.shape[0]
+    n = w.shape[1] if n is None else n
+    w3 = None if w3 is None else np.ascontiguousarray(w3)
+    normw = None if normw is None else np.ascontiguousarray(normw, dtype=np.float32)
+    T = x.shape[0]
+    assert x.ndim == 2 and out.ndim == 2 and out.shape[0] == T
+    assert w3 is None or w3.shape == w.shape
+    assert normw is None or normw.size == n
+    check(lib.yalm_matmul_rows(_ptr(out), _ptr(x), _ptr(w), None if w3 is None else _ptr(w3),
+                               None if normw is None else _ptr(normw), eps, T, n, d, x.shape[1], out.shape[1], dtype,
+                               epilogue, act))
+    return out
 
 
 def attn_prefill(q, kc, vc, T, pos0, n_heads, n_kv_heads, head_dim) -> np.ndarray:
