@@ -600,6 +600,15 @@ int yalm_moe_ffn_rows(float *xout, int *experts, float *weights, const float *x,
  * o [T][n_heads * head_dim] f16 (infer.cpp:216-248 per row and head). */
 int yalm_attn_prefill(uint16_t *o, const uint16_t *q, const uint16_t *kc, const uint16_t *vc, int T, int pos0,
                       int n_heads, int n_kv_heads, int head_dim);
+/* The same launch as a decoder's prefill makes, with the buffers a decoder has around it:
+ * kc / vc are [cache_rows][n_kv_heads * head_dim] with cache_rows >= pos0 + T (rows past
+ * pos0 + T are stale cache the kernel must not read), o is [o_rows][W] with o_rows >= T; its
+ * incoming content is uploaded first and all o_rows rows come back (rows past T must return
+ * untouched). W = n_heads * head_dim, or twice that when split != 0: the split-operand form,
+ * q is [T][W] too, and the rows of q and o are f16 [hi | lo] halves. YALM_ERR_ARG on a bad
+ * argument. */
+int yalm_attn_prefill_rows(uint16_t *o, int o_rows, const uint16_t *q, const uint16_t *kc, const uint16_t *vc,
+                           int cache_rows, int T, int pos0, int n_heads, int n_kv_heads, int head_dim, int split);
 
 #ifdef __cplusplus
 }

@@ -304,6 +304,11 @@ __global__ __launch_bounds__(THREADS) void attn_prefill_kernel(const uint16_t *_
 #pragma unroll
 				for (int e = 0; e < 4; ++e) {
 					v[e] = o[jd][4 * r4 + e] * inv;
+					// SPLIT: hi and lo must split one value. Left visible, the product is contracted
+					// into the conversions (v_fma_mix: f16(o * inv) in one rounding) for lo's hi but
+					// not for the stored hi, and the two differ by an f16 ulp when v is near a tie.
+					if constexpr (SPLIT)
+						asm volatile("" : "+v"(v[e]));
 					hb[e] = f2h_bits(v[e]);
 				}
 				*(uint2 *)(op + d) = make_uint2(hb[0] | ((uint32_t)hb[1] << 16), hb[2] | ((uint32_t)hb[3] << 16));

@@ -1190,19 +1190,29 @@ extern "C" int yalm_moe_ffn_rows(float *xout, int *experts, float *weights, cons
 	return YALM_OK;
 }
 
-extern "C" int yalm_attn_prefill(uint16_t *o, const uint16_t *q, const uint16_t *kc, const uint16_t *vc, int T,
-                                 int pos0, int n_heads, int n_kv_heads, int head_dim) {
-	ARGCHK(o && q && kc && vc && T > 0 && pos0 >= 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0,
-	       "yalm_attn_prefill: bad argument");
-	const size_t q_dim = (size_t)n_heads * head_dim, kv = (size_t)(pos0 + T) * n_kv_heads * head_dim;
+extern "C" int yalm_attn_prefill_rows(uint16_t *o, int o_rows, const uint16_t *q, const uint16_t *kc,
+                                      const uint16_t *vc, int cache_rows, int T, int pos0, int n_heads, int n_kv_heads,
+                                      int head_dim, int split) {
+	ARGCHK(o && q && kc && vc && T > 0 && pos0 >= 0 && n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 &&
+	           head_dim > 0,
+	       "yalm_attn_prefill_rows: bad argument");
+	ARGCHK(o_rows >= T && (long long)cache_rows >= (long long)pos0 + T && (split == 0 || split == 1),
+	       "yalm_attn_prefill_rows: o_rows >= T, cache_rows >= pos0 + T, split 0 or 1");
+	const size_t w = (size_t)n_heads * head_dim * (split ? 2 : 1), kv = (size_t)cache_rows * n_kv_heads * head_dim;
 	HostDev dq, dk, dv, dout;
-	TRY(hd(dq, q, T * q_dim * 2));
+	TRY(hd(dq, q, T * w * 2));
 	TRY(hd(dk, kc, kv * 2));
 	TRY(hd(dv, vc, kv * 2));
-	TRY(hd(dout, nullptr, T * q_dim * 2));
+	TRY(hd(dout, o, o_rows * w * 2));
 	TRY(launch_attn_prefill((const uint16_t *)dq.p, (const uint16_t *)dk.p, (const uint16_t *)dv.p, T, pos0, n_heads,
-	                        n_kv_heads, head_dim, (uint16_t *)dout.p, nullptr));
+	                        n_kv_heads, head_dim, (uint16_t *)dout.p, nullptr, split != 0));
 	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(o, dout.p, T * q_dim * 2, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(o, dout.p, o_rows * w * 2, hipMemcpyDeviceToHost));
 	return YALM_OK;
+}
+
+extern "C" int yalm_attn_prefill(uint16_t *o, const uint16_t *q, const uint16_t *kc, const uint16_t *vc, int T,
+                                 int pos0, int n_heads, int n_kv_heads, int head_dim) {
+	ARGCHK(T > 0 && pos0 >= 0, "yalm_attn_prefill: bad argument");
+	return yalm_attn_prefill_rows(o, T, q, kc, vc, pos0 + T, T, pos0, n_heads, n_kv_heads, head_dim, 0);
 }

@@ -174,6 +174,7 @@ _sig("yalm_prefill_info", c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTE
 _sig("yalm_set_prefill_precision", c_int, [c_void_p, c_int])
 _sig("yalm_gemm_f16", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int])
 _sig("yalm_attn_prefill", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int])
+_sig("yalm_attn_prefill_rows", c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 7)
 _sig("yalm_set_prefill_forms", c_int, [c_void_p, ctypes.c_char_p])
 _sig("yalm_graph_kernels", c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
 _sig("yalm_attn_wo_plan", c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
@@ -207,6 +208,7 @@ EXPORTED = [
     "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
     "yalm_decoder_set_qk_norm",
     "yalm_rows_plan", "yalm_matmul_rows",
+    "yalm_attn_prefill_rows",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
@@ -444,6 +446,24 @@ def attn_prefill(q, kc, vc, T, pos0, n_heads, n_kv_heads, head_dim) -> np.ndarra
     vc = np.ascontiguousarray(vc, dtype=np.float16)
     o = np.zeros((T, n_heads * head_dim), np.float16)
     check(lib.yalm_attn_prefill(_ptr(o), _ptr(q), _ptr(kc), _ptr(vc), T, pos0, n_heads, n_kv_heads, head_dim))
+    return o
+
+
+def attn_prefill_rows(o, q, kc, vc, T, pos0, n_heads, n_kv_heads, head_dim, split=False) -> np.ndarray:
+    """yalm_attn_prefill_rows: the decoder's prefill attention launch with a decoder's buffers.
+    kc / vc (cache_rows >= pos0 + T, n_kv*D) f16 with whatever lies past pos0 + T; o (o_rows >= T, W)
+    f16 is uploaded as it comes and returned whole (a copy); W = n_heads*D, doubled when split:
+    q (T, W) and o are then [hi | lo]."""
+    W = n_heads * head_dim * (2 if split else 1)
+    q = np.ascontiguousarray(q, dtype=np.float16)
+    kc = np.ascontiguousarray(kc, dtype=np.float16)
+    vc = np.ascontiguousarray(vc, dtype=np.float16)
+    o = np.array(o, dtype=np.float16, order="C", copy=True)
+    if q.shape != (T, W) or o.ndim != 2 or o.shape[1] != W or kc.shape != vc.shape or kc.ndim != 2 \
+            or kc.shape[1] != n_kv_heads * head_dim:
+        raise ValueError("attn_prefill_rows: q (T, W), o (o_rows, W), kc / vc (cache_rows, n_kv*D)")
+    check(lib.yalm_attn_prefill_rows(_ptr(o), o.shape[0], _ptr(q), _ptr(kc), _ptr(vc), kc.shape[0], T, pos0, n_heads,
+                                     n_kv_heads, head_dim, int(bool(split))))
     return o
 
 
