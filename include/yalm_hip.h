@@ -52,6 +52,27 @@ enum { YALM_F32 = 0, YALM_F16 = 1, YALM_BF16 = 2, YALM_F8E5M2 = 3 };
  * yalm_decoder_create_tp, yalm_decoder_create_tp_ipc, yalm_moe_ffn, yalm_moe_ffn_rows.
  * YALM_ERR_ARG: a q4 config whose dim, hidden_dim or n_heads * head_dim is no multiple of 32. */
 enum { YALM_Q4 = 16 };
+/* ---------------- e4m3: row-scaled OCP E4M3 weights ----------------
+ * A storage format of this engine alone (code 17: outside the reference's DType range; the
+ * reference's F8E4M3 = 4 names a tensor of bare bytes, which this is not). A matrix [rows][n],
+ * n % 16 == 0, is rows rows of yalm_row_bytes(YALM_E4M3, n) = n + 16 bytes: n codes (element e
+ * at byte e), then one little-endian f32 scale s at byte n, then 12 zero bytes. A code is OCP
+ * e4m3fn, S.EEEE.MMM with bias 7: subnormals m * 2^-9, maximum 448, no infinities, 0x7F and
+ * 0xFF NaN. The value of an element is code * s. The quantiser (models.e4m3_quantize) writes
+ * s = 2^k with -15 <= k <= 7 only and never a NaN code: for exactly those k every finite code
+ * times s is an exact f16, so an e4m3 model has an exact f16 twin (models.e4m3_twin). The
+ * decode kernels do not check the scale -- any finite f32 works there -- but the twin and the
+ * prefill (whose upcast stores f16(code * s)) hold for the quantiser's scales only. Every
+ * weight matrix of an e4m3 model, the embedding included, has this layout; norms, biases and
+ * q / k norm gains stay f32. Dense one-GPU decoders only: yalm_decoder_create, yalm_forward,
+ * the greedy / sampled loops, yalm_block, yalm_forward_rows, yalm_generate_speculative,
+ * yalm_prefill (through a per-layer exact f16 upcast, as fp8), yalm_matmul, yalm_matmul_rows,
+ * yalm_ffn, yalm_time_kernel, yalm_set_gemv_config. Attention and Wo fuse where the Wo row is
+ * 4096 or 8192 codes (yalm_attn_wo_plan).
+ * YALM_ERR_UNSUPPORTED, with a yalm_last_error naming e4m3: yalm_decoder_create_moe,
+ * yalm_decoder_create_tp, yalm_decoder_create_tp_ipc, yalm_moe_ffn, yalm_moe_ffn_rows.
+ * YALM_ERR_ARG: a config whose dim, hidden_dim or n_heads * head_dim is no multiple of 16. */
+enum { YALM_E4M3 = 17 };
 /* ActivationType (model.h:14-17) */
 enum { YALM_GELU = 0, YALM_SILU = 1 };
 /* InferenceMode (model.h:28-31) */
@@ -73,7 +94,7 @@ typedef struct yalm_config {
 	float norm_eps;
 	int act;          /* YALM_GELU / YALM_SILU */
 	float qkv_clip;   /* FLT_MAX when absent (model.cpp:60-61) */
-	int weight_dtype; /* YALM_F32 / YALM_F16 / YALM_F8E5M2 / YALM_Q4 */
+	int weight_dtype; /* YALM_F32 / YALM_F16 / YALM_F8E5M2 / YALM_Q4 / YALM_E4M3 */
 } yalm_config;
 
 /* Device pointers of one block (Block private fields, model.h:286-300). If
@@ -120,8 +141,9 @@ int yalm_stream_sync(yalm_stream s);
  * Used to build random-weight models of real shapes in HBM without a PCIe
  * upload (bench.py). Same integer hash as the CPU oracle. */
 int yalm_synth(void *device, size_t n, int dtype, uint64_t seed, float scale, float offset, yalm_stream s);
-/* Bytes of one row of n elements of a weight matrix in dtype (q4: the padded row above;
- * 0 for an unknown dtype or a q4 n that is no multiple of 32). Pure host arithmetic. */
+/* Bytes of one row of n elements of a weight matrix in dtype (q4: the padded row above; e4m3:
+ * n + 16; 0 for an unknown dtype, a q4 n that is no multiple of 32 or an e4m3 n that is no
+ * multiple of 16). Pure host arithmetic. */
 size_t yalm_row_bytes(int dtype, int n);
 /* yalm_synth for a q4 tensor [rows][n], which needs the row length (yalm_synth with YALM_Q4 is
  * YALM_ERR_ARG): nibble byte i of the tensor (row-major, nibble bytes only) is bits 40..47 of
@@ -129,6 +151,12 @@ size_t yalm_row_bytes(int dtype, int n);
  * nearest the f32 quotient, bits + 4 with the low 3 cleared), padding zero; the values are
  * uniform over (u - 8) * s, about [-8 / 7 scale, scale]. models.synth_q4_array is its numpy twin. */
 int yalm_synth_q4(void *device, size_t rows, int n, uint64_t seed, float scale, yalm_stream s);
+/* yalm_synth for an e4m3 tensor [rows][n] (yalm_synth with YALM_E4M3 is YALM_ERR_ARG): code
+ * byte i of the tensor (row-major, code bytes only) is bits 40..47 of the initialiser's hash of
+ * i, with the NaN codes made finite by clearing their lowest bit (0x7F -> 0x7E, 0xFF -> 0xFE);
+ * every row's scale is 2^k for the smallest k in [-15, 7] with 448 * 2^k >= scale (7 if none),
+ * the padding zero. models.synth_e4m3_array is its numpy twin. */
+int yalm_synth_e4m3(void *device, size_t rows, int n, uint64_t seed, float scale, yalm_stream s);
 
 /* ---------------- decoder: replaces Model::_forward_cuda / Block::_block_cuda ---------------- */
 /* Creates the device state for one sequence (InferenceState::cuda,
@@ -237,7 +265,7 @@ const char *yalm_kernel_name(yalm_decoder d, int kernel_id);
 /* 1 if this decoder's launch path runs attention and the Wo projection (+ the
  * residual add) as ONE launch (attn_wo.h: the Wo weight stream overlaps the
  * attention; replaces attn + fused_matmul_add_residuals, infer.cu:338-524, 270):
- * head_dim 128, fp16 / fp8 weights with 1, 2, 4 or 8 KB (per-rank) Wo rows, and
+ * head_dim 128, fp16 / fp8 weights with 1, 2, 4 or 8 KB (per-rank) Wo rows (e4m3: 4 or 8 KB of codes), and
  * not YALM_LAUNCH_SEPARATE_ATTN_WO. 0 = two separate launches. The split-KV
  * attention output is handed to the Wo workgroups as {value, epoch} granules. */
 int yalm_decoder_attn_wo(yalm_decoder d);
@@ -419,7 +447,7 @@ int yalm_copy_2d(void *dst, size_t dst_pitch, const void *src, size_t src_pitch,
  * expects them, so yalm_forward / yalm_generate_greedy can continue at
  * pos0 + n. logprobs (host, n floats, may be NULL): logprobs[i] =
  * log softmax(logits at position pos0 + i)[tokens[i + 1]] for i < n - 1 (the
- * quantity main.cpp:155 sums), logprobs[n - 1] = 0. Requires f16 weights (fp8 and q4:
+ * quantity main.cpp:155 sums), logprobs[n - 1] = 0. Requires f16 weights (fp8, e4m3 and q4:
  * through an exact f16 upcast of one layer at a time),
  * dims multiple of 128, head_dim 64 | 128 and pos0 + n <= max_seq_len
  * (the sliding window past max_seq_len stays on the decode path).
@@ -469,7 +497,7 @@ int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms);
 int yalm_set_prefill_forms(yalm_decoder d, const char *spec);
 
 /* ---------------- multi-row forward and speculative greedy decode ----------------
- * Dense decoders on one GPU with f32, f16 or fp8 weights. YALM_ERR_UNSUPPORTED, with a
+ * Dense decoders on one GPU with f32, f16, fp8 (E5M2) or e4m3 weights. YALM_ERR_UNSUPPORTED, with a
  * yalm_last_error naming the reason: q4 weights, mixture-of-experts decoders
  * (yalm_decoder_create_moe), tensor-parallel decoders (yalm_decoder_create_tp / _tp_ipc). */
 /* T tokens (1 <= T <= 4) at positions pos .. pos + T - 1 through every layer in ONE pass over
@@ -526,7 +554,7 @@ int yalm_spec_draft(const int *history, int m, int rows, int ngram_max, int ngra
 
 /* ---------------- test API: replaces infer.cu:890-1019 (model.h:370-384) ---------------- */
 /* Host pointers in and out; synchronous. dtype selects the weight type
- * (matmul_cuda<float|half|uint8_t>; YALM_Q4: w is d rows of yalm_row_bytes(YALM_Q4, n)). */
+ * (matmul_cuda<float|half|uint8_t>; YALM_Q4 / YALM_E4M3: w is d rows of yalm_row_bytes(dtype, n)). */
 int yalm_matmul(float *xout, const float *x, const void *w, int n, int d, int dtype);
 /* The geometry of one multi-row GEMV launch (gemv_rows.h: every weight matrix of yalm_forward_rows
  * and of the speculative verify step) over rows of n elements, n_groups wave groups (pairs of

@@ -1,7 +1,7 @@
 """GEMV launch-geometry sweep (default: the row-block kernel, gpw = workgroups per CU) on the Mistral-7B-shaped synthetic model.
 Times each weight-streaming kernel (HIP events, layers rotated so weights come
 from HBM) for every (threads, unroll, gpw) candidate; prints GB/s.
-usage: python tools/sweep_gemv.py [--dtype fp16|fp8|q4] [--iters 64]"""
+usage: python tools/sweep_gemv.py [--dtype fp16|fp8|q4|e4m3] [--iters 64]"""
 import argparse
 import os
 import sys

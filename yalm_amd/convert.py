@@ -9,7 +9,9 @@ fp16 (round-to-nearest-even) / fp8 E5M2 (torch's fp8e5m2_from_fp32_value:
 RNE, >= 2^16 -> inf), tied classifier when ``tie_word_embeddings`` is not
 False (convert.py:200). q4 (this engine's own format, models.q4_quantize): every weight
 matrix, the embedding included, is quantised from its fp16 conversion and stored as a U8
-tensor [rows, row_bytes(n)]; dense models only. Mixtral checkpoints (convert.py:54-56, 78-80, 188-193): the
+tensor [rows, row_bytes(n)]; dense models only. e4m3 (this engine's own too, models.e4m3_quantize:
+OCP E4M3 codes with one power-of-two f32 scale per row) is written the same way, as U8 tensors
+[rows, n + 16], from the fp16 conversion; dense models only. Mixtral checkpoints (convert.py:54-56, 78-80, 188-193): the
 router gate becomes ``moegate``, each layer's experts are stacked along a new
 leading axis, and n_experts / n_experts_active go into the metadata.
 Two forms the reference's converter and engine do not read (such a file is this engine's
@@ -39,7 +41,7 @@ from .yalmfile import read_yalm, write_yalm
 
 SUPPORTED_ARCHITECTURES = ["LlamaForCausalLM", "MistralForCausalLM", "MixtralForCausalLM", "Qwen2ForCausalLM",
                            "Qwen3ForCausalLM"]
-SUPPORTED_DTYPES = ["fp32", "fp16", "fp8", "q4"]
+SUPPORTED_DTYPES = ["fp32", "fp16", "fp8", "q4", "e4m3"]
 
 
 def metadata_from_config(config: dict, dtype: str) -> dict:
@@ -50,6 +52,8 @@ def metadata_from_config(config: dict, dtype: str) -> dict:
         raise ValueError(f"Data type {dtype} is not supported, must be one of {SUPPORTED_DTYPES}")
     if arch == "MixtralForCausalLM" and dtype == "q4":
         raise ValueError("q4 has no mixture-of-experts form")
+    if arch == "MixtralForCausalLM" and dtype == "e4m3":
+        raise ValueError("e4m3 has no mixture-of-experts form")
     head_dim = config.get("head_dim", config["hidden_size"] // config["num_attention_heads"])
     # (Llama's attention_bias also biases o_proj; Qwen2 has no such flag: its q / k / v bias is the architecture's)
     if config.get("attention_bias", False) or config.get("mlp_bias", False):
@@ -216,6 +220,8 @@ def convert(hf_dir: str, out_path: str, dtype: str = "fp16") -> None:
             return a.astype(np.float16), "F16"
         if dtype == "q4":  # from the fp16 conversion: |fp16 value - q4 value| <= scale / 2
             return M.q4_quantize(a.astype(np.float16).reshape(-1, a.shape[-1])), "U8"
+        if dtype == "e4m3":  # from the fp16 conversion: relative error <= 2^-4 above the row's subnormals
+            return M.e4m3_quantize(a.astype(np.float16).reshape(-1, a.shape[-1])), "U8"
         return f32_to_e5m2(a), "F8_E5M2"
 
     tensors, dtypes = {}, {}

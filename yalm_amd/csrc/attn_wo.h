@@ -33,7 +33,8 @@
 // *err.
 //
 // Geometry: Wo rows are q_dim * BYTES = KB KiB (KB in {1, 2, 4, 8}: 4 and 8 on one GPU
-// at Mistral / Llama shapes, 2 and 1 for the per-rank Wo of tensor parallelism); Wo
+// at Mistral / Llama shapes, 2 and 1 for the per-rank Wo of tensor parallelism; e4m3: KB KiB
+// of codes, 4 or 8, each row followed by the 16 bytes of its scale, see below); Wo
 // workgroup j owns rows [j * AWO_RPW, j * AWO_RPW + AWO_RPW) and thread t loads 16-byte
 // pieces i * 256 + t of that contiguous slice (LPT = AWO_RPW * KB / 4 loads). KB >= 4: a
 // thread's pieces cover every row of the slice, KB / 4 column pieces each; KB < 4: a
@@ -242,10 +243,14 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_wo_kernel(const float *__re
 	// the last slice may run past the matrix: shifted back so every load stays in
 	// bounds (unconditional loads); rows below row0 belong to workgroup j - 1
 	const int lrow0 = min(row0, p.dim - AWO_RPW);
-	const char *wbase = p.wo + (size_t)lrow0 * p.q_dim * WT::BYTES;
+	const char *wbase = p.wo + WT::row_off((size_t)lrow0, p.q_dim);
 	// the residual rows this workgroup adds to, loaded first (nothing else in the launch
 	// writes x): the read-modify-write at the end costs no load round trip
 	const float xres = p.add_base ? p.x[lrow0 + (tid & (AWO_RPW - 1))] : 0.0f;
+	// e4m3: the scale of the row this thread may finish, beside xres
+	[[maybe_unused]] float rscale = 1.0f;
+	if constexpr (WT::ROW_SCALE)
+		rscale = WT::row_scale(wbase + WT::row_off((size_t)(tid & (AWO_RPW - 1)), p.q_dim), p.q_dim);
 	const bool push = p.push.n > 0;
 	const unsigned xg = push ? p.push.g() : 0u; // exchange index, read ahead of the stream
 	if (p.delay > 0) {
@@ -255,8 +260,14 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_wo_kernel(const float *__re
 	}
 	u32x4_t wr[LPT];
 #pragma unroll
-	for (int i = 0; i < LPT; ++i)
-		wr[i] = load_nt16(wbase + ((size_t)i * ATTN_THREADS + tid) * 16);
+	for (int i = 0; i < LPT; ++i) {
+		if constexpr (WT::ROW_SCALE) { // rows end with their scale: load i is row i / XS, column piece (i % XS) * 256 + tid
+			static_assert(!WT::ROW_SCALE || KB >= 4, "row-scaled Wo: rows of 4 or 8 KiB of codes");
+			wr[i] = load_nt16(wbase + WT::row_off((size_t)(i / XS), p.q_dim) + ((size_t)(i % XS) * ATTN_THREADS + tid) * 16);
+		} else {
+			wr[i] = load_nt16(wbase + ((size_t)i * ATTN_THREADS + tid) * 16);
+		}
+	}
 	unsigned long long t_slice = 0, c_slice = 0, t_poll = 0, c_poll = 0;
 	if (tr) { // tracing only: when the whole slice has landed
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -315,8 +326,10 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_wo_kernel(const float *__re
 	__syncthreads();
 	const int row = lrow0 + tid;
 	if (tid < AWO_RPW && row >= row0) {
-		const float s = KB >= 4 ? (rowpart[tid][0] + rowpart[tid][1]) + (rowpart[tid][2] + rowpart[tid][3])
-		                        : (RPL == 4 ? rowpart[tid][0] : rowpart[tid][0] + rowpart[tid][1]);
+		float s = KB >= 4 ? (rowpart[tid][0] + rowpart[tid][1]) + (rowpart[tid][2] + rowpart[tid][3])
+		                  : (RPL == 4 ? rowpart[tid][0] : rowpart[tid][0] + rowpart[tid][1]);
+		if constexpr (WT::ROW_SCALE)
+			s *= rscale;
 		if (push)
 			tpx_put(p.push, xg, row, xres + s);
 		else

@@ -80,7 +80,7 @@ struct PrefillBufs {
 	float *skp = nullptr;                      // split-K partials of the short-prompt GEMMs (prefill_skinny.h)
 	size_t skp_floats = 0;
 	unsigned *range = nullptr;                 // [n_layers + 1][4] f16-operand range guard (prefill.h range_note)
-	uint16_t *wdq = nullptr;                   // fp8 models: one layer's (or the classifier's) weights as f16
+	uint16_t *wdq = nullptr;                   // fp8 / q4 / e4m3 models: one layer's (or the classifier's) weights as f16
 	int last_passes = 0, last_scaled = 0;      // the last yalm_prefill: passes run, layers with a scaled GLU output
 	// mixture of experts (moe_prefill.h; allocated only for such decoders): H then holds cap * K rows
 	float *Y = nullptr;                        // [cap * K][dim] f32 W2 outputs in slot order

@@ -132,13 +132,15 @@ __device__ __forceinline__ uint16_t f2h(float x) { // round to nearest even
 // Weight element types. EPL = elements per 16-byte lane load. Every type streams rows in
 // 64-lane chunks of 16-byte pieces (WT_CHUNK_BYTES, lane l at 16 l); row_off(r, n) is the
 // byte offset of row r of a [rows][n] matrix. Scale / load_scale: the side value a piece
-// needs beside its 16 bytes (nothing but for q4: its group's f16 scale).
+// needs beside its 16 bytes (nothing but for q4: its group's f16 scale). ROW_SCALE: every row
+// ends with one f32 scale that multiplies the row's sum (e4m3 alone).
 #define WT_CHUNK_BYTES ((size_t)YALM_WAVE * 16)
 struct NoScale {};
 struct WF32 {
 	static constexpr int EPL = 4;
 	static constexpr int BYTES = 4;
 	static constexpr bool Q4 = false;
+	static constexpr bool ROW_SCALE = false;
 	using Scale = NoScale;
 	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * n * BYTES; }
 	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
@@ -155,6 +157,7 @@ struct WF16 {
 	static constexpr int EPL = 8;
 	static constexpr int BYTES = 2;
 	static constexpr bool Q4 = false;
+	static constexpr bool ROW_SCALE = false;
 	using Scale = NoScale;
 	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * n * BYTES; }
 	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
@@ -176,6 +179,7 @@ struct WF8 {
 	static constexpr int EPL = 16;
 	static constexpr int BYTES = 1;
 	static constexpr bool Q4 = false;
+	static constexpr bool ROW_SCALE = false;
 	using Scale = NoScale;
 	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * n * BYTES; }
 	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
@@ -223,6 +227,7 @@ __device__ __forceinline__ void q4_pairs(uint32_t w, half2_t (&h)[4]) {
 struct WQ4 {
 	static constexpr int EPL = 32; // a lane's 16-byte load is one group
 	static constexpr bool Q4 = true;
+	static constexpr bool ROW_SCALE = false;
 	// the group's f16 scale, as bits in a register of its own: 16-bit values in flight are
 	// packed two to a register by hipcc, and the merge waits for each scale load at once (vmcnt(0))
 	using Scale = uint32_t;
@@ -273,8 +278,40 @@ __device__ __forceinline__ float q4_dot32(float acc, const u32x4_t &w, uint32_t 
 	return __builtin_fmaf(h2f((uint16_t)s), a0 + a1, acc);
 }
 
+// e4m3: OCP E4M3 codes (e4m3fn: bias 7, subnormals m * 2^-9, maximum 448, no infinities, 0x7F /
+// 0xFF NaN; gfx950 "fp8") with one f32 scale per row. A row of n elements (n % 16 == 0) is n code
+// bytes (element e at byte e), then the little-endian f32 scale at byte n, then 12 zero bytes:
+// n + 16 bytes, rows stay 16-byte aligned. The value of an element is code * scale. The
+// quantiser writes scales 2^k, -15 <= k <= 7, for which every finite value is an exact f16; the
+// decode kernels take any finite f32. v_cvt_pk_f32_fp8 is WF8's conversion for this format, the
+// row's sum is multiplied by the scale once (gemv.h, gemv_rows.h, attn_wo.h: ROW_SCALE).
+// No BYTES: code that multiplies by an element size does not compile for it.
+struct WE4M3 {
+	static constexpr int EPL = 16;
+	static constexpr bool Q4 = false;
+	static constexpr bool ROW_SCALE = true;
+	using Scale = NoScale;
+	__host__ __device__ static __forceinline__ size_t row_bytes(int n) { return (size_t)n + 16; }
+	__host__ __device__ static __forceinline__ size_t row_off(size_t r, int n) { return r * ((size_t)n + 16); }
+	// the scale of the row of n elements that begins at `row`
+	__device__ static __forceinline__ float row_scale(const char *row, int n) { return *(const float *)(row + n); }
+	__device__ static __forceinline__ void unpack(const u32x4_t &w, float *o) {
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			const uint32_t v = w[i];
+			const float2_t a = __builtin_amdgcn_cvt_pk_f32_fp8((int)v, false); // bytes 0, 1
+			const float2_t b = __builtin_amdgcn_cvt_pk_f32_fp8((int)v, true);  // bytes 2, 3
+			o[4 * i + 0] = a[0];
+			o[4 * i + 1] = a[1];
+			o[4 * i + 2] = b[0];
+			o[4 * i + 3] = b[1];
+		}
+	}
+};
+
 // x[0, dim) = one embedding row widened exactly, by the workgroup's threads: piece k of the
-// row is its bytes [16 k, 16 k + 16) = elements [EPL k, EPL k + EPL) (q4: times the group's scale).
+// row is its bytes [16 k, 16 k + 16) = elements [EPL k, EPL k + EPL) (q4: times the group's scale;
+// e4m3: times the row's).
 template <class WT>
 __device__ __forceinline__ void embed_row(const char *row, int dim, float *__restrict__ x) {
 	for (int k = threadIdx.x; k * WT::EPL < dim; k += blockDim.x) {
@@ -284,8 +321,12 @@ __device__ __forceinline__ void embed_row(const char *row, int dim, float *__res
 		else
 			WT::unpack(load16(row + (size_t)k * 16), f);
 #pragma unroll
-		for (int e = 0; e < WT::EPL; ++e)
-			x[k * WT::EPL + e] = f[e];
+		for (int e = 0; e < WT::EPL; ++e) {
+			if constexpr (WT::ROW_SCALE)
+				x[k * WT::EPL + e] = f[e] * WT::row_scale(row, dim);
+			else
+				x[k * WT::EPL + e] = f[e];
+		}
 	}
 }
 
@@ -295,7 +336,7 @@ __device__ __forceinline__ void embed_row(const char *row, int dim, float *__res
 // one asm statement so no compiler padding lands between the dependent ops.
 template <class WT>
 __device__ __forceinline__ void dot16_mix(float &a0, float &a1, const u32x4_t &w, const float (&x)[WT::EPL]) {
-	if constexpr (WT::BYTES == 2) {
+	if constexpr (WT::EPL == 8) { // f16
 		asm("v_fma_mix_f32 %0, %2, %4, %0 op_sel_hi:[1,0,0]\n\t"
 		    "v_fma_mix_f32 %1, %2, %5, %1 op_sel:[1,0,0] op_sel_hi:[1,0,0]\n\t"
 		    "v_fma_mix_f32 %0, %3, %6, %0 op_sel_hi:[1,0,0]\n\t"

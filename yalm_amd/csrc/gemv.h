@@ -12,7 +12,8 @@
 //       PQKV       clip + RoPE + fp16 KV-cache write, pairs of rows (fused_qkv_matmul_clip
 //                  + fused_rope_and_cache_update + rotate_sink_tokens)
 //       PGlu       act(W1 row) * (W3 row)          (fused_ffn_w1_w3_glu_act)
-// Accumulation is fp32 (weights widened exactly: f16 -> f32, E5M2 -> f16 -> f32).
+// Accumulation is fp32 (weights widened exactly: f16 -> f32, E5M2 -> f16 -> f32, e4m3 code -> f32;
+// e4m3's row scale multiplies the finished row sum once, in the kernels, ahead of every policy).
 #pragma once
 
 #include <type_traits>
@@ -549,6 +550,12 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(P p, const float *__
 			if constexpr (WT::Q4)
 				sp[r] = rp[r] - (size_t)lane * 16 + WT::scale_off(n, lane);
 		}
+		[[maybe_unused]] float rs[R]; // e4m3: each row's scale, requested ahead of the row's weights
+		if constexpr (WT::ROW_SCALE) {
+#pragma unroll
+			for (int r = 0; r < R; ++r)
+				rs[r] = WT::row_scale(rp[r] - (size_t)lane * 16, n);
+		}
 		float acc[R];
 #pragma unroll
 		for (int r = 0; r < R; ++r)
@@ -608,6 +615,11 @@ __global__ __launch_bounds__(GEMV_THREADS) void gemv_kernel(P p, const float *__
 #pragma unroll
 		for (int r = 0; r < R; ++r)
 			acc[r] = wave_sum(acc[r]);
+		if constexpr (WT::ROW_SCALE) {
+#pragma unroll
+			for (int r = 0; r < R; ++r)
+				acc[r] *= rs[r];
+		}
 		p.finish(g, acc, lane);
 	}
 }
@@ -725,6 +737,16 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 		for (int r = 0; r < R; ++r)
 			xr[r] = p.pre(g0, r);
 	}
+	// e4m3: the row scales of group threadIdx.x, the epilogue's (clamped, unconditional, as xr): 4
+	// bytes per row requested ahead of the weight stream, so the vmcnt order stays static and the
+	// epilogue waits for no round trip of its own
+	[[maybe_unused]] float rs[R] = {};
+	if constexpr (WT::ROW_SCALE) {
+		const int g0 = min(b + min((int)threadIdx.x, max(ngl - 1, 0)) * NB, p.n_groups - 1);
+#pragma unroll
+		for (int r = 0; r < R; ++r)
+			rs[r] = WT::row_scale(p.row(g0, r), n);
+	}
 	typename early_of<P>::type ek{}; // PQKV: the sink pairs, loaded ahead of the weight stream
 	if constexpr (gemv_early<P>::value)
 		ek = p.early();
@@ -794,6 +816,11 @@ __global__ __launch_bounds__(THREADS) void gemv_rb_kernel(P p, const float *__re
 			for (int w = 0; w < W; ++w)
 				t += part[(gl * R + r) * W + w];
 			a[r] = t;
+		}
+		if constexpr (WT::ROW_SCALE) { // (a group past the first THREADS of a workgroup loads its scales here)
+#pragma unroll
+			for (int r = 0; r < R; ++r)
+				a[r] *= gl == (int)threadIdx.x ? rs[r] : WT::row_scale(p.row(b + gl * NB, r), n);
 		}
 		if constexpr (gemv_pre<P>::value) {
 			if (gl == (int)threadIdx.x)

@@ -238,6 +238,12 @@ __global__ __launch_bounds__(ROWS_THREADS) void gemv_rows_kernel(P p, const floa
 #pragma unroll
 		for (int r = 0; r < R; ++r)
 			rp[r] = p.row(valid ? g : p.n_groups - 1, r) + (size_t)lane * 16;
+		[[maybe_unused]] float rs[R]; // e4m3: each row's scale, requested ahead of the row's weights
+		if constexpr (WT::ROW_SCALE) {
+#pragma unroll
+			for (int r = 0; r < R; ++r)
+				rs[r] = WT::row_scale(rp[r] - (size_t)lane * 16, n);
+		}
 		float acc[R][T];
 #pragma unroll
 		for (int r = 0; r < R; ++r)
@@ -300,6 +306,13 @@ __global__ __launch_bounds__(ROWS_THREADS) void gemv_rows_kernel(P p, const floa
 #pragma unroll
 				for (int t = 0; t < T; ++t)
 					acc[r][t] = wave_sum(acc[r][t]);
+			if constexpr (WT::ROW_SCALE) {
+#pragma unroll
+				for (int r = 0; r < R; ++r)
+#pragma unroll
+					for (int t = 0; t < T; ++t)
+						acc[r][t] *= rs[r];
+			}
 			if (lane == 0)
 				p.finish(g, acc);
 		}

@@ -306,6 +306,32 @@ __global__ void synth_q4_kernel(u32x4_t *dst, size_t rows, int n, uint64_t seed,
 	}
 }
 
+// An e4m3 tensor [rows][n] (device_common.h WE4M3) of the synthetic model: code byte i of the
+// tensor (counting code bytes only, row-major) is bits 40..47 of hash i, with the two NaN codes
+// made finite by clearing their lowest bit (0x7F -> 0x7E = 448, 0xFF -> 0xFE = -448); every
+// row's scale is `rscale`, its 12 bytes of padding are zero. One 16-byte piece per thread step.
+__global__ void synth_e4m3_kernel(u32x4_t *dst, size_t rows, int n, uint64_t seed, float rscale) {
+	const size_t cp = (size_t)n / 16, rp = cp + 1; // code pieces per row; pieces per row
+	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * rp; i += (size_t)gridDim.x * blockDim.x) {
+		const size_t r = i / rp, k = i - r * rp;
+		u32x4_t v = {0u, 0u, 0u, 0u};
+		if (k < cp) {
+			const uint64_t b0 = (r * cp + k) * 16;
+#pragma unroll
+			for (int j = 0; j < 16; ++j) {
+				const uint64_t h = splitmix64(seed ^ ((b0 + j) * 0xD1B54A32D192ED03ull));
+				uint32_t c = (uint32_t)((h >> 40) & 0xFFu);
+				if ((c & 0x7Fu) == 0x7Fu)
+					c &= 0xFEu;
+				v[j >> 2] |= c << (8 * (j & 3));
+			}
+		} else {
+			v[0] = __float_as_uint(rscale);
+		}
+		dst[i] = v;
+	}
+}
+
 __global__ void synth_kernel(void *dst, size_t n, int dtype, uint64_t seed, float scale, float offset) {
 	const float k = scale * (1.0f / 8388608.0f);
 	for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {

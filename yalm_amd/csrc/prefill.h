@@ -419,6 +419,43 @@ __global__ __launch_bounds__(256) void q4_to_f16_kernel(DqSegsQ4 s) {
 	}
 }
 
+// e4m3 weights (device_common.h WE4M3) -> f16 for the prefill of an e4m3 model: f16(code * s),
+// exact for the quantiser's scales 2^k, -15 <= k <= 7 (include/yalm_hip.h), so the f16 GEMMs
+// over the copy compute exactly what they compute for the f16 twin model. DqSegsQ4 with nb =
+// 16-byte code pieces per row (n / 16); one piece and its row's scale in, 32 bytes out per
+// thread step.
+__global__ __launch_bounds__(256) void e4m3_to_f16_kernel(DqSegsQ4 s) {
+	const size_t total = s.end[s.n - 1];
+	for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+		const uint8_t *sp = s.src[0];
+		uint16_t *dp = s.dst[0];
+		size_t base = 0;
+		int nb = s.nb[0];
+#pragma unroll
+		for (int m = 1; m < 8; ++m) // constant indices: the kernel-argument arrays stay in SGPRs
+			if (m < s.n && i >= s.end[m - 1]) {
+				sp = s.src[m];
+				dp = s.dst[m];
+				base = s.end[m - 1];
+				nb = s.nb[m];
+			}
+		const size_t j = i - base, r = j / (size_t)nb;
+		const int b = (int)(j - r * nb), n = nb * 16;
+		const char *row = (const char *)sp + WE4M3::row_off(r, n);
+		const u32x4_t v = load_nt16(row + 16 * (size_t)b);
+		const float sc = WE4M3::row_scale(row, n);
+		float f[16];
+		WE4M3::unpack(v, f);
+		u32x4_t o[2];
+#pragma unroll
+		for (int k = 0; k < 8; ++k)
+			o[k >> 2][k & 3] = (uint32_t)f2h(f[2 * k] * sc) | ((uint32_t)f2h(f[2 * k + 1] * sc) << 16);
+		u32x4_t *d = (u32x4_t *)(dp + r * (size_t)n + 16 * (size_t)b);
+		d[0] = o[0];
+		d[1] = o[1];
+	}
+}
+
 // Xn[t] = f16(rmsnorm(X[t]) * w)  (rmsnorm, infer.cpp:134-144 statement order).
 // SPLIT: row t of Xn is [hi | lo], 2 dim wide: hi = f16(v), lo = f16(v - hi), so
 // hi + lo carries v to ~22 bits (the K / V columns of the QKV GEMM run over both

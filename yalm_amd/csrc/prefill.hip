@@ -345,6 +345,26 @@ int dequant_q4_into(uint16_t *wdq, std::initializer_list<Q4Mat> t, const uint16_
 	return YALM_OK;
 }
 
+// e4m3 models: the same, one 16-byte piece of 16 codes per step (prefill.h e4m3_to_f16_kernel)
+int dequant_e4m3_into(uint16_t *wdq, std::initializer_list<Q4Mat> t, const uint16_t **out, hipStream_t st) {
+	pf::DqSegsQ4 s{};
+	size_t off = 0, pieces = 0;
+	for (auto &m : t) {
+		s.src[s.n] = (const uint8_t *)m.p;
+		s.dst[s.n] = wdq + off;
+		out[s.n] = s.dst[s.n];
+		s.nb[s.n] = m.n / 16;
+		pieces += m.rows * (size_t)(m.n / 16);
+		s.end[s.n] = pieces;
+		off += m.rows * (size_t)m.n;
+		++s.n;
+	}
+	const int grid = (int)std::min<size_t>((pieces + 255) / 256, (size_t)device_cu_count() * 8);
+	pf::e4m3_to_f16_kernel<<<grid, 256, 0, st>>>(s);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
 int dequant(yalm_decoder_s *d, std::initializer_list<std::pair<const void *, size_t>> t, const uint16_t **out,
 			hipStream_t st) {
 	return dequant_into(d->pf.wdq, t, out, st);
@@ -551,8 +571,9 @@ int alloc_moe_tabs(yalm_decoder_s *d, pf::MoeGroupTabs &t, size_t slots, int E) 
 
 int check_prefill_shape(const yalm_config &c) {
 	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
-	if (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2 && c.weight_dtype != YALM_Q4) {
-		set_err("yalm_prefill: f16, fp8 (E5M2) or q4 weights only (MFMA f16 operands)");
+	if (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2 && c.weight_dtype != YALM_Q4 &&
+	    c.weight_dtype != YALM_E4M3) {
+		set_err("yalm_prefill: f16, fp8 (E5M2), e4m3 or q4 weights only (MFMA f16 operands)");
 		return YALM_ERR_UNSUPPORTED;
 	}
 	if (c.dim % pf::BN || c.hidden_dim % pf::BN || q_dim % pf::BN || kv_dim % pf::BN || c.vocab_size % pf::BN ||
@@ -607,7 +628,7 @@ int ensure_bufs(yalm_decoder_s *d) {
 	TRY(pf_alloc(d, (void **)&b.lp, cap * 4));
 	TRY(pf_alloc(d, (void **)&b.rope, cap * c.head_dim * 4));
 	TRY(pf_alloc(d, (void **)&b.range, (size_t)(c.n_layers + 1) * RG_N * 4));
-	if (c.weight_dtype == YALM_F8E5M2 || c.weight_dtype == YALM_Q4) { // the f16 copy of one layer's weights, or of the classifier
+	if (c.weight_dtype == YALM_F8E5M2 || c.weight_dtype == YALM_Q4 || c.weight_dtype == YALM_E4M3) { // the f16 copy of one layer's weights, or of the classifier
 		const size_t layer = ((size_t)q_dim + 2 * (size_t)c.n_kv_heads * c.head_dim) * c.dim + (size_t)c.dim * q_dim +
 							 3 * me * c.dim * c.hidden_dim + // (the stacked expert tensors
 								 (d->moe_E > 0 ? me * c.dim : 0); //  and the router's gate)
@@ -669,8 +690,10 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	PrefillBufs &b = d->pf;
 	hipStream_t st = d->stream;
 	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
-	const bool fp8 = c.weight_dtype == YALM_F8E5M2, q4 = c.weight_dtype == YALM_Q4;
-	if (fp8)
+	const bool fp8 = c.weight_dtype == YALM_F8E5M2, q4 = c.weight_dtype == YALM_Q4, e4m3 = c.weight_dtype == YALM_E4M3;
+	if (e4m3)
+		pf::embed_rows_kernel<WE4M3><<<T, 256, 0, st>>>(b.tok, d->emb, c.dim, b.X);
+	else if (fp8)
 		pf::embed_rows_kernel<WF8><<<T, 256, 0, st>>>(b.tok, d->emb, c.dim, b.X);
 	else if (q4)
 		pf::embed_rows_kernel<WQ4><<<T, 256, 0, st>>>(b.tok, d->emb, c.dim, b.X);
@@ -721,10 +744,10 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			w.wq = p[0], w.wk = p[1], w.wv = p[2], w.wo = p[3], w.w1 = p[4], w.w2 = p[5], w.w3 = p[6];
 			gate16 = moe ? p[7] : nullptr;
 		}
-		if (q4) { // the same for a q4 layer (dense only)
+		if (q4 || e4m3) { // the same for a q4 or e4m3 layer (dense only)
 			const uint16_t *p[7];
 			const size_t qr = (size_t)q_dim, kr = (size_t)kv_dim, hr = (size_t)c.hidden_dim, dr = (size_t)c.dim;
-			TRY(dequant_q4_into(d->pf.wdq, {{w.wq, qr, c.dim}, {w.wk, kr, c.dim}, {w.wv, kr, c.dim}, {w.wo, dr, q_dim},
+			TRY((e4m3 ? dequant_e4m3_into : dequant_q4_into)(d->pf.wdq, {{w.wq, qr, c.dim}, {w.wk, kr, c.dim}, {w.wv, kr, c.dim}, {w.wo, dr, q_dim},
 			                                {w.w1, hr, c.dim}, {w.w2, dr, c.hidden_dim}, {w.w3, hr, c.dim}}, p, st));
 			w.wq = p[0], w.wk = p[1], w.wv = p[2], w.wo = p[3], w.w1 = p[4], w.w2 = p[5], w.w3 = p[6];
 		}
@@ -903,9 +926,9 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 		TRY(dequant(d, {{d->wcls, (size_t)c.vocab_size * c.dim}}, p, st));
 		wcls = p[0];
 	}
-	if (q4) {
+	if (q4 || e4m3) {
 		const uint16_t *p[1];
-		TRY(dequant_q4_into(d->pf.wdq, {{d->wcls, (size_t)c.vocab_size, c.dim}}, p, st));
+		TRY((e4m3 ? dequant_e4m3_into : dequant_q4_into)(d->pf.wdq, {{d->wcls, (size_t)c.vocab_size, c.dim}}, p, st));
 		wcls = p[0];
 	}
 	TRY(launch_plain(f, cls_bn, b.Xn, sp * c.dim, T, sp * c.dim, c.dim, one(wcls, c.vocab_size), c.vocab_size, e, st));
@@ -1126,6 +1149,10 @@ extern "C" int yalm_moe_ffn_rows(float *xout, int *experts, float *weights, cons
 	       "yalm_moe_ffn_rows: 1 <= n_experts_active <= n_experts <= 64");
 	if (dtype == YALM_Q4) {
 		set_err("yalm_moe_ffn_rows: q4 weights have no mixture-of-experts form");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	if (dtype == YALM_E4M3) {
+		set_err("yalm_moe_ffn_rows: e4m3 weights have no mixture-of-experts form");
 		return YALM_ERR_UNSUPPORTED;
 	}
 	if (dtype != YALM_F16 && dtype != YALM_F8E5M2) {

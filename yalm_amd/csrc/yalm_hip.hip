@@ -146,6 +146,7 @@ extern "C" int yalm_stream_sync(yalm_stream s) {
 
 extern "C" int yalm_synth(void *device, size_t n, int dtype, uint64_t seed, float scale, float offset, yalm_stream s) {
 	ARGCHK(dtype != YALM_Q4, "yalm_synth: q4 tensors need their row length (yalm_synth_q4)");
+	ARGCHK(dtype != YALM_E4M3, "yalm_synth: e4m3 tensors need their row length (yalm_synth_e4m3)");
 	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_synth: bad dtype");
 	hipStream_t st = reinterpret_cast<hipStream_t>(s);
 	synth_kernel<<<4096, 256, 0, st>>>(device, n, dtype, seed, scale, offset);
@@ -165,6 +166,8 @@ extern "C" size_t yalm_row_bytes(int dtype, int n) {
 		return (size_t)n;
 	case YALM_Q4:
 		return n % 32 ? 0 : q4_row_bytes(n);
+	case YALM_E4M3:
+		return n % 16 ? 0 : WE4M3::row_bytes(n);
 	}
 	return 0;
 }
@@ -182,6 +185,24 @@ extern "C" int yalm_synth_q4(void *device, size_t rows, int n, uint64_t seed, fl
 	ARGCHK(device && rows > 0 && n > 0 && n % 32 == 0, "yalm_synth_q4: rows > 0 and a row length that is a multiple of 32 (q4)");
 	hipStream_t st = reinterpret_cast<hipStream_t>(s);
 	synth_q4_kernel<<<4096, 256, 0, st>>>((u32x4_t *)device, rows, n, seed, q4_restricted_f16(scale / 7.0f));
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+// Every row's scale: the power of two 2^k, -15 <= k <= 7, that puts 448 (the largest code) at or
+// just above `scale`; models.synth_e4m3_scale.
+static float e4m3_synth_scale(float scale) {
+	int k = -15;
+	while (k < 7 && ldexpf(448.0f, k) < scale)
+		++k;
+	return ldexpf(1.0f, k);
+}
+
+extern "C" int yalm_synth_e4m3(void *device, size_t rows, int n, uint64_t seed, float scale, yalm_stream s) {
+	ARGCHK(device && rows > 0 && n > 0 && n % 16 == 0,
+	       "yalm_synth_e4m3: rows > 0 and a row length that is a multiple of 16 (e4m3)");
+	hipStream_t st = reinterpret_cast<hipStream_t>(s);
+	synth_e4m3_kernel<<<4096, 256, 0, st>>>((u32x4_t *)device, rows, n, seed, e4m3_synth_scale(scale));
 	HIPCHK(hipGetLastError());
 	return YALM_OK;
 }
@@ -256,7 +277,7 @@ template <class WT, class P, bool NORM, int THREADS, int U, bool ROWS>
 static int launch_rb_k(const P &p, const float *x, const float *normw, float eps, int nb, size_t lds, hipStream_t st,
                        const TpX &tin) {
 	auto kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS>;
-	if constexpr (NORM && !LocalX<P>::value && !WT::Q4) { // (q4 has no tensor-parallel form)
+	if constexpr (NORM && !LocalX<P>::value && !WT::Q4 && !WT::ROW_SCALE) { // (q4, e4m3: no tensor-parallel form)
 		if (tin.n > 0)
 			kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS, true>;
 	} else if (tin.n > 0) {
@@ -292,10 +313,10 @@ static int launch_rb_t(const P &p, const float *x, const float *normw, float eps
 
 // Per-kind, per-weight-type defaults from tools/sweep_gemv.py on MI355X
 // (profiles/r1_sweep_rb*.txt): {threads, U, workgroups per CU}.
-// fp8 and q4: more ALU per byte than f16 / f32
+// fp8 (E5M2, e4m3) and q4: more ALU per byte than f16 / f32
 template <class WT>
 constexpr bool wt_narrow() {
-	if constexpr (WT::Q4)
+	if constexpr (WT::Q4 || WT::ROW_SCALE)
 		return true;
 	else
 		return WT::BYTES == 1;
@@ -316,7 +337,7 @@ static GemvCfg default_rb_cfg(int kind) {
 			return GemvCfg{512, 4, 3};
 		}
 	}
-	if constexpr (wt_narrow<WT>()) { // fp8: more ALU per byte -> fewer loads in flight per lane
+	if constexpr (wt_narrow<WT>()) { // fp8 (e4m3 takes E5M2's: the same chunk): more ALU per byte -> fewer loads in flight per lane
 		switch (kind) {
 		case GK_W2:
 			return GemvCfg{512, 4, 1};
@@ -587,11 +608,14 @@ static const void *attn_wo_fn_kb(int G, int KB) {
 	                                                                            : attn_wo_fn_g<WT, 8>(G);
 }
 static const void *attn_wo_pick(int dtype, int G, int KB) {
+	if (dtype == YALM_E4M3) // one GPU only: rows of 4 or 8 KiB of codes
+		return KB == 4 ? attn_wo_fn_g<WE4M3, 4>(G) : attn_wo_fn_g<WE4M3, 8>(G);
 	return dtype == YALM_F16 ? attn_wo_fn_kb<WF16>(G, KB) : attn_wo_fn_kb<WF8>(G, KB);
 }
 // The fused launch's plan for a (per-rank) config: 1 with the key splits S and the grid,
 // or 0 = separate attention and Wo launches. Fused needs head_dim 128, G <= 8, fp16 / fp8
-// Wo rows of 1, 2, 4 or 8 KiB (one GPU: 4 / 8; a tensor-parallel rank's Wo slice: 1 / 2 too),
+// Wo rows of 1, 2, 4 or 8 KiB (one GPU: 4 / 8; a tensor-parallel rank's Wo slice: 1 / 2 too)
+// or e4m3 Wo rows of 4 or 8 KiB of codes (the format has no tensor-parallel form),
 // and the whole grid (attention, one merger per query head, Wo)
 // within the co-resident workgroup slots: a workgroup past them is dispatched only when
 // an earlier one exits, and at short contexts every attention workgroup without keys
@@ -608,10 +632,13 @@ extern "C" int yalm_attn_wo_plan(const yalm_config *cp, int slots, int *splits, 
 	if (c.head_dim != 128 || c.n_kv_heads <= 0 || c.n_heads % c.n_kv_heads)
 		return 0;
 	const int G = c.n_heads / c.n_kv_heads;
-	if (G < 1 || G > 8 || (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2))
+	if (G < 1 || G > 8 ||
+	    (c.weight_dtype != YALM_F16 && c.weight_dtype != YALM_F8E5M2 && c.weight_dtype != YALM_E4M3))
 		return 0;
 	const int rb = c.n_heads * c.head_dim * (c.weight_dtype == YALM_F16 ? 2 : 1);
 	if ((rb != 1024 && rb != 2048 && rb != 4096 && rb != 8192) || c.dim < AWO_RPW)
+		return 0;
+	if (c.weight_dtype == YALM_E4M3 && rb < 4096)
 		return 0;
 	const int nchunks = (c.max_seq_len + attn_chunk<128>() - 1) / attn_chunk<128>();
 	const int n_wo = (c.dim + AWO_RPW - 1) / AWO_RPW;
@@ -657,8 +684,9 @@ static int attn_wo_init(yalm_decoder_s *d) {
 	// profiles/r2_sweep_awo_delay.txt 10.6 -> 10.1 us at kv_len 17. fp8 (16.8 MB, slice lands
 	// ~3.1 us, before the heads): 0.5 us gives 9.4 -> 8.4 us at kv 17, 11.3 -> 10.3 at kv 151,
 	// 579 -> 586 tok/s (profiles/r3_ab_awo_delay.txt); fp16 at 0.5 us is within noise
-	d->awo_delay = denv ? std::max(0, atoi(denv)) : (c.weight_dtype == YALM_F8E5M2 ? 50 : 20);
-	d->awo_delay_short = denv ? -1 : (c.weight_dtype == YALM_F8E5M2 ? 0 : -1);
+	const bool fp8 = c.weight_dtype == YALM_F8E5M2 || c.weight_dtype == YALM_E4M3; // (e4m3: the same slice bytes)
+	d->awo_delay = denv ? std::max(0, atoi(denv)) : (fp8 ? 50 : 20);
+	d->awo_delay_short = denv ? -1 : (fp8 ? 0 : -1);
 	// Removed in round 4 (measured losers, round 3, profiles/r3_ab_awo*.txt): the combined
 	// first gather attempt (YALM_AWO_SPEC), per-XCD copies of the head outputs
 	// (YALM_AWO_REPL) and a sliding window on the Wo slice loads (YALM_ATTN_WO_WIN)
@@ -712,13 +740,20 @@ static TpX tpx_ex(const yalm_decoder_s *d, int ex) {
 	return t;
 }
 
-// weight types with a fused attention + Wo kernel (attn_wo.h): f16 and fp8
+// weight types with a fused attention + Wo kernel (attn_wo.h): f16, fp8 and e4m3
 template <class WT>
 constexpr bool wt_fused_wo() {
 	if constexpr (WT::Q4)
 		return false;
+	else if constexpr (WT::ROW_SCALE)
+		return true;
 	else
 		return WT::BYTES == 2 || WT::BYTES == 1;
+}
+// formats that exist on one GPU and in dense models only (q4, e4m3)
+template <class WT>
+constexpr bool wt_dense_one_gpu() {
+	return WT::Q4 || WT::ROW_SCALE;
 }
 template <class WT, int GT, int KB>
 static void launch_attn_wo_k(yalm_decoder_s *d, const yalm_block_weights &w, const AttnWoArgs &p) {
@@ -764,7 +799,12 @@ static int launch_attn_wo(yalm_decoder_s *d, const yalm_block_weights &w, int la
 	p.delay = d->awo_delay_short >= 0 && d->awo_kv_hint >= 0 && d->awo_kv_hint <= AWO_SHORT_KV ? d->awo_delay_short
 	                                                                                         : d->awo_delay;
 	const int G = c.n_heads / c.n_kv_heads;
-	if constexpr (wt_fused_wo<WT>()) {
+	if constexpr (WT::ROW_SCALE) { // one GPU only: rows of 4 or 8 KiB of codes (attn_wo_plan)
+		if (p.q_dim == 4096)
+			launch_attn_wo_g<WT, 4>(d, w, p, G);
+		else
+			launch_attn_wo_g<WT, 8>(d, w, p, G);
+	} else if constexpr (wt_fused_wo<WT>()) {
 		switch (p.q_dim * WT::BYTES) {
 		case 1024:
 			launch_attn_wo_g<WT, 1>(d, w, p, G);
@@ -820,7 +860,7 @@ template <class WT>
 static int enqueue_residual_gemv(yalm_decoder_s *d, const void *W, int n, const float *v, int kind, int ex) {
 	const yalm_config &c = d->c;
 	hipStream_t st = d->stream;
-	if constexpr (WT::Q4) { // one GPU only: yalm_decoder_create_tp / _tp_ipc refuse q4
+	if constexpr (wt_dense_one_gpu<WT>()) { // one GPU only: yalm_decoder_create_tp / _tp_ipc refuse q4 and e4m3
 		PResidual<WT, 1> p;
 		p.W = (const char *)W;
 		p.n = n;
@@ -976,7 +1016,7 @@ static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, 
 		                d->part, l, c.n_layers, d->awo_err, nullptr, d->xb2, st));
 		TRY(enqueue_residual_gemv<WT>(d, w.wo, q_dim, d->xb2, GK_WO, ex0));
 	}
-	if constexpr (!WT::Q4) { // (no q4 experts: yalm_decoder_create_moe refuses)
+	if constexpr (!wt_dense_one_gpu<WT>()) { // (no q4 or e4m3 experts: yalm_decoder_create_moe refuses)
 		if (d->moe_E > 0) { // router, then the selected experts' FFN (never tensor parallel)
 			const MoeArgs a = moe_layer_args(d, l);
 			TRY((launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, st)));
@@ -1012,7 +1052,7 @@ template <class WT>
 static int enqueue_logits_t(yalm_decoder_s *d, int consume_ex, int push_ex) {
 	const yalm_config &c = d->c;
 	const TpX tin = consume_ex >= 0 ? tpx_consume(d, consume_ex, c.dim) : TpX{};
-	if constexpr (!WT::Q4) {
+	if constexpr (!wt_dense_one_gpu<WT>()) {
 		if (push_ex >= 0) {
 			PPush<WT, 1> p;
 			p.W = (const char *)d->wcls;
@@ -1053,7 +1093,14 @@ static int enqueue_begin_t(yalm_decoder_s *d, int n_ex) {
 	((dtype) == YALM_F32   ? FN<WF32>(__VA_ARGS__)                                                                     \
 	 : (dtype) == YALM_F16 ? FN<WF16>(__VA_ARGS__)                                                                     \
 	 : (dtype) == YALM_Q4  ? FN<WQ4>(__VA_ARGS__)                                                                      \
+	 : (dtype) == YALM_E4M3 ? FN<WE4M3>(__VA_ARGS__)                                                                   \
 	                       : FN<WF8>(__VA_ARGS__))
+// the formats with a multi-row form (gemv_rows.h): all but q4
+#define DISPATCH_WT_ROWS(dtype, FN, ...)                                                                               \
+	((dtype) == YALM_F32    ? FN<WF32>(__VA_ARGS__)                                                                    \
+	 : (dtype) == YALM_F16  ? FN<WF16>(__VA_ARGS__)                                                                    \
+	 : (dtype) == YALM_E4M3 ? FN<WE4M3>(__VA_ARGS__)                                                                   \
+	                        : FN<WF8>(__VA_ARGS__))
 // the element-typed formats alone (the expert kernels)
 #define DISPATCH_WT_EL(dtype, FN, ...)                                                                                 \
 	((dtype) == YALM_F32   ? FN<WF32>(__VA_ARGS__)                                                                     \
@@ -1149,8 +1196,8 @@ static int validate_config(const yalm_config *c) {
 	       "config: non-positive dimension");
 	ARGCHK(c->n_heads % c->n_kv_heads == 0, "config: n_heads % n_kv_heads != 0");
 	ARGCHK(c->weight_dtype == YALM_F32 || c->weight_dtype == YALM_F16 || c->weight_dtype == YALM_F8E5M2 ||
-	           c->weight_dtype == YALM_Q4,
-	       "config: weight_dtype must be F32, F16, F8E5M2 or Q4");
+	           c->weight_dtype == YALM_Q4 || c->weight_dtype == YALM_E4M3,
+	       "config: weight_dtype must be F32, F16, F8E5M2, Q4 or E4M3");
 	ARGCHK(c->dim % 16 == 0 && c->hidden_dim % 16 == 0 && (c->n_heads * c->head_dim) % 16 == 0,
 	       "config: dim, hidden_dim and n_heads*head_dim must be multiples of 16 (infer.cpp:66)");
 	ARGCHK(c->weight_dtype != YALM_Q4 ||
@@ -1450,6 +1497,11 @@ extern "C" int yalm_decoder_create_moe(const yalm_config *config, const yalm_moe
                                        const yalm_model_weights *weights, const void *const *moegate, yalm_stream s,
                                        yalm_decoder *out) {
 	ARGCHK(config && moe && moegate, "yalm_decoder_create_moe: null argument");
+	if (config->weight_dtype == YALM_E4M3) {
+		set_err("yalm_decoder_create_moe: e4m3 weights have no mixture-of-experts form (the expert kernels take "
+		        "no row scale)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	if (config->weight_dtype == YALM_Q4) {
 		set_err("yalm_decoder_create_moe: q4 weights have no mixture-of-experts form (the expert kernels address "
 		        "their own chunks)");
@@ -1509,6 +1561,11 @@ extern "C" int yalm_decoder_create_tp(const yalm_config *config, const yalm_mode
                                       int tp_size, const void *unique_id, yalm_stream s, yalm_decoder *out) {
 	ARGCHK(config && weights && unique_id && out, "yalm_decoder_create_tp: null argument");
 	ARGCHK(tp_size >= 1 && tp_rank >= 0 && tp_rank < tp_size, "yalm_decoder_create_tp: bad rank / size");
+	if (config->weight_dtype == YALM_E4M3) {
+		set_err("yalm_decoder_create_tp: e4m3 weights have no tensor-parallel form (a column shard of a row has "
+		        "no scale of its own)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	if (config->weight_dtype == YALM_Q4) {
 		set_err("yalm_decoder_create_tp: q4 weights have no tensor-parallel form (a column shard of a q4 row is "
 		        "two strided pieces)");
@@ -1572,6 +1629,11 @@ extern "C" int yalm_decoder_create_tp_ipc(const yalm_config *config, const yalm_
                                           yalm_decoder *out) {
 	ARGCHK(config && weights && own_buf && handles && out, "yalm_decoder_create_tp_ipc: null argument");
 	ARGCHK(tp_size >= 1 && tp_size <= 8 && tp_rank >= 0 && tp_rank < tp_size, "bad rank / size (1..8 ranks)");
+	if (config->weight_dtype == YALM_E4M3) {
+		set_err("yalm_decoder_create_tp_ipc: e4m3 weights have no tensor-parallel form (a column shard of a row "
+		        "has no scale of its own)");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	if (config->weight_dtype == YALM_Q4) {
 		set_err("yalm_decoder_create_tp_ipc: q4 weights have no tensor-parallel form (a column shard of a q4 row is "
 		        "two strided pieces)");
@@ -1775,7 +1837,7 @@ extern "C" int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_s
 }
 
 // ------------------------------------------------------------------ multi-row forward, speculative greedy decode
-// (gemv_rows.h, spec.h) Dense decoders on one GPU, f32 / f16 / fp8 weights.
+// (gemv_rows.h, spec.h) Dense decoders on one GPU, f32 / f16 / fp8 (E5M2) / e4m3 weights.
 static const char *const ROWS_Q4_WHY = ": q4 weights have no multi-row form (gemv_rows.h streams element-typed rows)";
 static int rows_supported(const yalm_decoder_s *d, const char *who) {
 	const char *why = nullptr;
@@ -1838,9 +1900,11 @@ extern "C" int yalm_rows_plan(int dtype, int n, int n_groups, int T, int cus, in
 		set_err(std::string("yalm_rows_plan") + ROWS_Q4_WHY);
 		return YALM_ERR_UNSUPPORTED;
 	}
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_rows_plan: bad dtype");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_E4M3,
+	       "yalm_rows_plan: bad dtype");
 	ARGCHK(n > 0 && n_groups > 0 && cus >= 0 && T >= 1 && T <= ROWS_MAX_T, "yalm_rows_plan: bad argument");
-	const int EPL = dtype == YALM_F32 ? WF32::EPL : dtype == YALM_F16 ? WF16::EPL : WF8::EPL;
+	const int EPL = dtype == YALM_F32 ? WF32::EPL : dtype == YALM_F16 ? WF16::EPL : WF8::EPL; // (e4m3: WF8's)
+	static_assert(WE4M3::EPL == WF8::EPL, "e4m3 plans as fp8");
 	const RowsPlan r = rows_plan(YALM_WAVE * EPL, n, n_groups, T, cus ? cus : device_cu_count());
 	if (kseg)
 		*kseg = r.kseg;
@@ -2196,7 +2260,7 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	const yalm_config &c = d->c;
 	const yalm_block_weights &w = d->b[l];
 	const int q_dim = c.n_heads * c.head_dim;
-	if constexpr (!WT::Q4) {
+	if constexpr (!wt_dense_one_gpu<WT>()) {
 		if (d->moe_E > 0 && (kernel_id == 3 || kernel_id == 4 || kernel_id == 9)) { // the layer's last routing
 			const MoeArgs a = moe_layer_args(d, l);
 			if (kernel_id == 9)
@@ -2388,6 +2452,7 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 	const char *wt = d->c.weight_dtype == YALM_F32   ? "WF32"
 	                 : d->c.weight_dtype == YALM_F16 ? "WF16"
 	                 : d->c.weight_dtype == YALM_Q4  ? "WQ4"
+	                 : d->c.weight_dtype == YALM_E4M3 ? "WE4M3"
 	                                                 : "WF8";
 	const std::string gk = std::string("gemv_rb_kernel<") + wt;
 	std::string s;
@@ -2552,7 +2617,8 @@ static int matmul_t(float *out, const float *x, const void *w, int n, int d) {
 
 extern "C" int yalm_matmul(float *xout, const float *x, const void *w, int n, int d, int dtype) {
 	ARGCHK(xout && x && w && n > 0 && d > 0, "bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4, "bad dtype");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3,
+	       "bad dtype");
 	ARGCHK(n % 16 == 0, "n must be a multiple of 16 (infer.cpp:66)");
 	ARGCHK(dtype != YALM_Q4 || n % 32 == 0, "q4: n must be a multiple of 32");
 	DevBuf dx, dw, dout;
@@ -2598,7 +2664,8 @@ extern "C" int yalm_matmul_rows(float *out, const float *x, const void *w, const
 		return YALM_ERR_UNSUPPORTED;
 	}
 	ARGCHK(out && x && w && n > 0 && d > 0, "yalm_matmul_rows: bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_matmul_rows: bad dtype");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_E4M3,
+	       "yalm_matmul_rows: bad dtype");
 	ARGCHK(T >= 1 && T <= ROWS_MAX_T, "yalm_matmul_rows: 1 <= T <= 4 rows");
 	ARGCHK(n % 16 == 0, "yalm_matmul_rows: n must be a multiple of 16 (infer.cpp:66)");
 	ARGCHK(xstride >= n && xstride % 4 == 0, "yalm_matmul_rows: xstride must be at least n and a multiple of 4");
@@ -2616,7 +2683,7 @@ extern "C" int yalm_matmul_rows(float *out, const float *x, const void *w, const
 	if (normw)
 		TRY(up(dn, normw, sizeof(float) * n));
 	TRY(up(dout, out, sizeof(float) * (size_t)T * ostride));
-	TRY(DISPATCH_WT_EL(dtype, matmul_rows_t, (float *)dout.p, (const float *)dx.p, dw.p, dw3.p, (const float *)dn.p, eps,
+	TRY(DISPATCH_WT_ROWS(dtype, matmul_rows_t, (float *)dout.p, (const float *)dx.p, dw.p, dw3.p, (const float *)dn.p, eps,
 	                   T, n, d, xstride, ostride, epilogue, act));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(out, dout.p, sizeof(float) * (size_t)T * ostride, hipMemcpyDeviceToHost));
@@ -2742,7 +2809,8 @@ static int ffn_t(float *out, const float *x, const void *w1, const void *w2, con
 extern "C" int yalm_ffn(float *xout, const float *x, const void *w1, const void *w2, const void *w3, int hidden_dim,
                         int dim, int act, int dtype) {
 	ARGCHK(xout && x && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4, "bad dtype");
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3,
+	       "bad dtype");
 	ARGCHK(dim % 16 == 0 && hidden_dim % 16 == 0, "dims must be multiples of 16");
 	ARGCHK(dtype != YALM_Q4 || (dim % 32 == 0 && hidden_dim % 32 == 0), "q4: dims must be multiples of 32");
 	const size_t wb = yalm_row_bytes(dtype, dim) * (size_t)hidden_dim;   // w1, w3: hidden_dim rows of dim
@@ -2774,6 +2842,10 @@ extern "C" int yalm_moe_ffn(float *xout, int *experts, float *weights, const flo
 	ARGCHK(xout && x && moegate && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "bad argument");
 	if (dtype == YALM_Q4) {
 		set_err("yalm_moe_ffn: q4 weights have no mixture-of-experts form");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	if (dtype == YALM_E4M3) {
+		set_err("yalm_moe_ffn: e4m3 weights have no mixture-of-experts form");
 		return YALM_ERR_UNSUPPORTED;
 	}
 	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "bad dtype");

@@ -22,6 +22,7 @@ std::string dtype_to_string(DType dtype) {
 	case DType::I8: return "I8";
 	case DType::U8: return "U8";
 	case DType::Q4: return "Q4";
+	case DType::E4M3: return "E4M3";
 	}
 	return "UNKNOWN";
 }
@@ -38,6 +39,7 @@ size_t dtype_size(DType dtype) {
 	case DType::I8:
 	case DType::U8: return 1;
 	case DType::Q4: return 0; // no element size: rows are yalm_row_bytes(YALM_Q4, n)
+	case DType::E4M3: return 0; // nor here: yalm_row_bytes(YALM_E4M3, n)
 	}
 	return 0;
 }

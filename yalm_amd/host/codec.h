@@ -30,6 +30,9 @@ enum class DType {
 	// group-quantised WEIGHT format of a model ("dtype": "q4"), never a tensor's dtype -- its
 	// matrices are U8 tensors [rows, yalm_row_bytes(YALM_Q4, n)] (include/yalm_hip.h).
 	Q4,
+	// ... and the row-scaled OCP E4M3 WEIGHT format ("dtype": "e4m3"; the reference's F8E4M3 above
+	// names a tensor of bare bytes): U8 tensors [rows, yalm_row_bytes(YALM_E4M3, n)] = [rows, n + 16].
+	E4M3,
 };
 std::string dtype_to_string(DType dtype);
 size_t dtype_size(DType dtype);

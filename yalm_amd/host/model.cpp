@@ -57,12 +57,16 @@ void Config::from_yalm(YALMData &yalm, int context) {
 		weight_dtype = DType::F8E5M2;
 	else if (dtype == "q4")
 		weight_dtype = DType::Q4;
+	else if (dtype == "e4m3")
+		weight_dtype = DType::E4M3;
 	else
 		throw std::runtime_error("FATAL: unsupported dtype: " + dtype);
 	if (n_experts > 0 && !(n_experts_active >= 1 && n_experts_active <= n_experts && n_experts <= 64))
 		throw std::runtime_error("FATAL: mixture of experts needs 1 <= n_experts_active <= n_experts <= 64");
 	if (weight_dtype == DType::Q4 && n_experts > 0)
 		throw std::runtime_error("FATAL: q4 weights have no mixture-of-experts form");
+	if (weight_dtype == DType::E4M3 && n_experts > 0)
+		throw std::runtime_error("FATAL: e4m3 weights have no mixture-of-experts form");
 	const std::string qb = md.value("qkv_bias", "0");
 	qkv_bias = !(qb.empty() || qb == "0" || qb == "False" || qb == "false");
 	if (qkv_bias && n_experts > 0)
@@ -87,12 +91,12 @@ void Config::from_yalm(YALMData &yalm, int context) {
 		throw std::runtime_error("FATAL: q4 needs dim, hidden_dim and n_heads * head_dim multiples of 32");
 }
 
-// the C ABI's code of a weight dtype (the reference's enum order, but q4)
+// the C ABI's code of a weight dtype (the reference's enum order, but q4 and e4m3)
 static int dtype_code(DType dt) {
-	return dt == DType::Q4 ? YALM_Q4 : (int)dt;
+	return dt == DType::Q4 ? YALM_Q4 : dt == DType::E4M3 ? YALM_E4M3 : (int)dt;
 }
 
-// bytes of one row of n weights (q4: nibble blocks + scales + padding)
+// bytes of one row of n weights (q4: nibble blocks + scales + padding; e4m3: codes + scale + padding)
 static size_t weight_row_bytes(DType dt, size_t n) {
 	return yalm_row_bytes(dtype_code(dt), (int)n);
 }
@@ -149,9 +153,9 @@ static const void *check_tensor(const Tensor *t, DType dt, std::array<int, 4> sh
 	return t->data;
 }
 
-// a weight matrix [rows][n] in the model's weight dtype; q4: a U8 tensor [rows, row bytes]
+// a weight matrix [rows][n] in the model's weight dtype; q4 / e4m3: a U8 tensor [rows, row bytes]
 static const void *check_weight(const Tensor *t, DType dt, int rows, int n) {
-	if (dt == DType::Q4)
+	if (dt == DType::Q4 || dt == DType::E4M3)
 		return check_tensor(t, DType::U8, {rows, (int)weight_row_bytes(dt, n), 0, 0});
 	return check_tensor(t, dt, {rows, n, 0, 0});
 }

@@ -153,7 +153,7 @@ struct Model {
 	// fills the KV cache; logprobs (may be null) gets log p(tokens[i+1]) per
 	// position; split: the split-operand precision form (yalm_set_prefill_precision).
 	// Mixture-of-experts models take the same call (the grouped expert FFN, moe_prefill.h).
-	// Returns false when this model's shape/dtype has no prefill path (f16 / fp8
+	// Returns false when this model's shape/dtype has no prefill path (f16 / fp8 / q4 / e4m3
 	// weights, dims multiple of 128, head_dim 64|128), its activations leave the
 	// prefill's f16 operand range, or YALM_NO_PREFILL=1; the caller then runs the
 	// per-position forward.

@@ -11,19 +11,26 @@ import numpy as np
 
 F32, F16, BF16, F8E5M2 = 0, 1, 2, 3
 Q4 = 16  # YALM_Q4: 4-bit groups of 32 with an f16 scale (this engine's own format; "q4" below)
+E4M3 = 17  # YALM_E4M3: OCP E4M3 codes with one f32 scale per row (this engine's own format; "e4m3" below)
 GELU, SILU = 0, 1
 FLT_MAX = 3.4028234663852886e38
 KV_SINKS = 2  # model.h:12
 
-DTYPE_NAMES = {"fp32": F32, "fp16": F16, "fp8": F8E5M2, "q4": Q4}
-DTYPE_STRINGS = {F32: "F32", F16: "F16", F8E5M2: "F8_E5M2", Q4: "U8"}  # q4 rows are stored as U8 tensors
-DTYPE_BYTES = {F32: 4, F16: 2, F8E5M2: 1}  # per element; q4 has no element size: row_bytes
+DTYPE_NAMES = {"fp32": F32, "fp16": F16, "fp8": F8E5M2, "q4": Q4, "e4m3": E4M3}
+DTYPE_STRINGS = {F32: "F32", F16: "F16", F8E5M2: "F8_E5M2", Q4: "U8", E4M3: "U8"}  # q4 / e4m3 rows are stored as U8 tensors
+DTYPE_BYTES = {F32: 4, F16: 2, F8E5M2: 1}  # per element; q4 and e4m3 have no element size: row_bytes
 Q4_GROUP = 32
+E4M3_ROW_TAIL = 16  # the row's f32 scale and 12 zero bytes
 
 
 def row_bytes(dtype: int, n: int) -> int:
     """Bytes of one row of n elements of a weight matrix (yalm_row_bytes). q4: n / 32 16-byte
-    nibble blocks, n / 32 f16 scales, zero padding to a multiple of 16."""
+    nibble blocks, n / 32 f16 scales, zero padding to a multiple of 16. e4m3: n codes, the f32
+    scale, 12 zero bytes."""
+    if dtype == E4M3:
+        if n % 16:
+            raise ValueError(f"e4m3: row length {n} is not a multiple of 16")
+        return n + E4M3_ROW_TAIL
     if dtype == Q4:
         if n % Q4_GROUP:
             raise ValueError(f"q4: row length {n} is not a multiple of {Q4_GROUP}")
@@ -552,6 +559,86 @@ def q4_dequantize(a: np.ndarray, n: int) -> np.ndarray:
     return ((u.astype(np.float32) - 8.0).reshape(u.shape[0], -1, Q4_GROUP) * s[:, :, None]).reshape(u.shape[0], n)
 
 
+# ---- e4m3: OCP E4M3 codes with one power-of-two f32 scale per row (include/yalm_hip.h) ----
+# value = code * s, s = 2^k with -15 <= k <= 7: for exactly those k every finite code times s is
+# an exact f16, so an e4m3 model has an exact f16 twin (e4m3_twin), as fp8 and q4 have.
+E4M3_MAX = 448.0
+E4M3_K_MIN, E4M3_K_MAX = -15, 7
+
+
+def e4m3_table() -> np.ndarray:
+    """The 256 code values as float32 (e4m3fn: S.EEEE.MMM, bias 7, subnormals m * 2^-9, no
+    infinities, NaN at 0x7F and 0xFF)."""
+    b = np.arange(256)
+    e, m = (b >> 3) & 15, (b & 7).astype(np.float64)
+    v = np.where(e == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * 2.0 ** (e - 7.0))
+    v = np.where((e == 15) & (m == 7), np.nan, v)
+    return np.where(b >> 7, -v, v).astype(np.float32)
+
+
+def e4m3_encode(v: np.ndarray) -> np.ndarray:
+    """float -> E4M3 codes: round to nearest even, saturated to +-448 (never a NaN code)."""
+    v = np.asarray(v, np.float64)
+    a = np.minimum(np.abs(v), E4M3_MAX)
+    _, ex = np.frexp(a)  # a = mant * 2^ex, mant in [0.5, 1)
+    e = np.maximum(ex - 1, -6)  # the exponent whose 3 mantissa bits a is rounded to (subnormals: -6)
+    q = np.rint(np.ldexp(a, 3 - e))  # in units of 2^(e - 3), ties to even; 0..16
+    q = np.ldexp(q, e - 3)
+    mant, ex = np.frexp(q)
+    normal = q >= 2.0 ** -6
+    code = np.where(normal, ((ex - 1 + 7) << 3) + np.rint((mant * 2.0 - 1.0) * 8.0).astype(np.int64),
+                    np.rint(q * 512.0).astype(np.int64))
+    return (code | np.where(np.signbit(v), 0x80, 0)).astype(np.uint8)
+
+
+def e4m3_row_k(amax: np.ndarray) -> np.ndarray:
+    """Per row: k = clip(ceil(log2(amax / 448)), -15, 7), 0 for amax 0 -- the smallest 2^k in range
+    that puts 448 at or above amax."""
+    amax = np.asarray(amax, np.float64)
+    mant, ex = np.frexp(amax / E4M3_MAX)  # (exact where amax / 448 is a power of two)
+    k = np.where(mant == 0.5, ex - 1, ex)
+    return np.where(amax > 0, np.clip(k, E4M3_K_MIN, E4M3_K_MAX), 0).astype(np.int64)
+
+
+def e4m3_pack(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """Codes (rows, n) uint8 and f32 scales (rows,) -> uint8 rows (rows, n + 16)."""
+    codes = np.asarray(codes, np.uint8)
+    rows, n = codes.shape
+    out = np.zeros((rows, row_bytes(E4M3, n)), np.uint8)
+    out[:, :n] = codes
+    out[:, n: n + 4] = np.ascontiguousarray(scales, dtype="<f4").reshape(rows, 1).view(np.uint8)
+    return out
+
+
+def e4m3_unpack(a: np.ndarray, n: int):
+    """uint8 rows (rows, n + 16) -> (codes (rows, n) uint8, scales (rows,) float32)."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    return a[:, :n], np.ascontiguousarray(a[:, n: n + 4]).view("<f4").astype(np.float32).reshape(-1)
+
+
+def e4m3_quantize(v: np.ndarray) -> np.ndarray:
+    """float matrix (rows, n), n % 16 == 0 -> e4m3 rows. Per row amax = max |w|, k = e4m3_row_k(amax),
+    codes = w / 2^k rounded to nearest even onto E4M3 and saturated to +-448 (which only bites
+    when amax > 448 * 2^7 = 57344)."""
+    v = np.asarray(v, np.float64)
+    k = e4m3_row_k(np.abs(v).max(axis=1))
+    return e4m3_pack(e4m3_encode(np.ldexp(v, -k[:, None])), np.ldexp(1.0, k).astype(np.float32))
+
+
+def e4m3_dequantize(a: np.ndarray, n: int) -> np.ndarray:
+    """e4m3 rows -> float32 (rows, n): code * s (exact for the quantiser's scales)."""
+    codes, s = e4m3_unpack(a, n)
+    return (e4m3_table()[codes].astype(np.float64) * s.astype(np.float64)[:, None]).astype(np.float32)
+
+
+def e4m3_twin(cfg: ModelConfig, tensors: dict):
+    """The exact f16 twin of an e4m3 model: (f16 config, tensors with every e4m3 matrix as float16)."""
+    out = {}
+    for name, (shape, is_norm) in tensor_shapes(cfg).items():
+        out[name] = tensors[name] if is_norm else decode_weights(tensors[name], E4M3, shape).astype(np.float16)
+    return cfg.with_(weight_dtype=F16), out
+
+
 def q4_twin(cfg: ModelConfig, tensors: dict):
     """The exact f16 twin of a q4 model: (f16 config, tensors with every q4 matrix as float16)."""
     out = {}
@@ -561,10 +648,12 @@ def q4_twin(cfg: ModelConfig, tensors: dict):
 
 
 def decode_weights(a: np.ndarray, dtype: int, shape=None) -> np.ndarray:
-    """Stored weights (f32 / f16 / E5M2 bytes / q4 rows) -> float32, exactly. q4 needs the
-    logical shape (rows, n)."""
+    """Stored weights (f32 / f16 / E5M2 bytes / q4 rows / e4m3 rows) -> float32, exactly. q4 and
+    e4m3 need the logical shape (rows, n)."""
     if dtype == F8E5M2:
         return e5m2_to_f32(a)
+    if dtype == E4M3:
+        return e4m3_dequantize(a.reshape(-1, a.shape[-1]), int(shape[-1])).reshape(shape)
     if dtype == Q4:
         return q4_dequantize(a.reshape(-1, a.shape[-1]), int(shape[-1])).reshape(shape)
     return a.astype(np.float32)
@@ -573,10 +662,12 @@ def decode_weights(a: np.ndarray, dtype: int, shape=None) -> np.ndarray:
 def encode_weights(v: np.ndarray, dtype: int) -> np.ndarray:
     """float32 -> stored weights: f16 round to nearest even; E5M2 through f16, then round
     to nearest even on the byte (the initialiser's rule, synth_array); q4: q4_quantize on the
-    matrix (rows, n)."""
+    matrix (rows, n); e4m3: e4m3_quantize on the matrix."""
     v = np.asarray(v, np.float32)
     if dtype == F32:
         return v
+    if dtype == E4M3:
+        return e4m3_quantize(v.reshape(-1, v.shape[-1]))
     if dtype == Q4:
         return q4_quantize(v.reshape(-1, v.shape[-1]))
     h16 = v.astype(np.float16)
@@ -656,12 +747,34 @@ def synth_q4_array(rows: int, n: int, seed: int, scale: float) -> np.ndarray:
     return out
 
 
+def synth_e4m3_scale(scale: float) -> np.float32:
+    """Every synthetic row's scale: 2^k for the smallest k in [-15, 7] with 448 * 2^k >= scale (7 if none)."""
+    k = E4M3_K_MIN
+    while k < E4M3_K_MAX and np.float32(np.ldexp(np.float32(E4M3_MAX), k)) < np.float32(scale):
+        k += 1
+    return np.float32(np.ldexp(1.0, k))
+
+
+def synth_e4m3_array(rows: int, n: int, seed: int, scale: float) -> np.ndarray:
+    """numpy twin of yalm_synth_e4m3: code byte i of the tensor (row-major, code bytes only) is bits
+    40..47 of hash i, the NaN codes made finite by clearing their lowest bit (0x7F -> 0x7E, 0xFF ->
+    0xFE); every row's scale is synth_e4m3_scale(scale); padding zero."""
+    with np.errstate(over="ignore"):
+        i = np.arange(rows * n, dtype=np.uint64)
+        h = _splitmix64(np.uint64(seed) ^ (i * np.uint64(0xD1B54A32D192ED03)))
+    c = ((h >> np.uint64(40)) & np.uint64(0xFF)).astype(np.uint8)
+    c = np.where((c & 0x7F) == 0x7F, c & 0xFE, c).astype(np.uint8)
+    return e4m3_pack(c.reshape(rows, n), np.full(rows, synth_e4m3_scale(scale), np.float32))
+
+
 def synth_host_tensors(c: ModelConfig, seed: int = 1, peak: float = 1.0, real: Realistic = None) -> dict:
     """All tensors of a synthetic model as numpy arrays (norms f32, weights in
-    c.weight_dtype storage: f32 / f16 / uint8 E5M2 bits / uint8 q4 rows); real: the realistic
-    model (not for q4: its patches address elements of the stored array)."""
+    c.weight_dtype storage: f32 / f16 / uint8 E5M2 bits / uint8 q4 rows / uint8 e4m3 rows); real:
+    the realistic model (not for q4 or e4m3: its patches address elements of the stored array)."""
     if real is not None and c.weight_dtype == Q4:
         raise ValueError("the realistic synthetic model has no q4 form: quantise its f16 tensors (q4_quantize)")
+    if real is not None and c.weight_dtype == E4M3:
+        raise ValueError("the realistic synthetic model has no e4m3 form: quantise its f16 tensors (e4m3_quantize)")
     out = {}
     for name, (shape, is_norm) in tensor_shapes(c).items():
         scale, offset = synth_params(name, is_norm, peak, real, c.tied)
@@ -669,6 +782,8 @@ def synth_host_tensors(c: ModelConfig, seed: int = 1, peak: float = 1.0, real: R
         n = int(np.prod(shape))
         if dt == Q4:
             out[name] = synth_q4_array(n // shape[-1], shape[-1], synth_seed(seed, name), scale)
+        elif dt == E4M3:
+            out[name] = synth_e4m3_array(n // shape[-1], shape[-1], synth_seed(seed, name), scale)
         else:
             out[name] = synth_array(n, dt, synth_seed(seed, name), scale, offset).reshape(shape)
     return apply_realistic(c, out, real) if real is not None else out

@@ -130,6 +130,7 @@ _sig("yalm_stream_sync", c_int, [c_void_p])
 _sig("yalm_synth", c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint64, c_float, c_float, c_void_p])
 _sig("yalm_row_bytes", c_size_t, [c_int, c_int])
 _sig("yalm_synth_q4", c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint64, c_float, c_void_p])
+_sig("yalm_synth_e4m3", c_int, [c_void_p, c_size_t, c_int, ctypes.c_uint64, c_float, c_void_p])
 _sig("yalm_decoder_create", c_int, [ctypes.POINTER(Config), ctypes.POINTER(ModelWeights), c_void_p,
                                      ctypes.POINTER(c_void_p)])
 _sig("yalm_decoder_create_moe", c_int, [ctypes.POINTER(Config), c_void_p, ctypes.POINTER(ModelWeights), c_void_p,
@@ -203,7 +204,7 @@ EXPORTED = [
     "yalm_decoder_create_moe", "yalm_moe_routing", "yalm_moe_ffn",
     "yalm_prefill_routing", "yalm_moe_gemm_f16", "yalm_moe_ffn_rows",
     "yalm_generate_sampled", "yalm_sample",
-    "yalm_row_bytes", "yalm_synth_q4",
+    "yalm_row_bytes", "yalm_synth_q4", "yalm_synth_e4m3",
     "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
     "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
     "yalm_decoder_set_qk_norm",
@@ -234,13 +235,13 @@ def _ptr(a: np.ndarray) -> int:
 
 # ------------------------------------------------------------- kernel-level test API
 def matmul(x: np.ndarray, w: np.ndarray, dtype: int) -> np.ndarray:
-    """matmul_cuda (infer.cu:937-957): W (d, n) @ x (n,). q4: w is the uint8 rows
-    (d, row_bytes(Q4, n)) of models.q4_quantize; n is x's length."""
+    """matmul_cuda (infer.cu:937-957): W (d, n) @ x (n,). q4 / e4m3: w is the uint8 rows
+    (d, row_bytes(dtype, n)) of models.q4_quantize / e4m3_quantize; n is x's length."""
     d, n = w.shape
     x = np.ascontiguousarray(x, dtype=np.float32)
-    if dtype == M.Q4:
+    if dtype in (M.Q4, M.E4M3):
         n = x.size
-        assert w.dtype == np.uint8 and w.shape[1] == M.row_bytes(M.Q4, n)
+        assert w.dtype == np.uint8 and w.shape[1] == M.row_bytes(dtype, n)
     w = np.ascontiguousarray(w)
     out = np.zeros(d, np.float32)
     check(lib.yalm_matmul(_ptr(out), _ptr(x), _ptr(w), n, d, dtype))
@@ -292,13 +293,13 @@ def spec_draft(history, rows: int, ngram_max: int = 3, ngram_min: int = 1) -> li
 
 
 def ffn(x, w1, w2, w3, act: int, dtype: int) -> np.ndarray:
-    """ffn_cuda (infer.cu:959-1007). q4: w1 / w3 (hidden_dim, row_bytes(Q4, dim)) and w2
-    (dim, row_bytes(Q4, hidden_dim)) uint8 rows."""
+    """ffn_cuda (infer.cu:959-1007). q4 / e4m3: w1 / w3 (hidden_dim, row_bytes(dtype, dim)) and w2
+    (dim, row_bytes(dtype, hidden_dim)) uint8 rows."""
     hidden_dim, dim = w1.shape
     x = np.ascontiguousarray(x, dtype=np.float32)
-    if dtype == M.Q4:
+    if dtype in (M.Q4, M.E4M3):
         dim = x.size
-        assert w2.shape == (dim, M.row_bytes(M.Q4, hidden_dim)) and w1.shape[1] == M.row_bytes(M.Q4, dim)
+        assert w2.shape == (dim, M.row_bytes(dtype, hidden_dim)) and w1.shape[1] == M.row_bytes(dtype, dim)
     w1, w2, w3 = (np.ascontiguousarray(a) for a in (w1, w2, w3))
     out = np.zeros(dim, np.float32)
     check(lib.yalm_ffn(_ptr(out), _ptr(x), _ptr(w1), _ptr(w2), _ptr(w3), hidden_dim, dim, act, dtype))
@@ -420,12 +421,15 @@ def matmul_rows(out, x, w, dtype: int, epilogue: int = ROWS_STORE, w3=None, norm
                 act: int = M.SILU, n=None) -> np.ndarray:
     """One multi-row GEMV launch (yalm_matmul_rows): x (T, xstride) f32, w (d, n) stored weights
     (w3 too for ROWS_GLU), out (T, ostride) f32 as it stands before the launch (sentinels, the
-    residual's start). n defaults to w's row length. Returns the whole out after the launch; the
-    argument is not written."""
+    residual's start). n defaults to w's row length (e4m3: w is the uint8 rows (d, n + 16)).
+    Returns the whole out after the launch; the argument is not written."""
     x = np.ascontiguousarray(x, dtype=np.float32)
     out = np.array(out, dtype=np.float32, order="C")
     w = np.ascontiguousarray(w)
     d = w.shape[0]
+    if dtype == M.E4M3:
+        n = w.shape[1] - M.E4M3_ROW_TAIL if n is None else n
+        assert w.dtype == np.uint8 and w.shape[1] == M.row_bytes(M.E4M3, n)
     n = w.shape[1] if n is None else n
     w3 = None if w3 is None else np.ascontiguousarray(w3)
     normw = None if normw is None else np.ascontiguousarray(normw, dtype=np.float32)
@@ -494,6 +498,8 @@ class DeviceModel:
         M.tp_check(cfg, size)
         if cfg.weight_dtype == M.Q4 and size > 1:
             raise ValueError("q4 models run on one GPU (no tensor-parallel form)")
+        if cfg.weight_dtype == M.E4M3 and size > 1:
+            raise ValueError("e4m3 models run on one GPU (no tensor-parallel form)")
         self = cls(cfg)
         self.tp = tp
         items = dict(tensors)
@@ -551,6 +557,13 @@ class DeviceModel:
                     raise ValueError("q4 models are synthesised for one GPU, without the realistic patches")
                 p = self._alloc(M.matrix_bytes(M.Q4, shape))
                 check(lib.yalm_synth_q4(p, n // shape[-1], shape[-1], M.synth_seed(seed, src_name), scale, None))
+                self.ptrs[name] = p
+                continue
+            if dt == M.E4M3:  # rows with their scale: yalm_synth_e4m3 (never sharded: e4m3 runs on one GPU)
+                if size > 1 or real is not None:
+                    raise ValueError("e4m3 models are synthesised for one GPU, without the realistic patches")
+                p = self._alloc(M.matrix_bytes(M.E4M3, shape))
+                check(lib.yalm_synth_e4m3(p, n // shape[-1], shape[-1], M.synth_seed(seed, src_name), scale, None))
                 self.ptrs[name] = p
                 continue
             eb = M.DTYPE_BYTES[dt]
