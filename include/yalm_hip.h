@@ -578,6 +578,65 @@ int yalm_rows_plan(int dtype, int n, int n_groups, int T, int cus, int *kseg, in
 #define YALM_ROWS_GLU 2
 int yalm_matmul_rows(float *out, const float *x, const void *w, const void *w3, const float *normw, float eps, int T,
                      int n, int d, int xstride, int ostride, int dtype, int epilogue, int act);
+/* The geometry of one single-row (decode) GEMV launch, as the launcher itself computes it: over
+ * n_groups wave groups of rows of n elements, for the epilogue `policy`, with (norm != 0) or without
+ * the rmsnorm of x. kind 0..4 (QKV, Wo, W1|W3, W2, logits) selects the default {threads, unroll,
+ * workgroups per CU} of the weight type; threads / unroll / wpc != 0 override it as
+ * yalm_set_gemv_config does. cus: the CUs the grid is sized for (0 = this device's; pure host
+ * arithmetic otherwise). rows: -1 = whole-row mode where the policy has it and the rows divide,
+ * 0 = chunk order. A row that is no whole number of 64-lane chunks takes the generic kernel
+ * (generic = 1: 256 threads, one group per wave; threads / unroll / wpc / cus / rows are ignored). */
+#define YALM_GEMV_STORE1 0   /* out[i] = w[i] . x */
+#define YALM_GEMV_STORE2 1   /* the same, two rows per group (even vocabularies) */
+#define YALM_GEMV_RESIDUAL 2 /* out[i] += w[i] . x */
+#define YALM_GEMV_ADDTO 3    /* out[i] = base[i] + w[i] . x */
+#define YALM_GEMV_GLU 4      /* out[i] = act(w[i] . x) * (w3[i] . x) */
+#define YALM_GEMV_QKV 5      /* clip, RoPE, q to q_out, K / V rows of the cache, sink rotation */
+#define YALM_GEMV_QKVB 6     /* ... with a bias ahead of the clip */
+#define YALM_GEMV_QKVN 7     /* ... q and k clipped and stored raw (ahead of the q / k norm launch) */
+typedef struct {
+	int generic;          /* 1: gemv_kernel, 0: gemv_rb_kernel */
+	int threads, unroll;  /* block size, loads in flight per lane */
+	int nb;               /* grid */
+	int rows;             /* 1: whole-row mode */
+	int ngl_min, ngl_max; /* groups of a workgroup: the fewest and the most */
+	int xregs;            /* 1: x (and the norm weights) are loaded ahead of the weight stream */
+	size_t lds;           /* dynamic LDS bytes */
+} yalm_gemv_geometry;
+int yalm_gemv_plan(int dtype, int policy, int kind, int n, int n_groups, int norm, int threads, int unroll, int wpc,
+                   int cus, int rows, yalm_gemv_geometry *out);
+/* One single-row GEMV launch, the decoder's own (the launcher the forward pass calls, at the plan of
+ * yalm_gemv_plan), on host arrays, synchronous. x: n floats; normw: n floats when norm != 0 (x is
+ * rmsnorm'ed with eps while it is staged). Store / residual / addto / GLU: w (and w3) are d rows,
+ * out holds out_len >= d floats, base d floats. The QKV policies: wq is n_heads * head_dim rows, wk
+ * and wv n_kv_heads * head_dim; rope and rope_sink are head_dim floats each, the (cos, sin) pairs
+ * of this step and of the sinks' one-position rotation; kcache / vcache are cache_rows rows of
+ * n_kv_heads * head_dim f16; q_out holds q_len floats, raw raw_len (QKVN), bq / bk / bv the
+ * biases (QKVB). The step's `pos` is set to another cache row than kv_pos ((kv_pos + 1) %
+ * cache_rows), so a row stored at pos shows. Everything the launch may write (out, q_out, raw, kcache, vcache) is uploaded as
+ * given and returned whole: what the kernel does not write comes back as it went in.
+ * YALM_ERR_ARG: n no multiple of 16 (q4: of 32), head_dim odd or above 256, odd q or kv dims,
+ * cache_rows below 2 or at most kv_pos, kv_sink above kv_pos, a normalising PAddTo. */
+typedef struct {
+	int dtype, policy, kind;
+	int n, d; /* row length; output rows (not the QKV policies) */
+	int norm, act;
+	float eps;
+	int threads, unroll, wpc, cus, rows; /* as yalm_gemv_plan */
+	const float *x, *normw;
+	const void *w, *w3, *wq, *wk, *wv;
+	float *out;
+	const float *base;
+	int out_len;
+	int n_heads, n_kv_heads, head_dim, kv_sink, kv_pos, cache_rows;
+	float qkv_clip;
+	const float *rope, *rope_sink;
+	uint16_t *kcache, *vcache;
+	float *q_out, *raw;
+	int q_len, raw_len;
+	const float *bq, *bk, *bv;
+} yalm_gemv_args;
+int yalm_gemv_one(const yalm_gemv_args *args);
 /* mha_cuda: xout (n_heads, head_dim), att (n_heads, max_seq_len) softmax
  * probabilities for t < kv_len. */
 int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint16_t *vb, const float *q, int head_dim, int kv_len,

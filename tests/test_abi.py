@@ -17,7 +17,7 @@ def test_header_declares_expected_entry_points():
     syms = declared_symbols()
     for s in ("yalm_upload", "yalm_free", "yalm_decoder_create", "yalm_forward", "yalm_block", "yalm_matmul",
               "yalm_mha", "yalm_ffn", "yalm_generate_greedy", "yalm_rows_plan", "yalm_matmul_rows",
-              "yalm_attn_prefill_rows"):
+              "yalm_attn_prefill_rows", "yalm_gemv_plan", "yalm_gemv_one"):
         assert s in syms
 
 

@@ -41,8 +41,11 @@ void set_err(const std::string &s); // yalm_hip.hip (thread-local last error)
 	} while (0)
 
 // GEMV launch geometry of gemv_rb_kernel: threads, loads in flight per lane, workgroups per CU. 0 = automatic.
+// cus / rows: set by the yalm_gemv_plan / yalm_gemv_one hooks alone (the CUs the grid is sized for, 0 = this
+// device's; whole-row mode: -1 where the launch qualifies, 0 never).
 struct GemvCfg {
 	int threads = 0, U = 0, gpw = 0;
+	int cus = 0, rows = -1;
 };
 enum { GK_QKV = 0, GK_WO = 1, GK_GLU = 2, GK_W2 = 3, GK_CLS = 4, GK_N = 5 };
 

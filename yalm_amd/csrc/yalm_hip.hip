@@ -270,6 +270,11 @@ template <class WT, int ACT>
 struct LocalX<PMoeGlu<WT, ACT>> {
 	static constexpr bool value = true;
 };
+// ... and the residual policy: the decoder never norms its x; only the yalm_gemv_one hook does
+template <class WT, int R>
+struct LocalX<PResidual<WT, R>> {
+	static constexpr bool value = true;
+};
 
 // One launch of gemv_rb_kernel; a consumer of an IPC exchange (tin.n > 0, always a
 // normalising GEMV: QKV, W1|W3, logits) runs the TIN instantiation.
@@ -291,24 +296,66 @@ static int launch_rb_k(const P &p, const float *x, const float *normw, float eps
 	return YALM_OK;
 }
 
-template <class WT, class P, bool NORM, int THREADS, int U>
-static int launch_rb_t(const P &p, const float *x, const float *normw, float eps, int wpc, hipStream_t st,
-                       const TpX &tin) {
-	// an exchange consumer stages x from the exchange once per CU: one workgroup per CU
-	const int nb = std::max(1, std::min(p.n_groups, device_cu_count() * (tin.n > 0 ? 1 : std::max(1, wpc))));
-	const int ngl = (p.n_groups + nb - 1) / nb;
-	const size_t lds = ((size_t)xs_len<WT::Q4>(p.n) + 64 + (size_t)ngl * P::R * (THREADS / YALM_WAVE)) * sizeof(float);
-	if constexpr (RowsMode<P>::value) {
-		// every workgroup the same number of rows and a whole number of rows, at least 2,
-		// per wave (profiles/r3_gemv_rows.txt: W1|W3 fp16 39.4-40.0 -> 36.9 us, fp8 W2 13.4 ->
-		// 12.7-13.0; fp16 W2 with ONE 28-KB row per wave went 20.3 -> 21.3, so it keeps the
-		// chunk order); YALM_GEMV_ROWS=0 keeps the chunk order everywhere (A/B)
-		const bool rows_on = !ab_env("YALM_GEMV_ROWS") || atoi(ab_env("YALM_GEMV_ROWS")) != 0;
-		constexpr int W = THREADS / YALM_WAVE;
-		if (rows_on && p.n_groups % nb == 0 && (ngl * P::R) % W == 0 && ngl * P::R >= 2 * W)
-			return launch_rb_k<WT, P, NORM, THREADS, U, true>(p, x, normw, eps, nb, lds, st, tin);
+// The geometry of one single-row GEMV launch (launch_gemv: gemv_kernel when the row is no whole
+// number of CH-element chunks, else gemv_rb_kernel) over n_groups groups of R rows of n elements.
+// `def` is the kind's default {threads, U, workgroups per CU}, `want` what the caller overrides
+// (0: the default), with want.cus CUs (0: this device's) and want.rows (-1: whole-row mode where
+// rows_ok and the rows divide; 0: chunk order). Pure host arithmetic when want.cus > 0.
+struct GemvPlan {
+	bool generic, rows, xregs;
+	int threads, U, nb;    // block, loads in flight, grid
+	int ngl_min, ngl_max;  // groups of a workgroup, the fewest and the most
+	size_t lds;            // dynamic LDS bytes
+};
+static GemvPlan gemv_plan(int CH, bool q4, int R, bool rows_ok, bool norm, int n, int n_groups, const GemvCfg &def,
+                          const GemvCfg &want, bool tin) {
+	GemvPlan g{};
+	const size_t xl = q4 ? (size_t)xs_len<true>(n) : (size_t)xs_len<false>(n);
+	if (n % CH != 0) { // ragged K: generic kernel (tests / unusual shapes), one group per wave
+		constexpr int W = GEMV_THREADS / YALM_WAVE;
+		g.generic = true;
+		g.threads = GEMV_THREADS;
+		g.U = 4;
+		g.nb = (n_groups + W - 1) / W;
+		g.ngl_max = std::min(n_groups, W);
+		g.ngl_min = n_groups - (g.nb - 1) * W;
+		g.lds = xl * sizeof(float) + 64 * sizeof(float);
+		return g;
 	}
-	return launch_rb_k<WT, P, NORM, THREADS, U, false>(p, x, normw, eps, nb, lds, st, tin);
+	const int threads = want.threads ? want.threads : def.threads;
+	const int U = want.U ? want.U : def.U;
+	const int wpc = want.gpw ? want.gpw : def.gpw;
+	g.threads = threads == 256 || threads == 1024 ? threads : 512;
+	g.U = U == 2 || U == 8 ? U : 4;
+	const int W = g.threads / YALM_WAVE;
+	const int cus = want.cus > 0 ? want.cus : device_cu_count();
+	// an exchange consumer stages x from the exchange once per CU: one workgroup per CU
+	g.nb = std::max(1, std::min(n_groups, cus * (tin ? 1 : std::max(1, wpc))));
+	const int ngl = (n_groups + g.nb - 1) / g.nb;
+	g.ngl_max = ngl;
+	g.ngl_min = n_groups / g.nb;
+	g.lds = (xl + 64 + (size_t)ngl * R * W) * sizeof(float);
+	// every workgroup the same number of rows and a whole number of rows, at least 2,
+	// per wave (profiles/r3_gemv_rows.txt: W1|W3 fp16 39.4-40.0 -> 36.9 us, fp8 W2 13.4 ->
+	// 12.7-13.0; fp16 W2 with ONE 28-KB row per wave went 20.3 -> 21.3, so it keeps the
+	// chunk order); YALM_GEMV_ROWS=0 keeps the chunk order everywhere (A/B)
+	const bool rows_on = want.rows != 0 && (!ab_env("YALM_GEMV_ROWS") || atoi(ab_env("YALM_GEMV_ROWS")) != 0);
+	g.rows = rows_ok && rows_on && n_groups % g.nb == 0 && (ngl * R) % W == 0 && ngl * R >= 2 * W;
+	const int xpre = g.threads == 256    ? (norm ? xpre_n<true, 256>() : xpre_n<false, 256>())
+	                 : g.threads == 1024 ? (norm ? xpre_n<true, 1024>() : xpre_n<false, 1024>())
+	                                     : (norm ? xpre_n<true, 512>() : xpre_n<false, 512>());
+	g.xregs = !tin && n <= 4 * xpre * g.threads; // (the kernel's own test)
+	return g;
+}
+
+template <class WT, class P, bool NORM, int THREADS, int U>
+static int launch_rb_t(const P &p, const float *x, const float *normw, float eps, const GemvPlan &g, hipStream_t st,
+                       const TpX &tin) {
+	if constexpr (RowsMode<P>::value) {
+		if (g.rows)
+			return launch_rb_k<WT, P, NORM, THREADS, U, true>(p, x, normw, eps, g.nb, g.lds, st, tin);
+	}
+	return launch_rb_k<WT, P, NORM, THREADS, U, false>(p, x, normw, eps, g.nb, g.lds, st, tin);
 }
 
 // Per-kind, per-weight-type defaults from tools/sweep_gemv.py on MI355X
@@ -364,53 +411,65 @@ static GemvCfg default_rb_cfg(int kind) {
 	}
 }
 
+// the plan of launch_gemv<WT, P, NORM>
+template <class WT, class P>
+static GemvPlan gemv_plan_of(bool norm, int n, int n_groups, int kind, const GemvCfg &want, bool tin) {
+	return gemv_plan(YALM_WAVE * WT::EPL, WT::Q4, P::R, RowsMode<P>::value, norm, n, n_groups, default_rb_cfg<WT>(kind),
+	                 want, tin);
+}
+
 template <class WT, class P, bool NORM, int THREADS>
-static int launch_rb_u(const P &p, const float *x, const float *normw, float eps, int U, int wpc, hipStream_t st,
+static int launch_rb_u(const P &p, const float *x, const float *normw, float eps, const GemvPlan &g, hipStream_t st,
                        const TpX &tin) {
-	switch (U) {
+	switch (g.U) {
 	case 2:
-		return launch_rb_t<WT, P, NORM, THREADS, 2>(p, x, normw, eps, wpc, st, tin);
+		return launch_rb_t<WT, P, NORM, THREADS, 2>(p, x, normw, eps, g, st, tin);
 	case 8:
-		return launch_rb_t<WT, P, NORM, THREADS, 8>(p, x, normw, eps, wpc, st, tin);
+		return launch_rb_t<WT, P, NORM, THREADS, 8>(p, x, normw, eps, g, st, tin);
 	default:
-		return launch_rb_t<WT, P, NORM, THREADS, 4>(p, x, normw, eps, wpc, st, tin);
+		return launch_rb_t<WT, P, NORM, THREADS, 4>(p, x, normw, eps, g, st, tin);
 	}
+}
+
+template <class WT, class P, bool NORM>
+static int launch_rb_g(const P &p, const float *x, const float *normw, float eps, const GemvPlan &g, hipStream_t st,
+                       const TpX &tin) {
+	if (g.generic) {
+		set_err("internal: the row-block GEMV needs rows of whole chunks");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	if (g.threads == 256)
+		return launch_rb_u<WT, P, NORM, 256>(p, x, normw, eps, g, st, tin);
+	if (g.threads == 1024)
+		return launch_rb_u<WT, P, NORM, 1024>(p, x, normw, eps, g, st, tin);
+	return launch_rb_u<WT, P, NORM, 512>(p, x, normw, eps, g, st, tin);
 }
 
 template <class WT, class P, bool NORM>
 static int launch_rb(const P &p, const float *x, const float *normw, float eps, int kind, GemvCfg want,
                      hipStream_t st, const TpX &tin) {
-	const GemvCfg def = default_rb_cfg<WT>(kind);
-	const int threads = want.threads ? want.threads : def.threads;
-	const int U = want.U ? want.U : def.U;
-	const int wpc = want.gpw ? want.gpw : def.gpw;
-	if (threads == 256)
-		return launch_rb_u<WT, P, NORM, 256>(p, x, normw, eps, U, wpc, st, tin);
-	if (threads == 1024)
-		return launch_rb_u<WT, P, NORM, 1024>(p, x, normw, eps, U, wpc, st, tin);
-	return launch_rb_u<WT, P, NORM, 512>(p, x, normw, eps, U, wpc, st, tin);
+	return launch_rb_g<WT, P, NORM>(p, x, normw, eps, gemv_plan_of<WT, P>(NORM, p.n, p.n_groups, kind, want, tin.n > 0),
+	                                st, tin);
 }
 
 // tin: the exchange this launch consumes (tensor parallelism over IPC), default none
 template <class WT, class P, bool NORM>
 static int launch_gemv(const P &p, const float *x, const float *normw, float eps, int kind, GemvCfg want,
                        hipStream_t st, const TpX &tin = TpX{}) {
-	const size_t lds = (size_t)xs_len<WT::Q4>(p.n) * sizeof(float) + 64 * sizeof(float);
-	constexpr int CH = YALM_WAVE * WT::EPL;
-	if (p.n % CH != 0) { // ragged K: generic kernel (tests / unusual shapes)
+	const GemvPlan g = gemv_plan_of<WT, P>(NORM, p.n, p.n_groups, kind, want, tin.n > 0);
+	if (g.generic) {
 		if (tin.n > 0) {
 			set_err("tensor parallel: dim must be a multiple of 64 x elements per 16 bytes");
 			return YALM_ERR_UNSUPPORTED;
 		}
 		auto kern = gemv_kernel<WT, P, 4, NORM>;
-		if (lds > 65536)
-			HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-		const int blocks = (p.n_groups + GEMV_THREADS / YALM_WAVE - 1) / (GEMV_THREADS / YALM_WAVE);
-		hipLaunchKernelGGL(kern, dim3(blocks), dim3(GEMV_THREADS), lds, st, p, x, normw, eps, 1);
+		if (g.lds > 65536)
+			HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+		hipLaunchKernelGGL(kern, dim3(g.nb), dim3(GEMV_THREADS), g.lds, st, p, x, normw, eps, 1);
 		HIPCHK(hipGetLastError());
 		return YALM_OK;
 	}
-	return launch_rb<WT, P, NORM>(p, x, normw, eps, kind, want, st, tin);
+	return launch_rb_g<WT, P, NORM>(p, x, normw, eps, g, st, tin);
 }
 
 // The decoder's weight-streaming GEMVs: gemv_rb_kernel with the geometry set
@@ -2687,6 +2746,260 @@ extern "C" int yalm_matmul_rows(float *out, const float *x, const void *w, const
 	                   T, n, d, xstride, ostride, epilogue, act));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(out, dout.p, sizeof(float) * (size_t)T * ostride, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+// ---- the single-row GEMV by itself: its plan, and one launch_gemv call on host arrays
+static bool gemv_policy_qkv(int policy) {
+	return policy == YALM_GEMV_QKV || policy == YALM_GEMV_QKVB || policy == YALM_GEMV_QKVN;
+}
+template <class WT>
+static GemvPlan gemv_plan_dt(int policy, bool norm, int n, int n_groups, int kind, const GemvCfg &want) {
+	switch (policy) {
+	case YALM_GEMV_STORE2:
+		return gemv_plan_of<WT, PStore<WT, 2>>(norm, n, n_groups, kind, want, false);
+	case YALM_GEMV_RESIDUAL:
+		return gemv_plan_of<WT, PResidual<WT, 1>>(norm, n, n_groups, kind, want, false);
+	case YALM_GEMV_ADDTO:
+		return gemv_plan_of<WT, PAddTo<WT, 1>>(norm, n, n_groups, kind, want, false);
+	case YALM_GEMV_GLU:
+		return gemv_plan_of<WT, PGlu<WT, 1>>(norm, n, n_groups, kind, want, false);
+	case YALM_GEMV_QKV:
+		return gemv_plan_of<WT, PQKV<WT>>(norm, n, n_groups, kind, want, false);
+	case YALM_GEMV_QKVB:
+		return gemv_plan_of<WT, PQKVB<WT>>(norm, n, n_groups, kind, want, false);
+	case YALM_GEMV_QKVN:
+		return gemv_plan_of<WT, PQKVN<WT>>(norm, n, n_groups, kind, want, false);
+	default:
+		return gemv_plan_of<WT, PStore<WT, 1>>(norm, n, n_groups, kind, want, false);
+	}
+}
+
+static int gemv_cfg_check(const char *who, int dtype, int policy, int kind, int n, int threads, int unroll, int wpc,
+                          int cus, int rows) {
+	const std::string w(who);
+	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3,
+	       w + ": bad dtype");
+	ARGCHK(policy >= YALM_GEMV_STORE1 && policy <= YALM_GEMV_QKVN, w + ": bad policy");
+	ARGCHK(kind >= 0 && kind < GK_N, w + ": bad kind");
+	ARGCHK(n > 0 && n % 16 == 0, w + ": n must be a multiple of 16 (infer.cpp:66)");
+	ARGCHK(dtype != YALM_Q4 || n % 32 == 0, w + ": q4: n must be a multiple of 32");
+	ARGCHK((threads == 0 || threads == 256 || threads == 512 || threads == 1024) &&
+	           (unroll == 0 || unroll == 2 || unroll == 4 || unroll == 8) && wpc >= 0 && cus >= 0 &&
+	           (rows == -1 || rows == 0),
+	       w + ": threads 0 / 256 / 512 / 1024, unroll 0 / 2 / 4 / 8, wpc >= 0, cus >= 0, rows -1 / 0");
+	return YALM_OK;
+}
+
+extern "C" int yalm_gemv_plan(int dtype, int policy, int kind, int n, int n_groups, int norm, int threads, int unroll,
+                              int wpc, int cus, int rows, yalm_gemv_geometry *out) {
+	TRY(gemv_cfg_check("yalm_gemv_plan", dtype, policy, kind, n, threads, unroll, wpc, cus, rows));
+	ARGCHK(out && n_groups > 0, "yalm_gemv_plan: bad argument");
+	GemvCfg want{threads, unroll, wpc};
+	want.cus = cus;
+	want.rows = rows;
+	const GemvPlan g = DISPATCH_WT(dtype, gemv_plan_dt, policy, norm != 0, n, n_groups, kind, want);
+	out->generic = g.generic;
+	out->threads = g.threads;
+	out->unroll = g.U;
+	out->nb = g.nb;
+	out->rows = g.rows;
+	out->ngl_min = g.ngl_min;
+	out->ngl_max = g.ngl_max;
+	out->xregs = g.xregs;
+	out->lds = g.lds;
+	return YALM_OK;
+}
+
+namespace {
+struct GemvOneDev { // the device side of one yalm_gemv_one call
+	const float *x, *normw, *base, *bq, *bk, *bv;
+	const void *w, *w3, *wq, *wk, *wv;
+	float *out, *q_out, *raw;
+	uint16_t *kc, *vc;
+	const StepState *step;
+};
+} // namespace
+
+template <class WT, class P>
+static int gemv_one_launch(const yalm_gemv_args &a, const P &p, const GemvOneDev &v, const GemvCfg &cfg) {
+	if (a.norm)
+		return launch_gemv<WT, P, true>(p, v.x, v.normw, a.eps, a.kind, cfg, nullptr);
+	return launch_gemv<WT, P, false>(p, v.x, nullptr, 0.f, a.kind, cfg, nullptr);
+}
+template <class WT, class P>
+static void gemv_one_qkv(const yalm_gemv_args &a, const GemvOneDev &v, P &p) {
+	p.wq = (const char *)v.wq;
+	p.wk = (const char *)v.wk;
+	p.wv = (const char *)v.wv;
+	p.n = a.n;
+	p.q_dim = a.n_heads * a.head_dim;
+	p.kv_dim = a.n_kv_heads * a.head_dim;
+	p.head_dim = a.head_dim;
+	p.n_groups = (p.q_dim + 2 * p.kv_dim) / 2;
+	p.qkv_clip = a.qkv_clip;
+	p.inv_freq = nullptr; // (the epilogue reads the step's tables)
+	p.step = v.step;
+	p.q_out = v.q_out;
+	p.kcache = v.kc;
+	p.vcache = v.vc;
+}
+template <class WT>
+static int gemv_one_t(const yalm_gemv_args &a, const GemvOneDev &v, const GemvCfg &cfg) {
+	const char *w = (const char *)v.w;
+	switch (a.policy) {
+	case YALM_GEMV_STORE1: {
+		PStore<WT, 1> p{w, a.n, v.out, a.d};
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	case YALM_GEMV_STORE2: {
+		PStore<WT, 2> p{w, a.n, v.out, a.d / 2};
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	case YALM_GEMV_RESIDUAL: {
+		PResidual<WT, 1> p{w, a.n, v.out, a.d};
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	case YALM_GEMV_ADDTO: {
+		PAddTo<WT, 1> p{w, a.n, v.out, v.base, a.d};
+		return launch_gemv<WT, PAddTo<WT, 1>, false>(p, v.x, nullptr, 0.f, a.kind, cfg, nullptr);
+	}
+	case YALM_GEMV_GLU: {
+		if (a.act == YALM_SILU) {
+			PGlu<WT, 1> p{w, (const char *)v.w3, a.n, v.out, a.d};
+			return gemv_one_launch<WT>(a, p, v, cfg);
+		}
+		PGlu<WT, 0> p{w, (const char *)v.w3, a.n, v.out, a.d};
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	case YALM_GEMV_QKV: {
+		PQKV<WT> p;
+		gemv_one_qkv<WT>(a, v, p);
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	case YALM_GEMV_QKVB: {
+		PQKVB<WT> p;
+		gemv_one_qkv<WT>(a, v, p);
+		p.bq = v.bq;
+		p.bk = v.bk;
+		p.bv = v.bv;
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	default: {
+		PQKVN<WT> p;
+		gemv_one_qkv<WT>(a, v, p);
+		p.raw = v.raw;
+		return gemv_one_launch<WT>(a, p, v, cfg);
+	}
+	}
+}
+
+extern "C" int yalm_gemv_one(const yalm_gemv_args *ap) {
+	ARGCHK(ap, "yalm_gemv_one: bad argument");
+	const yalm_gemv_args &a = *ap;
+	TRY(gemv_cfg_check("yalm_gemv_one", a.dtype, a.policy, a.kind, a.n, a.threads, a.unroll, a.wpc, a.cus, a.rows));
+	const bool qkv = gemv_policy_qkv(a.policy);
+	ARGCHK(a.x && (!a.norm || a.normw), "yalm_gemv_one: bad argument");
+	ARGCHK(!a.norm || a.policy != YALM_GEMV_ADDTO, "yalm_gemv_one: PAddTo has no normalising form");
+	int n_groups = 0, q_dim = 0, kv_dim = 0;
+	if (qkv) {
+		ARGCHK(a.head_dim > 0 && a.head_dim % 2 == 0 && a.head_dim <= 256,
+		       "yalm_gemv_one: head_dim must be even and at most 256");
+		ARGCHK(a.n_heads > 0 && a.n_kv_heads > 0, "yalm_gemv_one: bad argument");
+		q_dim = a.n_heads * a.head_dim;
+		kv_dim = a.n_kv_heads * a.head_dim;
+		ARGCHK(q_dim % 2 == 0 && kv_dim % 2 == 0, "yalm_gemv_one: q and kv dims must be even");
+		ARGCHK(a.cache_rows >= 2 && a.kv_pos >= 0 && a.kv_pos < a.cache_rows,
+		       "yalm_gemv_one: cache_rows must be at least 2 and above kv_pos");
+		ARGCHK(a.kv_sink >= 0 && a.kv_sink <= a.kv_pos, "yalm_gemv_one: 0 <= kv_sink <= kv_pos");
+		ARGCHK(a.wq && a.wk && a.wv && a.rope && a.rope_sink && a.kcache && a.vcache && a.q_out && a.q_len >= q_dim,
+		       "yalm_gemv_one: bad argument");
+		ARGCHK(a.policy != YALM_GEMV_QKVB || (a.bq && a.bk && a.bv), "yalm_gemv_one: PQKVB needs bq, bk and bv");
+		ARGCHK(a.policy != YALM_GEMV_QKVN || (a.raw && a.raw_len >= q_dim + kv_dim),
+		       "yalm_gemv_one: PQKVN needs raw of q_dim + kv_dim floats");
+		n_groups = (q_dim + 2 * kv_dim) / 2;
+	} else {
+		ARGCHK(a.w && a.out && a.d > 0 && a.out_len >= a.d, "yalm_gemv_one: bad argument");
+		ARGCHK(a.policy != YALM_GEMV_STORE2 || a.d % 2 == 0, "yalm_gemv_one: PStore<., 2> needs an even row count");
+		ARGCHK(a.policy != YALM_GEMV_ADDTO || a.base, "yalm_gemv_one: PAddTo needs base");
+		ARGCHK(a.policy != YALM_GEMV_GLU || (a.w3 && (a.act == YALM_SILU || a.act == YALM_GELU)),
+		       "yalm_gemv_one: the GLU epilogue needs w3 and act GELU or SILU");
+		n_groups = a.policy == YALM_GEMV_STORE2 ? a.d / 2 : a.d;
+	}
+	GemvCfg cfg{a.threads, a.unroll, a.wpc};
+	cfg.cus = a.cus;
+	cfg.rows = a.rows;
+	const GemvPlan g = DISPATCH_WT(a.dtype, gemv_plan_dt, a.policy, a.norm != 0, a.n, n_groups, a.kind, cfg);
+	ARGCHK(g.lds <= MOE_LDS_BYTES, "yalm_gemv_one: x and the partial slots do not fit the LDS");
+	const size_t rb = yalm_row_bytes(a.dtype, a.n);
+	DevBuf dx, dn, dw, dw3, dq, dk, dv, dout, dbase, dqo, draw, dkc, dvc, dbq, dbk, dbv, dstep;
+	GemvOneDev v{};
+	TRY(up(dx, a.x, sizeof(float) * a.n));
+	v.x = (const float *)dx.p;
+	if (a.norm) {
+		TRY(up(dn, a.normw, sizeof(float) * a.n));
+		v.normw = (const float *)dn.p;
+	}
+	const size_t cache_bytes = sizeof(uint16_t) * (size_t)a.cache_rows * kv_dim;
+	if (qkv) {
+		TRY(up(dq, a.wq, rb * q_dim));
+		TRY(up(dk, a.wk, rb * kv_dim));
+		TRY(up(dv, a.wv, rb * kv_dim));
+		TRY(up(dqo, a.q_out, sizeof(float) * a.q_len));
+		TRY(up(dkc, a.kcache, cache_bytes));
+		TRY(up(dvc, a.vcache, cache_bytes));
+		StepState h{};
+		h.pos = (a.kv_pos + 1) % a.cache_rows; // another cache row: a row stored at pos, not kv_pos, shows
+		h.kv_sink = a.kv_sink;
+		h.kv_pos = a.kv_pos;
+		h.kv_len = a.kv_pos + 1;
+		memcpy(h.rope, a.rope, sizeof(float) * a.head_dim);
+		memcpy(h.rope_sink, a.rope_sink, sizeof(float) * a.head_dim);
+		TRY(up(dstep, &h, sizeof(h)));
+		v.wq = dq.p;
+		v.wk = dk.p;
+		v.wv = dv.p;
+		v.q_out = (float *)dqo.p;
+		v.kc = (uint16_t *)dkc.p;
+		v.vc = (uint16_t *)dvc.p;
+		v.step = (const StepState *)dstep.p;
+		if (a.policy == YALM_GEMV_QKVB) {
+			TRY(up(dbq, a.bq, sizeof(float) * q_dim));
+			TRY(up(dbk, a.bk, sizeof(float) * kv_dim));
+			TRY(up(dbv, a.bv, sizeof(float) * kv_dim));
+			v.bq = (const float *)dbq.p;
+			v.bk = (const float *)dbk.p;
+			v.bv = (const float *)dbv.p;
+		}
+		if (a.policy == YALM_GEMV_QKVN) {
+			TRY(up(draw, a.raw, sizeof(float) * a.raw_len));
+			v.raw = (float *)draw.p;
+		}
+	} else {
+		TRY(up(dw, a.w, rb * a.d));
+		v.w = dw.p;
+		if (a.policy == YALM_GEMV_GLU) {
+			TRY(up(dw3, a.w3, rb * a.d));
+			v.w3 = dw3.p;
+		}
+		TRY(up(dout, a.out, sizeof(float) * a.out_len));
+		v.out = (float *)dout.p;
+		if (a.policy == YALM_GEMV_ADDTO) {
+			TRY(up(dbase, a.base, sizeof(float) * a.d));
+			v.base = (const float *)dbase.p;
+		}
+	}
+	TRY(DISPATCH_WT(a.dtype, gemv_one_t, a, v, cfg));
+	HIPCHK(hipDeviceSynchronize());
+	if (qkv) {
+		HIPCHK(hipMemcpy(a.q_out, dqo.p, sizeof(float) * a.q_len, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(a.kcache, dkc.p, cache_bytes, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(a.vcache, dvc.p, cache_bytes, hipMemcpyDeviceToHost));
+		if (a.policy == YALM_GEMV_QKVN)
+			HIPCHK(hipMemcpy(a.raw, draw.p, sizeof(float) * a.raw_len, hipMemcpyDeviceToHost));
+	} else {
+		HIPCHK(hipMemcpy(a.out, dout.p, sizeof(float) * a.out_len, hipMemcpyDeviceToHost));
+	}
 	return YALM_OK;
 }
 

@@ -82,6 +82,26 @@ class SpecStats(ctypes.Structure):
                 ("launches_per_step", c_int)]
 
 
+class GemvGeometry(ctypes.Structure):
+    """yalm_gemv_geometry: the plan of one single-row GEMV launch."""
+
+    _fields_ = [(n, c_int) for n in ("generic", "threads", "unroll", "nb", "rows", "ngl_min", "ngl_max", "xregs")] + [
+        ("lds", c_size_t)]
+
+
+class GemvArgs(ctypes.Structure):
+    """yalm_gemv_args: one single-row GEMV launch on host arrays (yalm_gemv_one)."""
+
+    _fields_ = ([(n, c_int) for n in ("dtype", "policy", "kind", "n", "d", "norm", "act")] + [("eps", c_float)]
+                + [(n, c_int) for n in ("threads", "unroll", "wpc", "cus", "rows")]
+                + [(n, c_void_p) for n in ("x", "normw", "w", "w3", "wq", "wk", "wv", "out", "base")]
+                + [(n, c_int) for n in ("out_len", "n_heads", "n_kv_heads", "head_dim", "kv_sink", "kv_pos",
+                                        "cache_rows")]
+                + [("qkv_clip", c_float)]
+                + [(n, c_void_p) for n in ("rope", "rope_sink", "kcache", "vcache", "q_out", "raw")]
+                + [("q_len", c_int), ("raw_len", c_int)] + [(n, c_void_p) for n in ("bq", "bk", "bv")])
+
+
 class RopeScaling(ctypes.Structure):
     """yalm_rope_scaling: type 0 none, 1 llama3."""
 
@@ -189,6 +209,8 @@ _sig("yalm_decoder_set_qkv_bias", c_int, [c_void_p, c_void_p, c_void_p, c_void_p
 _sig("yalm_decoder_set_qk_norm", c_int, [c_void_p, c_void_p, c_void_p])
 _sig("yalm_rows_plan", c_int, [c_int] * 5 + [ctypes.POINTER(c_int)] * 4 + [ctypes.POINTER(c_size_t)])
 _sig("yalm_matmul_rows", c_int, [c_void_p] * 5 + [c_float] + [c_int] * 8)
+_sig("yalm_gemv_plan", c_int, [c_int] * 11 + [ctypes.POINTER(GemvGeometry)])
+_sig("yalm_gemv_one", c_int, [ctypes.POINTER(GemvArgs)])
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -209,6 +231,7 @@ EXPORTED = [
     "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
     "yalm_decoder_set_qk_norm",
     "yalm_rows_plan", "yalm_matmul_rows",
+    "yalm_gemv_plan", "yalm_gemv_one",
     "yalm_attn_prefill_rows",
 ]
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
@@ -441,6 +464,85 @@ def matmul_rows(out, x, w, dtype: int, epilogue: int = ROWS_STORE, w3=None, norm
                                None if normw is None else _ptr(normw), eps, T, n, d, x.shape[1], out.shape[1], dtype,
                                epilogue, act))
     return out
+
+
+# yalm_gemv_plan / yalm_gemv_one policies and launch kinds (include/yalm_hip.h, decoder.h GK_*)
+GEMV_STORE1, GEMV_STORE2, GEMV_RESIDUAL, GEMV_ADDTO, GEMV_GLU, GEMV_QKV, GEMV_QKVB, GEMV_QKVN = range(8)
+GK_QKV, GK_WO, GK_GLU, GK_W2, GK_CLS = range(5)
+
+
+def gemv_plan(dtype: int, policy: int, kind: int, n: int, n_groups: int, norm: bool = False, threads: int = 0,
+              unroll: int = 0, wpc: int = 0, cus: int = 0, rows: int = -1) -> dict:
+    """The geometry of one single-row GEMV launch (yalm_gemv_plan, the function the launcher itself
+    calls; host arithmetic with cus > 0): generic, threads, unroll, nb, rows, ngl_min, ngl_max,
+    xregs, lds."""
+    g = GemvGeometry()
+    check(lib.yalm_gemv_plan(dtype, policy, kind, n, n_groups, int(norm), threads, unroll, wpc, cus, rows,
+                             ctypes.byref(g)))
+    return {k: int(getattr(g, k)) for k, _ in GemvGeometry._fields_}
+
+
+def gemv_one(dtype: int, policy: int, kind: int, n: int, x, *, d: int = 0, w=None, w3=None, out=None, base=None,
+             normw=None, eps: float = 0.0, act: int = M.SILU, threads: int = 0, unroll: int = 0, wpc: int = 0,
+             cus: int = 0, rows: int = -1, wq=None, wk=None, wv=None, n_heads: int = 0, n_kv_heads: int = 0,
+             head_dim: int = 0, qkv_clip: float = 0.0, kv_sink: int = 0, kv_pos: int = 0, rope=None, rope_sink=None,
+             kcache=None, vcache=None, q_out=None, raw=None, bq=None, bk=None, bv=None) -> dict:
+    """One single-row GEMV launch through the decoder's launcher (yalm_gemv_one). Weights are the
+    stored rows (q4 / e4m3: uint8 rows of row_bytes(dtype, n)). out / q_out / raw (f32) and kcache /
+    vcache (uint16, (cache_rows, kv_dim)) are given as they stand before the launch and returned
+    whole, as copies, in a dict under the same names; the arguments are not written."""
+    keep = []
+
+    def arr(a, dt, copy=False):
+        if a is None:
+            return None, None
+        a = np.array(a, dtype=dt, order="C") if copy else np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a, _ptr(a)
+
+    def wts(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a)
+        rb = lib.yalm_row_bytes(dtype, n)  # (0: a row length the library refuses)
+        assert rb == 0 or a.nbytes == a.shape[0] * rb, "weights: rows of row_bytes(dtype, n)"
+        keep.append(a)
+        return _ptr(a)
+
+    a = GemvArgs()
+    a.dtype, a.policy, a.kind, a.n, a.d, a.norm, a.act, a.eps = dtype, policy, kind, n, d, int(normw is not None), act, eps
+    a.threads, a.unroll, a.wpc, a.cus, a.rows = threads, unroll, wpc, cus, rows
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert x.size == n and (normw is None or np.asarray(normw).size == n)
+    a.x = _ptr(x)
+    a.normw = arr(normw, np.float32)[1]
+    a.w, a.w3, a.wq, a.wk, a.wv = wts(w), wts(w3), wts(wq), wts(wk), wts(wv)
+    res = {}
+    res["out"], a.out = arr(out, np.float32, copy=True)
+    a.out_len = 0 if out is None else res["out"].size
+    assert base is None or np.asarray(base).size == d
+    a.base = arr(base, np.float32)[1]
+    a.n_heads, a.n_kv_heads, a.head_dim, a.kv_sink, a.kv_pos = n_heads, n_kv_heads, head_dim, kv_sink, kv_pos
+    a.qkv_clip = qkv_clip
+    for name, v in (("rope", rope), ("rope_sink", rope_sink)):
+        assert v is None or np.asarray(v).size == head_dim
+        setattr(a, name, arr(v, np.float32)[1])
+    kv_dim, q_dim = n_kv_heads * head_dim, n_heads * head_dim
+    res["kcache"], a.kcache = arr(kcache, np.uint16, copy=True)
+    res["vcache"], a.vcache = arr(vcache, np.uint16, copy=True)
+    a.cache_rows = 0
+    if kcache is not None and kv_dim > 0:
+        assert vcache is not None and res["kcache"].size == res["vcache"].size and res["kcache"].size % kv_dim == 0
+        a.cache_rows = res["kcache"].size // kv_dim
+    res["q_out"], a.q_out = arr(q_out, np.float32, copy=True)
+    a.q_len = 0 if q_out is None else res["q_out"].size
+    res["raw"], a.raw = arr(raw, np.float32, copy=True)
+    a.raw_len = 0 if raw is None else res["raw"].size
+    for name, v, ln in (("bq", bq, q_dim), ("bk", bk, kv_dim), ("bv", bv, kv_dim)):
+        assert v is None or np.asarray(v).size == ln
+        setattr(a, name, arr(v, np.float32)[1])
+    check(lib.yalm_gemv_one(ctypes.byref(a)))
+    return {k: v for k, v in res.items() if v is not None}
 
 
 def attn_prefill(q, kc, vc, T, pos0, n_heads, n_kv_heads, head_dim) -> np.ndarray:
