@@ -240,7 +240,9 @@ int yalm_get_logits(yalm_decoder d, float *host);
  * the decoder's current logits, with the parameters of the last such call (before any:
  * temperature 1, no truncation) and its first uniform; it commits into a scratch step
  * state, not the decoder's; 11 = the q / k norm launch (yalm_decoder_set_qk_norm, which it
- * needs) on what the last QKV launch left. Used by bench.py for the roofline of the
+ * needs) on what the last QKV launch left; 12 / 13 = the draw and the accept launch of a 4-row
+ * sampled speculative step, 14 = the verify launch of a greedy one, on the rows' current logits
+ * and a scratch step state (decoders with a multi-row form). Used by bench.py for the roofline of the
  * dominant kernel. */
 int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms);
 /* The same-process streaming envelope: average ms of one pure read-only pass over
@@ -496,7 +498,7 @@ int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms);
  * unknown key is YALM_ERR_ARG. */
 int yalm_set_prefill_forms(yalm_decoder d, const char *spec);
 
-/* ---------------- multi-row forward and speculative greedy decode ----------------
+/* ---------------- multi-row forward and speculative greedy / sampled decode ----------------
  * Dense decoders on one GPU with f32, f16, fp8 (E5M2) or e4m3 weights. YALM_ERR_UNSUPPORTED, with a
  * yalm_last_error naming the reason: q4 weights, mixture-of-experts decoders
  * (yalm_decoder_create_moe), tensor-parallel decoders (yalm_decoder_create_tp / _tp_ipc). */
@@ -533,8 +535,8 @@ typedef struct yalm_spec {
 typedef struct yalm_spec_stats {
 	int spec_steps;        /* multi-row steps run */
 	int accepted_drafts;   /* drafts whose token was delivered: spec_steps + accepted_drafts + plain_steps == n_tokens */
-	int plain_steps;       /* plain greedy steps (at and past the window's end) */
-	int launches_per_step; /* kernel launches of one multi-row step: 4 + n_layers * (4 + rows) */
+	int plain_steps;       /* plain steps (at and past the window's end) */
+	int launches_per_step; /* kernel launches of one multi-row step: 4 + n_layers * (4 + rows), sampled: 5 + ... */
 } yalm_spec_stats;
 /* The contract of yalm_generate_greedy: feeds `token` at `pos`, writes exactly n_tokens tokens to
  * out_tokens (host), and the decoder then continues at pos + n_tokens (yalm_device_step,
@@ -548,6 +550,39 @@ typedef struct yalm_spec_stats {
  * the token buffer (65536), a context that does not end with token. */
 int yalm_generate_speculative(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
                               const int *context, int n_context, int *out_tokens, yalm_spec_stats *stats);
+/* Speculative sampled decode: yalm_generate_speculative with every row drawn by the rule of
+ * yalm_generate_sampled instead of its argmax. Row t of a step is drawn with
+ * uniforms[p + t], p = the tokens produced so far: the uniform of the output index the row would
+ * fill. Draft d_k is accepted iff it equals the token drawn from row k - 1 (the drafter proposes
+ * one token, not a distribution, so there is nothing to resample: a draft is accepted with
+ * probability p(d_k)). Row k's input is then the token the plain sampled loop would have fed at
+ * that index and its draw uses the uniform that loop would have used: the tokens are
+ * yalm_generate_sampled's for the same uniforms, as the greedy call's are yalm_generate_greedy's.
+ * Caveat: that equality holds when both paths see the same logits. The multi-row GEMV and the
+ * decode GEMV sum in different orders, so a draw whose target lies within that rounding of a
+ * boundary of the cumulative distribution can land on the neighbouring token in one path and not
+ * in the other (both are valid draws; greedy has the same property at near-ties).
+ * A step is: draft, rows, one launch of `rows` workgroups that draw (csrc/spec.h,
+ * spec_sample_rows_kernel), one that accepts (spec_accept_kernel): 5 + n_layers * (4 + rows)
+ * launches. Otherwise the contract of yalm_generate_speculative: batches with one count
+ * read-back each, the overshoot dropped (rows past output index n_tokens - 1 read the last
+ * uniform and their tokens are not delivered, so a following call's uniforms start at its own
+ * index 0), a context that ends with `token`, and from the first position with pos + rows >
+ * max_seq_len the plain steps of yalm_generate_sampled, which read uniforms[p] like every other
+ * draw. uniforms: host, n_tokens values in [0, 1]. Same scope and refusals as the greedy call
+ * (YALM_ERR_UNSUPPORTED: q4, mixture-of-experts, tensor-parallel); YALM_ERR_ARG: its argument
+ * errors and those of yalm_generate_sampled (temperature, top_k, top_p, a uniform outside
+ * [0, 1], a vocabulary above 131072). */
+int yalm_generate_speculative_sampled(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
+                                      const yalm_sampling *s, const float *uniforms, const int *context,
+                                      int n_context, int *out_tokens, yalm_spec_stats *stats);
+/* Test hook (host pointers, synchronous, no decoder): the draw and the accept launch of a sampled
+ * speculative step exactly as the loop makes them, on logits [T][n] (stride n, n <= 131072, 1 <=
+ * T <= 4) with no token produced yet: row t is drawn with uniforms[t]; drafts[k - 1] = d_k for k
+ * = 1..T-1, -1 for none (may be NULL when T == 1). drawn_out [T]: every row's token; kept_out
+ * [T] (may be NULL): every row's kept-set size; *accepted_out = a, the tokens the step yields. */
+int yalm_spec_sample_rows(const float *logits, int n, int T, const yalm_sampling *s, const float *uniforms,
+                          const int *drafts, int *drawn_out, int *kept_out, int *accepted_out);
 /* Test hook (host pointers, synchronous, no decoder): the drafter kernel on history[0, m),
  * 1 <= m <= 131072; drafts_out[k - 1] = d_k for k = 1..rows-1, -1 for none. */
 int yalm_spec_draft(const int *history, int m, int rows, int ngram_max, int ngram_min, int *drafts_out);

@@ -80,6 +80,8 @@ __global__ __launch_bounds__(256) void step_begin_kernel(StepState *st, const vo
 // Greedy sampling on the device (sampler.cpp:27-38: strict '>' scan, so the
 // FIRST maximum wins). Feeds the result back as the next step's token.
 // First max of logits[0, n) over one workgroup of 1024 threads: (value, index) in thread 0.
+// VEC = false: logits is not 16-byte aligned, every element goes through the one-by-one loop.
+template <bool VEC = true>
 __device__ __forceinline__ void argmax_block(const float *__restrict__ logits, int n, float &best_out, int &idx_out) {
 	__shared__ float sv[16];
 	__shared__ int si[16];
@@ -90,7 +92,7 @@ __device__ __forceinline__ void argmax_block(const float *__restrict__ logits, i
 	// Thread t owns elements [4t, 4t+4) of each 4*blockDim.x span: ascending
 	// per thread, so the strict '>' keeps its first max.
 	constexpr int B = 8;
-	const int n4 = n & ~3;
+	const int n4 = VEC ? n & ~3 : 0;
 	for (int base = 0; base < n4; base += B * 4 * (int)blockDim.x) {
 		float4_t v[B];
 #pragma unroll

@@ -80,7 +80,8 @@ __device__ __forceinline__ unsigned long long smp_q(float l, float m, float T) {
 
 // f(i, l) for every element this thread owns, ascending; after the thread's 4 elements of span s, g(s).
 // Both are called by every thread for every span (g may hold wave-wide operations).
-template <class F, class G>
+// VEC: logits is 16-byte aligned (float4 loads); else the same elements one by one.
+template <bool VEC, class F, class G>
 __device__ __forceinline__ void smp_for_each(const float *__restrict__ logits, int n, F f, G g) {
 	constexpr int B = 4; // spans in flight
 	const int nsp = (n + SMP_SPAN - 1) / SMP_SPAN;
@@ -89,7 +90,7 @@ __device__ __forceinline__ void smp_for_each(const float *__restrict__ logits, i
 #pragma unroll
 		for (int k = 0; k < B; ++k) {
 			const int i0 = (s0 + k) * SMP_SPAN + 4 * (int)threadIdx.x;
-			if (i0 + 3 < n) {
+			if (VEC && i0 + 3 < n) {
 				const float4_t x = *(const float4_t *)(logits + i0);
 #pragma unroll
 				for (int e = 0; e < 4; ++e)
@@ -203,7 +204,7 @@ __device__ __forceinline__ bool smp_crossing(SampleShared &sh, int nb, unsigned 
 // candidate list in LDS (any order: histograms do not care); when they fit, the third pass
 // reads the list, and a later select whose set lies inside it (from_list) reads nothing else.
 // Called by all threads.
-template <bool BY_W, class P>
+template <bool BY_W, bool VEC, class P>
 __device__ __forceinline__ bool smp_select(const float *__restrict__ logits, int n, float m, float T, P in_set,
                                            bool from_list, unsigned long long &target, double frac,
                                            unsigned long long &set_w, SampleShared &sh, unsigned &K,
@@ -249,7 +250,7 @@ __device__ __forceinline__ bool smp_select(const float *__restrict__ logits, int
 			for (int j = threadIdx.x; j < nc; j += SMP_THREADS)
 				body(sh.cand_i[j], sh.cand_l[j]);
 		} else {
-			smp_for_each(logits, n, body, [](int) {});
+			smp_for_each<VEC>(logits, n, body, [](int) {});
 		}
 		__syncthreads();
 		unsigned long long tw = 0;
@@ -271,14 +272,14 @@ __device__ __forceinline__ bool smp_select(const float *__restrict__ logits, int
 }
 
 // Per-span sums of val(i, l) into sh.span; returns their total. Called by all threads.
-template <class V>
+template <bool VEC, class V>
 __device__ __forceinline__ unsigned long long smp_span_sums(const float *__restrict__ logits, int n, V val,
                                                             SampleShared &sh) {
 	if (threadIdx.x < SMP_MAX_SPANS)
 		sh.span[threadIdx.x] = 0ull;
 	__syncthreads();
 	unsigned long long acc = 0;
-	smp_for_each(
+	smp_for_each<VEC>(
 	    logits, n, [&](int i, float l) { acc += val(i, l); },
 	    [&](int s) {
 		    if (__ballot(acc != 0ull)) {
@@ -337,35 +338,32 @@ __device__ __forceinline__ int smp_locate(const float *__restrict__ logits, int 
 	return sh.res_idx;
 }
 
-// One sampled token from logits[0, n), n <= SMP_MAX_N: the uniform is uniforms[st->n_gen]
-// (clamped to u_cap - 1), the token is committed like the greedy one (argmax_commit).
-// kept_out (may be null): [st->n_gen] = the kept-set size; weights_out (may be null): every q_i.
-__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__restrict__ logits, int n,
-                                                             const SampleParams *__restrict__ prm,
-                                                             const float *__restrict__ uniforms, int u_cap,
-                                                             StepState *st, int *__restrict__ tokens_out, int cap,
-                                                             int *__restrict__ kept_out,
-                                                             unsigned long long *__restrict__ weights_out) {
-	__shared__ SampleShared sh;
-	const int gen = st->n_gen; // read by every thread before thread 0 commits
-	{
-		float b = 0.0f;
-		int idx = 0;
-		argmax_block(logits, n, b, idx);
-		if (threadIdx.x == 0) {
-			sh.m = b;
-			sh.amax = idx;
-		}
+// The first-maximum of logits[0, n) into sh.m / sh.amax, visible to every thread on return.
+template <bool VEC>
+__device__ __forceinline__ void smp_first_max(const float *__restrict__ logits, int n, SampleShared &sh) {
+	float b = 0.0f;
+	int idx = 0;
+	argmax_block<VEC>(logits, n, b, idx);
+	if (threadIdx.x == 0) {
+		sh.m = b;
+		sh.amax = idx;
 	}
 	__syncthreads();
-	const float m = sh.m, T = prm->temperature, top_p = prm->top_p;
-	const int amax = sh.amax, top_k = prm->top_k;
-	const int ui = gen < 0 ? 0 : gen < u_cap ? gen : u_cap - 1;
-	const float u = uniforms[ui];
-	if (weights_out)
-		smp_for_each(
-		    logits, n, [&](int i, float l) { weights_out[i] = smp_q(l, m, T); }, [](int) {});
+}
 
+struct SampleDraw {
+	int token;
+	long long kept; // the kept-set size
+};
+
+// The rule's draw from logits[0, n), n <= SMP_MAX_N, with the uniform u, after smp_first_max on
+// the same logits. sh is this workgroup's alone. VEC: logits is 16-byte aligned. Called by all
+// threads; every thread gets the result.
+template <bool VEC>
+__device__ __forceinline__ SampleDraw sample_row(const float *__restrict__ logits, int n, const SampleParams prm,
+                                                 float u, SampleShared &sh) {
+	const float m = sh.m, T = prm.temperature, top_p = prm.top_p;
+	const int amax = sh.amax, top_k = prm.top_k;
 	// the kept set {key > K or (key == K and i <= istar)}; everything to begin with
 	unsigned K = 0;
 	int istar = INT_MAX;
@@ -375,12 +373,12 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__rest
 	if (top_k > 0 && top_k < n) {
 		target = (unsigned long long)top_k;
 		unsigned K1 = 0;
-		smp_select<false>(
+		smp_select<false, VEC>(
 		    logits, n, m, T, [](int, unsigned) { return true; }, false, target, -1.0, set_w, sh, K1, ca, wa, ct, wt);
 		const unsigned long long r = (unsigned long long)top_k - ca; // of the ct elements equal to K1
 		if (r < ct) {
 			auto tie = [&](int, float l) { return smp_key(l) == K1 ? 1ull : 0ull; };
-			smp_span_sums(logits, n, tie, sh);
+			smp_span_sums<VEC>(logits, n, tie, sh);
 			istar = smp_locate(logits, n, tie, r, sh);
 		}
 		K = K1;
@@ -392,7 +390,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__rest
 		const int i1 = istar;
 		unsigned K2 = 0;
 		target = 0;
-		const bool ok = smp_select<true>(
+		const bool ok = smp_select<true, VEC>(
 		    logits, n, m, T, [&](int i, unsigned key) { return key > K1 || (key == K1 && i <= i1); }, have_list,
 		    target, (double)top_p, set_w, sh, K2, ca, wa, ct, wt);
 		if (!ok) { // S_k == 0: need is 0, the empty prefix
@@ -404,7 +402,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__rest
 			r = r < 1 ? 1 : r > ct ? ct : r;
 			if (r < ct) {
 				auto tie = [&](int, float l) { return smp_key(l) == K2 ? 1ull : 0ull; };
-				smp_span_sums(logits, n, tie, sh);
+				smp_span_sums<VEC>(logits, n, tie, sh);
 				istar = smp_locate(logits, n, tie, r, sh);
 			} else if (K2 != K1) {
 				istar = INT_MAX;
@@ -420,16 +418,39 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__rest
 			const unsigned key = smp_key(l);
 			return key > K || (key == K && i <= istar) ? smp_q(l, m, T) : 0ull;
 		};
-		const unsigned long long S = smp_span_sums(logits, n, val, sh);
+		const unsigned long long S = smp_span_sums<VEC>(logits, n, val, sh);
 		if (S > 0) {
 			const int idx = smp_locate(logits, n, val, smp_frac_target((double)u, S), sh);
 			if (idx >= 0)
 				token = idx;
 		}
 	}
+	return SampleDraw{token, kept};
+}
+
+// One sampled token from logits[0, n), n <= SMP_MAX_N: the uniform is uniforms[st->n_gen]
+// (clamped to u_cap - 1), the token is committed like the greedy one (argmax_commit).
+// kept_out (may be null): [st->n_gen] = the kept-set size; weights_out (may be null): every q_i.
+__global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__restrict__ logits, int n,
+                                                             const SampleParams *__restrict__ prm,
+                                                             const float *__restrict__ uniforms, int u_cap,
+                                                             StepState *st, int *__restrict__ tokens_out, int cap,
+                                                             int *__restrict__ kept_out,
+                                                             unsigned long long *__restrict__ weights_out) {
+	__shared__ SampleShared sh;
+	const int gen = st->n_gen; // read by every thread before thread 0 commits
+	smp_first_max<true>(logits, n, sh);
+	const float m = sh.m, T = prm->temperature, top_p = prm->top_p;
+	const int top_k = prm->top_k;
+	const int ui = gen < 0 ? 0 : gen < u_cap ? gen : u_cap - 1;
+	const float u = uniforms[ui];
+	if (weights_out)
+		smp_for_each<true>(
+		    logits, n, [&](int i, float l) { weights_out[i] = smp_q(l, m, T); }, [](int) {});
+	const SampleDraw r = sample_row<true>(logits, n, SampleParams{T, top_k, top_p}, u, sh);
 	if (threadIdx.x == 0) {
 		if (kept_out && gen >= 0 && gen < cap)
-			kept_out[gen] = (int)kept;
-		argmax_commit(st, token, tokens_out, cap);
+			kept_out[gen] = (int)r.kept;
+		argmax_commit(st, r.token, tokens_out, cap);
 	}
 }

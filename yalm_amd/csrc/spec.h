@@ -1,4 +1,4 @@
-// spec.h — speculative greedy decode: the per-row step states of a multi-row forward
+// spec.h — speculative greedy and sampled decode: the per-row step states of a multi-row forward
 // (gemv_rows.h), the n-gram drafter and the verify / accept launch. Everything is plain kernel
 // work on one stream: no cross-workgroup hand-off, no spin, no wait inside a launch.
 //
@@ -8,10 +8,17 @@
 // first-maximum argmax of every row (argmax_block, the rule of argmax_kernel) and accepts the
 // longest prefix of drafts that equal the argmax of the row before them, so the tokens are
 // those of plain greedy decode by construction.
+//
+// The sampled step ends with two launches in the verify launch's place: T workgroups draw every
+// row's token by the sampling rule with the uniform of the output index the row would fill
+// (spec_sample_rows_kernel), then one accepts the drafts that equal the draw of the row before
+// them (spec_accept_kernel). The drafter proposes one token, not a distribution, so there is
+// nothing to resample, and the tokens are those of the plain sampled loop for the same uniforms.
 #pragma once
 
 #include "device_common.h"
 #include "misc_kernels.h"
+#include "sampler.h"
 
 #define SPEC_MAX_ROWS 4
 #define SPEC_MAX_NGRAM 4
@@ -23,6 +30,7 @@ struct SpecState {
 	int draft[SPEC_MAX_ROWS]; // draft[k], k >= 1: the drafted token of row k, -1 = none (the row is fed token 0)
 	int steps;                // speculative steps run since the loop began
 	int accepted;             // drafts accepted since the loop began
+	int drawn[SPEC_MAX_ROWS]; // the sampled loop: the token drawn from each row (spec_sample_rows_kernel)
 };
 
 // yalm_forward_rows: the host's row tokens (kernel arguments: no host buffer to outlive the call).
@@ -154,6 +162,25 @@ __global__ __launch_bounds__(SPEC_DRAFT_THREADS) void spec_draft_test_kernel(con
 	spec_draft_body(hist, m, hist, 0, T, gmax, gmin, nullptr, 0, draft);
 }
 
+// Accept, by one thread: with tk[t] the token chosen from row t (the argmax, or the draw),
+// a = 1 + the longest prefix of drafts with draft[k] == tk[k - 1] (a none draft never matches);
+// tk[0..a-1] are appended to the token buffer and the next step is (tk[a - 1], pos + a).
+__device__ __forceinline__ void spec_accept_commit(const int *tk, int T, StepState *st, SpecState *sp,
+                                                   int *__restrict__ tokens_out, int cap) {
+	int a = 1;
+	while (a < T && sp->draft[a] >= 0 && sp->draft[a] == tk[a - 1])
+		++a;
+	const int k = st->n_gen;
+	for (int j = 0; j < a; ++j)
+		if (k + j < cap)
+			tokens_out[k + j] = tk[j];
+	st->n_gen = k + a;
+	st->token = tk[a - 1];
+	st->pos = st->pos + a;
+	sp->steps = sp->steps + 1;
+	sp->accepted = sp->accepted + (a - 1);
+}
+
 // Verify and accept, one launch of one workgroup: am_t = the first-maximum argmax of row t's
 // logits; a = 1 + the longest prefix of drafts with draft[k] == am[k - 1] (a none draft never
 // matches); am[0..a-1] are appended to the token buffer and the next step is (am[a - 1], pos + a).
@@ -169,20 +196,43 @@ __global__ __launch_bounds__(1024) void spec_verify_kernel(const float *__restri
 			am[t] = idx;
 		__syncthreads(); // argmax_block's LDS scratch is reused by the next row
 	}
+	if (threadIdx.x == 0)
+		spec_accept_commit(am, T, st, sp, tokens_out, cap);
+}
+
+// The sampled step's draws (sampler.h, the rule of sample_kernel): workgroup t draws row t's
+// token from logits + t * stride with uniforms[n_gen + t] (clamped to [0, u_cap - 1]) into
+// sp->drawn[t]; n_gen is read, not written. Row t is thereby drawn with the uniform of the
+// output index it would fill. One workgroup per row, each with its own SampleShared; nothing
+// passes between them. VEC: every row is 16-byte aligned (stride % 4 == 0); else the rows are
+// read element by element. kept_out (may be null): [t] = the kept-set size of row t.
+template <bool VEC>
+__global__ __launch_bounds__(SMP_THREADS) void spec_sample_rows_kernel(const float *__restrict__ logits, int n,
+                                                                       int stride,
+                                                                       const SampleParams *__restrict__ prm,
+                                                                       const float *__restrict__ uniforms, int u_cap,
+                                                                       const StepState *__restrict__ st, SpecState *sp,
+                                                                       int *__restrict__ kept_out) {
+	__shared__ SampleShared sh;
+	const int t = blockIdx.x;
+	const float *__restrict__ row = logits + (size_t)t * stride;
+	const long long gi = (long long)st->n_gen + t;
+	const int ui = gi < 0 ? 0 : gi < u_cap ? (int)gi : u_cap - 1;
+	smp_first_max<VEC>(row, n, sh);
+	const SampleParams p{prm->temperature, prm->top_k, prm->top_p};
+	const SampleDraw r = sample_row<VEC>(row, n, p, uniforms[ui], sh);
 	if (threadIdx.x == 0) {
-		int a = 1;
-		while (a < T && sp->draft[a] >= 0 && sp->draft[a] == am[a - 1])
-			++a;
-		const int k = st->n_gen;
-		for (int j = 0; j < a; ++j)
-			if (k + j < cap)
-				tokens_out[k + j] = am[j];
-		st->n_gen = k + a;
-		st->token = am[a - 1];
-		st->pos = st->pos + a;
-		sp->steps = sp->steps + 1;
-		sp->accepted = sp->accepted + (a - 1);
+		sp->drawn[t] = r.token;
+		if (kept_out)
+			kept_out[t] = (int)r.kept;
 	}
+}
+
+// The launch after it: spec_verify_kernel's tail over the drawn tokens.
+__global__ __launch_bounds__(64) void spec_accept_kernel(int T, StepState *st, SpecState *sp,
+                                                         int *__restrict__ tokens_out, int cap) {
+	if (threadIdx.x == 0)
+		spec_accept_commit(sp->drawn, T, st, sp, tokens_out, cap);
 }
 
 // After a batch that overshot the requested count: the device continues at (token, pos) with

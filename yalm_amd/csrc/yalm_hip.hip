@@ -2157,25 +2157,30 @@ extern "C" int yalm_spec_draft(const int *history, int m, int rows, int ngram_ma
 	return YALM_OK;
 }
 
-extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
-                                         const int *context, int n_context, int *out_tokens,
-                                         yalm_spec_stats *stats) {
-	ARGCHK(d && cfg && (out_tokens || n_tokens == 0), "yalm_generate_speculative: null argument");
-	TRY(rows_supported(d, "yalm_generate_speculative"));
-	ARGCHK(token >= 0 && token < d->vocab_full && pos >= 0 && n_tokens >= 0,
-	       "yalm_generate_speculative: bad token/pos/n_tokens");
-	ARGCHK(cfg->rows >= 2 && cfg->rows <= SPEC_MAX_ROWS, "yalm_generate_speculative: rows must be 2..4");
+// The speculative loop, greedy (smp == nullptr: every row's argmax, spec_verify_kernel) or sampled
+// (every row drawn with the uniform of its output index, spec_sample_rows_kernel, then
+// spec_accept_kernel; the plain steps past the window are sample_kernel steps).
+static int generate_speculative(yalm_decoder_s *d, const char *name, int token, int pos, int n_tokens,
+                                const yalm_spec *cfg, const yalm_sampling *smp, const float *uniforms,
+                                const int *context, int n_context, int *out_tokens, yalm_spec_stats *stats) {
+	const std::string who(name);
+	ARGCHK(d && cfg && (out_tokens || n_tokens == 0), who + ": null argument");
+	TRY(rows_supported(d, name));
+	ARGCHK(token >= 0 && token < d->vocab_full && pos >= 0 && n_tokens >= 0, who + ": bad token/pos/n_tokens");
+	ARGCHK(cfg->rows >= 2 && cfg->rows <= SPEC_MAX_ROWS, who + ": rows must be 2..4");
 	ARGCHK(cfg->ngram_min >= 1 && cfg->ngram_min <= cfg->ngram_max && cfg->ngram_max <= SPEC_MAX_NGRAM,
-	       "yalm_generate_speculative: need 1 <= ngram_min <= ngram_max <= 4");
-	ARGCHK(n_tokens <= d->tokens_cap, "yalm_generate_speculative: n_tokens exceeds the token buffer (65536)");
-	ARGCHK(n_context >= 0 && (n_context == 0 || context), "yalm_generate_speculative: bad context");
-	ARGCHK(n_context == 0 || context[n_context - 1] == token,
-	       "yalm_generate_speculative: the context must end with the token to feed");
-	ARGCHK(cfg->draft_stream_len >= 0 && (cfg->draft_stream || cfg->draft_stream_len == 0),
-	       "yalm_generate_speculative: bad draft_stream");
+	       who + ": need 1 <= ngram_min <= ngram_max <= 4");
+	ARGCHK(n_tokens <= d->tokens_cap, who + ": n_tokens exceeds the token buffer (65536)");
+	ARGCHK(n_context >= 0 && (n_context == 0 || context), who + ": bad context");
+	ARGCHK(n_context == 0 || context[n_context - 1] == token, who + ": the context must end with the token to feed");
+	ARGCHK(cfg->draft_stream_len >= 0 && (cfg->draft_stream || cfg->draft_stream_len == 0), who + ": bad draft_stream");
+	if (smp) {
+		TRY(validate_sampling(smp, uniforms, n_tokens));
+		ARGCHK(d->c.vocab_size <= SMP_MAX_N, who + ": vocabulary above 131072");
+	}
 	const int rows = cfg->rows, L = d->c.n_layers, n = n_tokens;
 	yalm_spec_stats s{};
-	s.launches_per_step = 4 + L * ((d->gq.empty() ? 4 : 5) + rows);
+	s.launches_per_step = (smp ? 5 : 4) + L * ((d->gq.empty() ? 4 : 5) + rows);
 	if (n == 0) {
 		if (stats)
 			*stats = s;
@@ -2183,6 +2188,10 @@ extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int
 	}
 	TRY(rows_init(d));
 	hipStream_t st = d->stream;
+	if (smp) {
+		HIPCHK(hipMemcpyAsync(d->smp_params, smp, sizeof(SampleParams), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d->smp_u, uniforms, sizeof(float) * n, hipMemcpyHostToDevice, st));
+	}
 	int n_ctx = 1;
 	if (n_context == 0) {
 		HIPCHK(hipMemcpyAsync(d->spec_ctx, &token, sizeof(int), hipMemcpyHostToDevice, st));
@@ -2201,13 +2210,14 @@ extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int
 	HIPCHK(hipMemsetAsync(d->spec, 0, sizeof(SpecState), st));
 	set_step_kernel<<<1, 1, 0, st>>>(d->step, token, pos, 1);
 	HIPCHK(hipGetLastError());
+	const int V = d->c.vocab_size;
 	int done = 0;
 	while (done < n) {
 		const long long p = (long long)pos + done;
 		// every step of a batch must keep its rows inside the window whatever the steps before it accepted
 		const int room = p + rows <= d->c.max_seq_len ? (int)((d->c.max_seq_len - p) / rows) : 0;
-		if (room == 0) { // the window's end (and past it): the plain greedy steps
-			TRY(replay_greedy(d, n - done, p));
+		if (room == 0) { // the window's end (and past it): the plain steps
+			TRY(replay_greedy(d, n - done, p, smp ? GRAPH_SAMPLED : GRAPH_GREEDY));
 			s.plain_steps = n - done;
 			done = n;
 			break;
@@ -2216,11 +2226,21 @@ extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int
 		for (int i = 0; i < batch; ++i) {
 			spec_draft_kernel<<<1, SPEC_DRAFT_THREADS, 0, st>>>(d->step, d->spec, d->spec_ctx, n_ctx, d->tokens,
 			                                                    d->tokens_cap, rows, cfg->ngram_max, cfg->ngram_min,
-			                                                    stream, stream_len, d->c.vocab_size);
+			                                                    stream, stream_len, V);
 			HIPCHK(hipGetLastError());
 			TRY(enqueue_rows_forward(d, rows, 1));
-			spec_verify_kernel<<<1, 1024, 0, st>>>(d->rlogits, d->c.vocab_size, rows, d->step, d->spec, d->tokens,
-			                                       d->tokens_cap);
+			if (smp) { // rows past output index n - 1 read the clamped last uniform; their tokens are dropped below
+				if (V % 4 == 0)
+					spec_sample_rows_kernel<true><<<rows, SMP_THREADS, 0, st>>>(d->rlogits, V, V, d->smp_params, d->smp_u,
+					                                                           n, d->step, d->spec, nullptr);
+				else
+					spec_sample_rows_kernel<false><<<rows, SMP_THREADS, 0, st>>>(d->rlogits, V, V, d->smp_params,
+					                                                            d->smp_u, n, d->step, d->spec, nullptr);
+				HIPCHK(hipGetLastError());
+				spec_accept_kernel<<<1, 64, 0, st>>>(rows, d->step, d->spec, d->tokens, d->tokens_cap);
+			} else {
+				spec_verify_kernel<<<1, 1024, 0, st>>>(d->rlogits, V, rows, d->step, d->spec, d->tokens, d->tokens_cap);
+			}
 			HIPCHK(hipGetLastError());
 		}
 		int produced = 0; // the batch's one round trip
@@ -2228,7 +2248,7 @@ extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int
 		HIPCHK(hipStreamSynchronize(st));
 		TRY(awo_check(d));
 		if (produced <= done) {
-			set_err("yalm_generate_speculative: internal: a batch produced no token");
+			set_err(who + ": internal: a batch produced no token");
 			return YALM_ERR_HIP;
 		}
 		done = produced;
@@ -2249,6 +2269,21 @@ extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int
 	if (stats)
 		*stats = s;
 	return YALM_OK;
+}
+
+extern "C" int yalm_generate_speculative(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
+                                         const int *context, int n_context, int *out_tokens,
+                                         yalm_spec_stats *stats) {
+	return generate_speculative(d, "yalm_generate_speculative", token, pos, n_tokens, cfg, nullptr, nullptr, context,
+	                            n_context, out_tokens, stats);
+}
+
+extern "C" int yalm_generate_speculative_sampled(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
+                                                 const yalm_sampling *s, const float *uniforms, const int *context,
+                                                 int n_context, int *out_tokens, yalm_spec_stats *stats) {
+	ARGCHK(s && (uniforms || n_tokens == 0), "yalm_generate_speculative_sampled: null argument");
+	return generate_speculative(d, "yalm_generate_speculative_sampled", token, pos, n_tokens, cfg, s, uniforms, context,
+	                            n_context, out_tokens, stats);
 }
 
 extern "C" int yalm_device_step(yalm_decoder d, int *token, int *pos) {
@@ -2377,6 +2412,25 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 		                                                d->smp_step, nullptr, 0, nullptr, nullptr);
 		HIPCHK(hipGetLastError());
 		return YALM_OK;
+	// the launches that end a 4-row speculative step, on the rows' current logits and a scratch step state
+	case 12:
+		if (c.vocab_size % 4 == 0)
+			spec_sample_rows_kernel<true><<<SPEC_MAX_ROWS, SMP_THREADS, 0, d->stream>>>(
+			    d->rlogits, c.vocab_size, c.vocab_size, d->smp_params, d->smp_u, 1, d->smp_step, d->spec, nullptr);
+		else
+			spec_sample_rows_kernel<false><<<SPEC_MAX_ROWS, SMP_THREADS, 0, d->stream>>>(
+			    d->rlogits, c.vocab_size, c.vocab_size, d->smp_params, d->smp_u, 1, d->smp_step, d->spec, nullptr);
+		HIPCHK(hipGetLastError());
+		return YALM_OK;
+	case 13:
+		spec_accept_kernel<<<1, 64, 0, d->stream>>>(SPEC_MAX_ROWS, d->smp_step, d->spec, d->tokens, 0);
+		HIPCHK(hipGetLastError());
+		return YALM_OK;
+	case 14:
+		spec_verify_kernel<<<1, 1024, 0, d->stream>>>(d->rlogits, c.vocab_size, SPEC_MAX_ROWS, d->smp_step, d->spec,
+		                                              d->tokens, 0);
+		HIPCHK(hipGetLastError());
+		return YALM_OK;
 	}
 	set_err("bad kernel_id");
 	return YALM_ERR_ARG;
@@ -2465,11 +2519,16 @@ static int time_loop(yalm_decoder_s *d, int kernel_id, int iters, bool bump, boo
 }
 
 extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms) {
-	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 11 && kernel_id != 7,
-	       "bad argument (kernel ids 0-6, 8, 9, 10, 11)");
+	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 14 && kernel_id != 7,
+	       "bad argument (kernel ids 0-6, 8-14)");
 	ARGCHK(kernel_id != 11 || !d->gq.empty(), "kernel 11 (q / k norm) needs yalm_decoder_set_qk_norm");
 	ARGCHK(kernel_id != 10 || (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
 	       "kernel 10 (device sampling) needs a one-GPU decoder and a vocabulary of at most 131072");
+	if (kernel_id >= 12) { // the speculative step's last launches: a decoder with a multi-row form, its row buffers
+		TRY(rows_supported(d, "yalm_time_kernel (kernels 12-14)"));
+		ARGCHK(d->c.vocab_size <= SMP_MAX_N, "kernels 12-14 need a vocabulary of at most 131072");
+		TRY(rows_init(d));
+	}
 	ARGCHK(kernel_id != 9 || d->moe_E > 0, "kernel 9 (expert router) needs a mixture-of-experts decoder");
 	ARGCHK(kernel_id != 6 || d->comm || d->ipc, "kernel 6 (tensor-parallel exchange) needs a tensor-parallel decoder");
 	ARGCHK(kernel_id != 8 || d->attn_wo, "kernel 8 (fused attention + Wo) needs yalm_decoder_attn_wo");
@@ -2546,6 +2605,15 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 		break;
 	case 11:
 		s = d->gq.empty() ? "" : "qk_norm_rope_kernel<";
+		break;
+	case 12:
+		s = "spec_sample_rows_kernel<";
+		break;
+	case 13:
+		s = "spec_accept_kernel";
+		break;
+	case 14:
+		s = "spec_verify_kernel";
 		break;
 	default:
 		s = "";
@@ -3088,6 +3156,48 @@ extern "C" int yalm_sample(const float *logits, int n, const yalm_sampling *s, c
 		HIPCHK(hipMemcpy(kept, dkept.p, sizeof(int) * n_draws, hipMemcpyDeviceToHost));
 	if (weights_out)
 		HIPCHK(hipMemcpy(weights_out, dw.p, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+// Host-pointer hook: the sampled step's two launches as the loop makes them, n_gen = 0, stride n.
+extern "C" int yalm_spec_sample_rows(const float *logits, int n, int T, const yalm_sampling *s, const float *uniforms,
+                                     const int *drafts, int *drawn_out, int *kept_out, int *accepted_out) {
+	ARGCHK(logits && drawn_out && accepted_out && n > 0, "yalm_spec_sample_rows: bad argument");
+	ARGCHK(T >= 1 && T <= SPEC_MAX_ROWS, "yalm_spec_sample_rows: 1 <= T <= 4 rows");
+	ARGCHK(T == 1 || drafts, "yalm_spec_sample_rows: null drafts");
+	ARGCHK(n <= SMP_MAX_N, "yalm_spec_sample_rows: n above 131072");
+	TRY(validate_sampling(s, uniforms, T));
+	SpecState sp{};
+	for (int k = 1; k < T; ++k)
+		sp.draft[k] = drafts[k - 1];
+	DevBuf dl, dst, dsp, dprm, du, dtok, dkept;
+	TRY(up(dl, logits, sizeof(float) * (size_t)T * n));
+	TRY(up(dst, nullptr, sizeof(StepState)));
+	TRY(up(dsp, &sp, sizeof(sp)));
+	TRY(up(dprm, s, sizeof(SampleParams)));
+	TRY(up(du, uniforms, sizeof(float) * T));
+	TRY(up(dtok, nullptr, sizeof(int) * SPEC_MAX_ROWS));
+	TRY(up(dkept, nullptr, sizeof(int) * SPEC_MAX_ROWS));
+	if (n % 4 == 0)
+		spec_sample_rows_kernel<true><<<T, SMP_THREADS>>>((const float *)dl.p, n, n, (const SampleParams *)dprm.p,
+		                                                 (const float *)du.p, T, (const StepState *)dst.p,
+		                                                 (SpecState *)dsp.p, (int *)dkept.p);
+	else
+		spec_sample_rows_kernel<false><<<T, SMP_THREADS>>>((const float *)dl.p, n, n, (const SampleParams *)dprm.p,
+		                                                  (const float *)du.p, T, (const StepState *)dst.p,
+		                                                  (SpecState *)dsp.p, (int *)dkept.p);
+	HIPCHK(hipGetLastError());
+	spec_accept_kernel<<<1, 64>>>(T, (StepState *)dst.p, (SpecState *)dsp.p, (int *)dtok.p, SPEC_MAX_ROWS);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipDeviceSynchronize());
+	StepState h;
+	HIPCHK(hipMemcpy(&h, dst.p, sizeof(h), hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(&sp, dsp.p, sizeof(sp), hipMemcpyDeviceToHost));
+	for (int t = 0; t < T; ++t)
+		drawn_out[t] = sp.drawn[t];
+	if (kept_out)
+		HIPCHK(hipMemcpy(kept_out, dkept.p, sizeof(int) * T, hipMemcpyDeviceToHost));
+	*accepted_out = h.n_gen;
 	return YALM_OK;
 }
 

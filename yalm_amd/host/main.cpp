@@ -2,9 +2,10 @@
 // /root/reference/src/main.cpp:17-428): completion, perplexity and passkey,
 // -d device switch (cpu | cuda | hip prefixes), -m -n -t -i -f -T -l.
 // -t 0 runs the greedy loop with the argmax on the device; -k / -p (top-k, top-p) select
-// device sampling for -t > 0: only the token comes back per step. -s <rows> (with -t 0) runs
-// the greedy completion by speculative steps of 2..4 rows with n-gram drafts from the prompt
-// and the output so far: the same tokens, several per pass over the weights where drafts hit.
+// device sampling for -t > 0: only the token comes back per step. -s <rows> runs the greedy
+// (-t 0) or the device-sampled (-t > 0 with -k / -p) completion by speculative steps of 2..4
+// rows with n-gram drafts from the prompt and the output so far: the same tokens, several per
+// pass over the weights where drafts hit.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -44,8 +45,9 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -k <int>   top-k: sample among the k most likely tokens (0 - off); samples on the device\n");
 	fprintf(stderr, "  -p <float> top-p: sample from the smallest set of most likely tokens whose probability\n"
 	                "             reaches p, in (0, 1] (1 - off); samples on the device\n");
-	fprintf(stderr, "  -s <int>   speculative greedy decode with this many rows per step, 2..4 (0 - off, the default);\n"
-	                "             needs -t 0\n");
+	fprintf(stderr, "  -s <int>   speculative decode with this many rows per step, 2..4 (0 - off, the default);\n"
+	                "             needs -t 0 (greedy), or -t > 0 with -k or -p (sampled on the device: the\n"
+	                "             same tokens as without -s)\n");
 	fprintf(stderr, "  Choose one:\n    -i <string> input prompt\n    -f <filepath> input file with prompt\n");
 	fprintf(stderr, "Passkey mode options:\n  -n <int>    number of junk lines to insert (default - 250)\n");
 	fprintf(stderr, "  -l <int>    passkey position (-1 - random)\n");
@@ -153,8 +155,16 @@ static void run_completion(const std::string &path, const std::string &device, c
 		const int chunk = num_steps == -1 ? SPEC_CHUNK : std::min(SPEC_CHUNK, num_steps - done);
 		int out[SPEC_CHUNK];
 		const int pos = (int)encoding.size() - 1;
-		model.generate_speculative(state, encoding.back(), pos, chunk, spec_rows, encoding.data(), (int)encoding.size(),
-		                           out, &spec_steps, &spec_accepted, &spec_plain);
+		if (sampled) { // one draw per token of the chunk, in order: token j consumes the j-th draw, as without -s
+			float u[SPEC_CHUNK];
+			for (int j = 0; j < chunk; ++j)
+				u[j] = uniform();
+			model.generate_speculative_sampled(state, encoding.back(), pos, chunk, spec_rows, temperature, top_k, top_p, u,
+			                                   encoding.data(), (int)encoding.size(), out, &spec_steps, &spec_accepted,
+			                                   &spec_plain);
+		} else
+			model.generate_speculative(state, encoding.back(), pos, chunk, spec_rows, encoding.data(),
+			                           (int)encoding.size(), out, &spec_steps, &spec_accepted, &spec_plain);
 		for (int j = 0; j < chunk && !stop; ++j, ++done) {
 			std::cout << tokenizer.decode_one(encoding.back(), out[j]) << std::flush;
 			ids += std::to_string(out[j]) + " ";
@@ -382,8 +392,10 @@ int main(int argc, char *argv[]) {
 		default: error_usage();
 		}
 	}
-	// -s: completion mode with -t 0 only
-	if (spec_rows != 0 && (spec_rows < 2 || spec_rows > 4 || temperature != 0.0f || mode != "completion"))
+	// -s: completion mode, with -t 0 (greedy) or with -t > 0 and -k / -p (the device draw); the
+	// host sampler (-t > 0 alone) reads the logits of one row and has no speculative form
+	if (spec_rows != 0 && (spec_rows < 2 || spec_rows > 4 || (temperature != 0.0f && !device_sampling) ||
+	                       temperature < 0.0f || mode != "completion"))
 		error_usage();
 	const int has_prompt = prompt.size() > 0, has_path = prompt_path.size() > 0;
 	if (mode == "completion" || mode == "perplexity") {

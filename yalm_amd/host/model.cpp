@@ -414,6 +414,23 @@ void Model::generate_speculative(InferenceState &s, int token, int pos, int n, i
 		*plain += st.plain_steps;
 }
 
+void Model::generate_speculative_sampled(InferenceState &s, int token, int pos, int n, int rows, float temperature,
+                                         int top_k, float top_p, const float *uniforms, const int *context,
+                                         int n_context, int *out, int *steps, int *accepted, int *plain) {
+	ensure_decoder(s);
+	const yalm_spec cfg{rows, 3, 1, nullptr, 0};
+	const yalm_sampling sp{temperature, top_k, top_p};
+	yalm_spec_stats st{};
+	check(yalm_generate_speculative_sampled(s._decoder, token, pos, n, &cfg, &sp, uniforms, context, n_context, out, &st),
+	      "speculative sampled steps");
+	if (steps)
+		*steps += st.spec_steps;
+	if (accepted)
+		*accepted += st.accepted_drafts;
+	if (plain)
+		*plain += st.plain_steps;
+}
+
 int Model::forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u) {
 	ensure_decoder(s);
 	const yalm_sampling sp{temperature, top_k, top_p};

@@ -149,6 +149,11 @@ struct Model {
 	// plain (may be null) are incremented by the call's counts.
 	void generate_speculative(InferenceState &s, int token, int pos, int n, int rows, const int *context, int n_context,
 	                          int *out, int *steps, int *accepted, int *plain);
+	// The same with every row drawn on the device (yalm_generate_speculative_sampled): the tokens
+	// of forward_sampled step by step with uniforms[j] for token j (n of them, each in [0, 1]).
+	void generate_speculative_sampled(InferenceState &s, int token, int pos, int n, int rows, float temperature,
+	                                  int top_k, float top_p, const float *uniforms, const int *context, int n_context,
+	                                  int *out, int *steps, int *accepted, int *plain);
 	// Batched MFMA prefill of tokens[0..n) at positions pos0.. (yalm_prefill):
 	// fills the KV cache; logprobs (may be null) gets log p(tokens[i+1]) per
 	// position; split: the split-operand precision form (yalm_set_prefill_precision).

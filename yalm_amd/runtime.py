@@ -203,6 +203,11 @@ _sig("yalm_forward_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p])
 _sig("yalm_generate_speculative", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Spec), c_void_p, c_int, c_void_p,
                                            ctypes.POINTER(SpecStats)])
 _sig("yalm_spec_draft", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p])
+_sig("yalm_generate_speculative_sampled", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Spec),
+                                                   ctypes.POINTER(Sampling), c_void_p, c_void_p, c_int, c_void_p,
+                                                   ctypes.POINTER(SpecStats)])
+_sig("yalm_spec_sample_rows", c_int, [c_void_p, c_int, c_int, ctypes.POINTER(Sampling), c_void_p, c_void_p, c_void_p,
+                                       c_void_p, ctypes.POINTER(c_int)])
 _sig("yalm_decoder_set_rope_scaling", c_int, [c_void_p, ctypes.POINTER(RopeScaling)])
 _sig("yalm_decoder_get_inv_freq", c_int, [c_void_p, c_void_p])
 _sig("yalm_decoder_set_qkv_bias", c_int, [c_void_p, c_void_p, c_void_p, c_void_p])
@@ -228,6 +233,7 @@ EXPORTED = [
     "yalm_generate_sampled", "yalm_sample",
     "yalm_row_bytes", "yalm_synth_q4", "yalm_synth_e4m3",
     "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
+    "yalm_generate_speculative_sampled", "yalm_spec_sample_rows",
     "yalm_decoder_set_rope_scaling", "yalm_decoder_get_inv_freq", "yalm_decoder_set_qkv_bias",
     "yalm_decoder_set_qk_norm",
     "yalm_rows_plan", "yalm_matmul_rows",
@@ -313,6 +319,27 @@ def spec_draft(history, rows: int, ngram_max: int = 3, ngram_min: int = 1) -> li
     out = np.full(4, -1, np.int32)
     check(lib.yalm_spec_draft(_ptr(h) if h.size else None, h.size, rows, ngram_max, ngram_min, _ptr(out)))
     return out[:rows - 1].tolist()
+
+
+def spec_sample_rows(logits, temperature: float, top_k: int = 0, top_p: float = 1.0, uniforms=(0.5,), drafts=()):
+    """The draw and the accept launch of a sampled speculative step (yalm_spec_sample_rows) on
+    host logits (T, n), row t drawn with uniforms[t], drafts[k - 1] the draft of row k (-1 =
+    none). Returns (drawn, kept, a): every row's token and kept-set size (int32 arrays) and the
+    number of tokens the step yields."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    assert lg.ndim == 2
+    T, n = lg.shape
+    u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+    dr = np.full(4, -1, np.int32)
+    d = np.asarray(drafts, np.int32).reshape(-1)
+    if u.size != T or d.size != max(T - 1, 0):
+        raise ValueError(f"spec_sample_rows: {T} rows need {T} uniforms and {T - 1} drafts")
+    dr[:d.size] = d
+    s = Sampling(temperature, top_k, top_p)
+    drawn, kept, a = np.zeros(4, np.int32), np.zeros(4, np.int32), c_int()
+    check(lib.yalm_spec_sample_rows(_ptr(lg), n, T, ctypes.byref(s), _ptr(u), _ptr(dr), _ptr(drawn), _ptr(kept),
+                                    ctypes.byref(a)))
+    return drawn[:T], kept[:T], a.value
 
 
 def ffn(x, w1, w2, w3, act: int, dtype: int) -> np.ndarray:
@@ -919,6 +946,33 @@ class Decoder:
         out = np.zeros(max(n, 1), np.int32)
         check(lib.yalm_generate_sampled(self.h, token, pos, n, ctypes.byref(s), _ptr(u), out.ctypes.data))
         return out[:n].tolist()
+
+    def generate_speculative_sampled(self, token: int, pos: int, n: int, temperature: float, top_k: int = 0,
+                                     top_p: float = 1.0, uniforms=None, seed: int = 0, rows: int = 4,
+                                     ngram_max: int = 3, ngram_min: int = 1, context=None, draft_stream=None):
+        """n sampled tokens by speculative steps of `rows` rows (yalm_generate_speculative_sampled):
+        (tokens, stats dict); the tokens of generate_sampled for the same uniforms. uniforms / seed
+        as generate_sampled, the rest as generate_speculative."""
+        if uniforms is None:
+            uniforms = np.random.default_rng(seed).random(n, dtype=np.float32)
+        u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+        if u.size < n:
+            raise ValueError(f"generate_speculative_sampled: {n} tokens need {n} uniforms, got {u.size}")
+        if u.size == 0:
+            u = np.zeros(1, np.float32)
+        ctx = np.ascontiguousarray(context if context is not None else [], dtype=np.int32).reshape(-1)
+        ds = None if draft_stream is None else np.ascontiguousarray(draft_stream, dtype=np.int32).reshape(-1)
+        keep = np.zeros(1, np.int32)  # a non-NULL pointer for an empty stream
+        spec = Spec(rows, ngram_max, ngram_min,
+                    None if ds is None else (_ptr(ds) if ds.size else _ptr(keep)), 0 if ds is None else ds.size)
+        s = Sampling(temperature, top_k, top_p)
+        st = SpecStats()
+        out = np.zeros(max(n, 1), np.int32)
+        check(lib.yalm_generate_speculative_sampled(self.h, token, pos, n, ctypes.byref(spec), ctypes.byref(s), _ptr(u),
+                                                    _ptr(ctx) if ctx.size else None, ctx.size, out.ctypes.data,
+                                                    ctypes.byref(st)))
+        return out[:n].tolist(), {"spec_steps": st.spec_steps, "accepted_drafts": st.accepted_drafts,
+                                  "plain_steps": st.plain_steps, "launches_per_step": st.launches_per_step}
 
     def enqueue_greedy(self, n: int) -> None:
         check(lib.yalm_enqueue_greedy(self.h, n))
