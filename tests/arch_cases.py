@@ -14,6 +14,8 @@ import functools
 import numpy as np
 
 import arch_ref
+import gemv_cases
+import gemv_ref
 from yalm_amd import models as M
 
 # the decode bars of tests/test_gpu_decode.py (it asserts these literals; DESIGN.md "Parity"):
@@ -152,3 +154,33 @@ def spec_case(name):
 
 def relerr(a, b):
     return float(np.max(np.abs(a - b)) / (np.max(np.abs(b)) + 1e-30))
+
+
+# ------------------------------------------------------------------ the timing hook's GLU (test_gpu_arch.py)
+# One dense layer whose W1|W3 and W2 launches run the row-block kernel (dim 512, hidden 1536: whole
+# f16 chunks), attention and Wo as separate launches.
+GLU_CFG = M.ModelConfig(dim=512, hidden_dim=1536, head_dim=128, n_layers=1, n_heads=4, n_kv_heads=4, vocab_size=256,
+                        max_seq_len=16, act=M.GELU, weight_dtype=M.F16)
+GLU_SEED = 23
+# gemv_ref.rel_tol of the f16 GLU and residual cases (both families keep gemv_ref.REL_TOL)
+GLU_BAR = max(gemv_ref.rel_tol(c) for c in gemv_cases.CASES if c.dtype == gemv_cases.F16 and c.family in ("glu", "residual"))
+
+
+@functools.lru_cache(maxsize=None)
+def glu_case(act):
+    """x0 and x0 + 2 W2 (act(W1 xn) * (W3 xn)), xn the RMS-normed x0, in float64 with the oracle's
+    f32 GELU constants: what yalm_time_kernel ids 3 then 4 (a warm-up and one iteration each, both
+    on the only layer) leave in x."""
+    cfg = GLU_CFG.with_(act=act)
+    t = M.synth_host_tensors(cfg, seed=GLU_SEED)
+    nm = M.layer_names(0)
+    w1, w2, w3 = (t[nm[k]].astype(np.float64) for k in ("w1", "w2", "w3"))
+    x0 = np.random.default_rng(GLU_SEED).standard_normal(cfg.dim).astype(np.float32)
+    x = x0.astype(np.float64)
+    xn = x / np.sqrt(np.mean(x * x) + cfg.norm_eps) * t[nm["rms_ffn"]].astype(np.float64)
+    a = w1 @ xn
+    if act == M.SILU:
+        h = a / (1.0 + np.exp(-a))
+    else:
+        h = 0.5 * a * (1.0 + np.tanh(gemv_ref.GELU_C0 * (a + gemv_ref.GELU_C1 * a * a * a)))
+    return cfg, t, x0, x + 2.0 * (w2 @ (h * (w3 @ xn)))

@@ -54,7 +54,7 @@ STORE1, STORE2, RESIDUAL, ADDTO, GLU, QKV, QKVB, QKVN = range(8)  # yalm_gemv_on
 POLICY_NAMES = ("store1", "store2", "residual", "addto", "glu", "qkv", "qkvb", "qkvn")
 FAMILIES = {"store": (STORE1, STORE2), "residual": (RESIDUAL, ADDTO), "glu": (GLU,), "qkv": (QKV, QKVB, QKVN)}
 POLICY_R = (1, 2, 1, 1, 2, 2, 2, 2)
-ROWS_POLICIES = (RESIDUAL, GLU, QKV, QKVB, QKVN)  # yalm_hip.hip RowsMode
+ROWS_POLICIES = (RESIDUAL, GLU, QKV, QKVB, QKVN)  # gemv.h ROWS_MODE
 QKV_POLICIES = (QKV, QKVB, QKVN)
 GK_QKV, GK_WO, GK_GLU, GK_W2, GK_CLS = range(5)
 GELU, SILU = 0, 1

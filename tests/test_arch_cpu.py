@@ -12,6 +12,7 @@ import pytest
 import arch_cases as A
 import arch_hf
 import arch_ref
+import gemv_ref
 import ref_numpy
 from yalm_amd import convert
 from yalm_amd import models as M
@@ -283,3 +284,10 @@ def test_spec_cases_have_no_near_tie(name):
     """The speculative tests compare token sequences: the reference's greedy path clears twice
     the logits bar at every step (seeds searched here, on the CPU)."""
     assert A.spec_case(name)[3] >= 2 * LOGITS_BAR
+
+
+def test_glu_case_separates_the_activations():
+    """test_gpu_arch.py test_time_kernel_glu_runs_the_models_activation: the SILU model's x is far
+    outside the bar around the GELU model's, so a hook that ran the wrong activation fails there."""
+    assert A.GLU_BAR == gemv_ref.REL_TOL
+    assert A.relerr(A.glu_case(M.SILU)[3], A.glu_case(M.GELU)[3]) > 100 * A.GLU_BAR

@@ -133,6 +133,34 @@ def test_bias_mechanics(name):
             h.close()
 
 
+# ------------------------------------------------------------------ 2b. the timing hook's GLU
+# arch_cases.glu_case: one dense GELU / SILU layer; tests/test_arch_cpu.py shows that the two are far apart
+GLU_BAR, glu_case = A.GLU_BAR, A.glu_case
+
+
+@pytest.mark.parametrize("act", [M.GELU, M.SILU], ids=["gelu", "silu"])
+def test_time_kernel_glu_runs_the_models_activation(act):
+    """yalm_time_kernel launches what the forward launches: the GLU of a GELU model is GELU."""
+    R = rt()
+    cfg, t, x0, want = glu_case(act)
+    other = glu_case(M.SILU if act == M.GELU else M.GELU)[3]
+    dm = R.DeviceModel.from_arrays(cfg, t)
+    dec = R.Decoder(dm, launch=R.LAUNCH_SEPARATE_ATTN_WO)
+    try:
+        assert not dec.attn_wo and dec.kernel_name(3) == "gemv_rb_kernel<WF16, PGlu<"
+        dec.set_x(x0)
+        dec.time_kernel(3, 1)
+        dec.time_kernel(4, 1)
+        got = dec.get_x().astype(np.float64)
+        e, off = relerr(got, want), relerr(got, other)
+        print(f"act {act}: rel err {e:.3e}, against the other activation {off:.3e}")
+        assert e < GLU_BAR, e
+        assert off > GLU_BAR, off
+    finally:
+        dec.close()
+        dm.close()
+
+
 # ------------------------------------------------------------------ 3. scaled RoPE
 def ulps(a, b):
     a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)

@@ -48,6 +48,12 @@ struct GemvCfg {
 	int cus = 0, rows = -1;
 };
 enum { GK_QKV = 0, GK_WO = 1, GK_GLU = 2, GK_W2 = 3, GK_CLS = 4, GK_N = 5 };
+// The launches yalm_time_kernel times and yalm_kernel_name names (7 is unused).
+enum {
+	KID_QKV = 0, KID_ATTN = 1, KID_WO = 2, KID_GLU = 3, KID_W2 = 4, KID_CLS = 5, KID_EXCHANGE = 6, KID_ATTN_WO = 8,
+	KID_ROUTER = 9, KID_SAMPLE = 10, KID_QK_NORM = 11, KID_SPEC_SAMPLE = 12, KID_SPEC_ACCEPT = 13, KID_SPEC_VERIFY = 14,
+	KID_LAST = KID_SPEC_VERIFY
+};
 
 int device_cu_count();
 

@@ -137,6 +137,7 @@ __device__ __forceinline__ uint16_t f2h(float x) { // round to nearest even
 #define WT_CHUNK_BYTES ((size_t)YALM_WAVE * 16)
 struct NoScale {};
 struct WF32 {
+	static constexpr const char *NAME = "WF32"; // as yalm_kernel_name spells the type
 	static constexpr int EPL = 4;
 	static constexpr int BYTES = 4;
 	static constexpr bool Q4 = false;
@@ -154,6 +155,7 @@ struct WF32 {
 	}
 };
 struct WF16 {
+	static constexpr const char *NAME = "WF16"; // as yalm_kernel_name spells the type
 	static constexpr int EPL = 8;
 	static constexpr int BYTES = 2;
 	static constexpr bool Q4 = false;
@@ -176,6 +178,7 @@ struct WF16 {
 // widen sequence; tests/test_gpu_kernels.py checks all 256 byte values.
 typedef float float2_t __attribute__((ext_vector_type(2)));
 struct WF8 {
+	static constexpr const char *NAME = "WF8"; // as yalm_kernel_name spells the type
 	static constexpr int EPL = 16;
 	static constexpr int BYTES = 1;
 	static constexpr bool Q4 = false;
@@ -225,6 +228,7 @@ __device__ __forceinline__ void q4_pairs(uint32_t w, half2_t (&h)[4]) {
 	h[3] = __builtin_bit_cast(half2_t, q4_and_or(w8, 0x00F000F0u, 0x64006400u)) * c16th - c72;
 }
 struct WQ4 {
+	static constexpr const char *NAME = "WQ4"; // as yalm_kernel_name spells the type
 	static constexpr int EPL = 32; // a lane's 16-byte load is one group
 	static constexpr bool Q4 = true;
 	static constexpr bool ROW_SCALE = false;
@@ -287,6 +291,7 @@ __device__ __forceinline__ float q4_dot32(float acc, const u32x4_t &w, uint32_t 
 // row's sum is multiplied by the scale once (gemv.h, gemv_rows.h, attn_wo.h: ROW_SCALE).
 // No BYTES: code that multiplies by an element size does not compile for it.
 struct WE4M3 {
+	static constexpr const char *NAME = "WE4M3"; // as yalm_kernel_name spells the type
 	static constexpr int EPL = 16;
 	static constexpr bool Q4 = false;
 	static constexpr bool ROW_SCALE = true;

@@ -72,6 +72,8 @@ struct PResidual {
 	// the residual rows, read before the weight stream (gemv_rb_kernel): the epilogue's
 	// read-modify-write then costs no load round trip at the tail
 	static constexpr bool PRE = true;
+	static constexpr bool ROWS_MODE = true;
+	static constexpr bool LOCAL_X = true; // the decoder never norms its x; only the yalm_gemv_one hook does
 	__device__ __forceinline__ float pre(int g, int r) const { return out[g * R + r]; }
 	__device__ __forceinline__ void finish_pre(int g, const float *acc, const float *xr) const {
 #pragma unroll
@@ -124,6 +126,20 @@ template <class P, class = void>
 struct gemv_pre : std::false_type {};
 template <class P>
 struct gemv_pre<P, std::void_t<decltype(P::PRE)>> : std::bool_constant<P::PRE> {};
+
+// policies that stream in whole-row mode (ROWS_MODE = true; gemv_rb_kernel ROWS) when the rows divide
+// evenly over the waves: W1|W3 (PGlu), W2 / Wo (PResidual), QKV (PQKV and its kin), and the expert
+// policies (moe.h), which stream as their dense counterparts do
+template <class P, class = void>
+struct gemv_rows_mode : std::false_type {};
+template <class P>
+struct gemv_rows_mode<P, std::void_t<decltype(P::ROWS_MODE)>> : std::bool_constant<P::ROWS_MODE> {};
+
+// policies that never consume a tensor-parallel exchange (LOCAL_X = true: no TIN instantiation)
+template <class P, class = void>
+struct gemv_local_x : std::false_type {};
+template <class P>
+struct gemv_local_x<P, std::void_t<decltype(P::LOCAL_X)>> : std::bool_constant<P::LOCAL_X> {};
 
 // out[row] = base[row] + acc: the tensor-parallel Wo / W2 partial of rank 0,
 // which also carries the residual into the all-reduce (other ranks: PStore).
@@ -202,6 +218,7 @@ struct PQKV {
 	// (late), so no wave waits on a dependent round trip; rows < kv_sink never alias the kv_pos
 	// row the epilogue writes (kv_pos >= kv_sink)
 	static constexpr bool EARLY = true;
+	static constexpr bool ROWS_MODE = true;
 	static constexpr int KV_SINKS = 2; // model.h:12
 	struct Early {
 		uint32_t kv; // the pair (fp16 x 2) of pair index pi below
@@ -326,6 +343,7 @@ struct PQKVN : PQKV<WT> {
 template <class WT, int ACT>
 struct PGlu {
 	static constexpr int R = 2;
+	static constexpr bool ROWS_MODE = true;
 	const char *w1, *w3;
 	int n;
 	float *out;

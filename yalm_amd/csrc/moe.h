@@ -121,6 +121,8 @@ __global__ __launch_bounds__(MOE_ROUTER_THREADS) void moe_router_kernel(const ch
 template <class WT, int ACT>
 struct PMoeGlu {
 	static constexpr int R = 2;
+	static constexpr bool ROWS_MODE = true;
+	static constexpr bool LOCAL_X = true; // the expert GLU never consumes a tensor-parallel exchange
 	const char *w1, *w3; // stacked (E, hidden, n)
 	int n;
 	float *out; // [K * hidden]
@@ -160,6 +162,7 @@ template <class WT>
 struct PMoeW2 {
 	static constexpr int R = 1;
 	static constexpr bool CHUNKED = true;
+	static constexpr bool ROWS_MODE = true;
 	const char *W; // stacked (E, dim, hidden)
 	int n;         // K * hidden
 	float *out;
@@ -190,6 +193,7 @@ struct PMoeW2 {
 template <class WT>
 struct PMoeW2One {
 	static constexpr int R = 1;
+	static constexpr bool ROWS_MODE = true;
 	const char *W; // stacked (E, dim, n)
 	int n;         // hidden
 	float *out;

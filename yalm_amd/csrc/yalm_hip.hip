@@ -144,10 +144,15 @@ extern "C" int yalm_stream_sync(yalm_stream s) {
 	return YALM_OK;
 }
 
+// a weight format of this library (each entry point first refuses the formats it has no form for)
+static bool dtype_ok(int dtype) {
+	return dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3;
+}
+
 extern "C" int yalm_synth(void *device, size_t n, int dtype, uint64_t seed, float scale, float offset, yalm_stream s) {
 	ARGCHK(dtype != YALM_Q4, "yalm_synth: q4 tensors need their row length (yalm_synth_q4)");
 	ARGCHK(dtype != YALM_E4M3, "yalm_synth: e4m3 tensors need their row length (yalm_synth_e4m3)");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "yalm_synth: bad dtype");
+	ARGCHK(dtype_ok(dtype), "yalm_synth: bad dtype");
 	hipStream_t st = reinterpret_cast<hipStream_t>(s);
 	synth_kernel<<<4096, 256, 0, st>>>(device, n, dtype, seed, scale, offset);
 	HIPCHK(hipGetLastError());
@@ -220,61 +225,8 @@ int device_cu_count() {
 }
 
 // Row-block geometry (gemv_rb_kernel): `gpw` = workgroups per CU (default 1),
-// threads 512 (8 waves), U = 8 loads in flight per wave.
-// whole-row mode (gemv.h ROWS): W1|W3 (PGlu), W2 / Wo (PResidual), QKV (PQKV) when the rows divide
-// evenly over the waves
-template <class P>
-struct RowsMode {
-	static constexpr bool value = false;
-};
-template <class WT, int ACT>
-struct RowsMode<PGlu<WT, ACT>> {
-	static constexpr bool value = true;
-};
-template <class WT, int R>
-struct RowsMode<PResidual<WT, R>> {
-	static constexpr bool value = true;
-};
-template <class WT>
-struct RowsMode<PQKV<WT>> {
-	static constexpr bool value = true;
-};
-template <class WT>
-struct RowsMode<PQKVB<WT>> {
-	static constexpr bool value = true;
-};
-template <class WT>
-struct RowsMode<PQKVN<WT>> {
-	static constexpr bool value = true;
-};
-// the expert policies (moe.h) stream as their dense counterparts do
-template <class WT, int ACT>
-struct RowsMode<PMoeGlu<WT, ACT>> {
-	static constexpr bool value = true;
-};
-template <class WT>
-struct RowsMode<PMoeW2<WT>> {
-	static constexpr bool value = true;
-};
-template <class WT>
-struct RowsMode<PMoeW2One<WT>> {
-	static constexpr bool value = true;
-};
-
-// policies that never consume a tensor-parallel exchange (no TIN instantiation): the expert GLU
-template <class P>
-struct LocalX {
-	static constexpr bool value = false;
-};
-template <class WT, int ACT>
-struct LocalX<PMoeGlu<WT, ACT>> {
-	static constexpr bool value = true;
-};
-// ... and the residual policy: the decoder never norms its x; only the yalm_gemv_one hook does
-template <class WT, int R>
-struct LocalX<PResidual<WT, R>> {
-	static constexpr bool value = true;
-};
+// threads 512 (8 waves), U = 8 loads in flight per wave. Whole-row mode (gemv.h ROWS) for the
+// policies that declare ROWS_MODE when the rows divide evenly over the waves.
 
 // One launch of gemv_rb_kernel; a consumer of an IPC exchange (tin.n > 0, always a
 // normalising GEMV: QKV, W1|W3, logits) runs the TIN instantiation.
@@ -282,7 +234,7 @@ template <class WT, class P, bool NORM, int THREADS, int U, bool ROWS>
 static int launch_rb_k(const P &p, const float *x, const float *normw, float eps, int nb, size_t lds, hipStream_t st,
                        const TpX &tin) {
 	auto kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS>;
-	if constexpr (NORM && !LocalX<P>::value && !WT::Q4 && !WT::ROW_SCALE) { // (q4, e4m3: no tensor-parallel form)
+	if constexpr (NORM && !gemv_local_x<P>::value && !WT::Q4 && !WT::ROW_SCALE) { // (q4, e4m3: no tensor-parallel form)
 		if (tin.n > 0)
 			kern = gemv_rb_kernel<WT, P, U, NORM, THREADS, ROWS, true>;
 	} else if (tin.n > 0) {
@@ -351,7 +303,7 @@ static GemvPlan gemv_plan(int CH, bool q4, int R, bool rows_ok, bool norm, int n
 template <class WT, class P, bool NORM, int THREADS, int U>
 static int launch_rb_t(const P &p, const float *x, const float *normw, float eps, const GemvPlan &g, hipStream_t st,
                        const TpX &tin) {
-	if constexpr (RowsMode<P>::value) {
+	if constexpr (gemv_rows_mode<P>::value) {
 		if (g.rows)
 			return launch_rb_k<WT, P, NORM, THREADS, U, true>(p, x, normw, eps, g.nb, g.lds, st, tin);
 	}
@@ -414,7 +366,7 @@ static GemvCfg default_rb_cfg(int kind) {
 // the plan of launch_gemv<WT, P, NORM>
 template <class WT, class P>
 static GemvPlan gemv_plan_of(bool norm, int n, int n_groups, int kind, const GemvCfg &want, bool tin) {
-	return gemv_plan(YALM_WAVE * WT::EPL, WT::Q4, P::R, RowsMode<P>::value, norm, n, n_groups, default_rb_cfg<WT>(kind),
+	return gemv_plan(YALM_WAVE * WT::EPL, WT::Q4, P::R, gemv_rows_mode<P>::value, norm, n, n_groups, default_rb_cfg<WT>(kind),
 	                 want, tin);
 }
 
@@ -478,6 +430,44 @@ template <class WT, class P, bool NORM>
 static int launch_gemv_d(yalm_decoder_s *d, const P &p, const float *x, const float *normw, float eps, int kind,
                          const TpX &tin = TpX{}) {
 	return launch_gemv<WT, P, NORM>(p, x, normw, eps, kind, d->gemv[kind], d->stream, tin);
+}
+
+// ---- the policies, filled: the forward, the timing hook and the host-pointer test entry points
+// all build theirs here. `rows` weight rows of n elements each.
+template <class WT, int R>
+static PStore<WT, R> make_store(const void *W, int n, float *out, int rows) {
+	return {(const char *)W, n, out, rows / R};
+}
+template <class WT>
+static PResidual<WT, 1> make_residual(const void *W, int n, float *out, int rows) {
+	return {(const char *)W, n, out, rows};
+}
+template <class WT>
+static PAddTo<WT, 1> make_addto(const void *W, int n, float *out, const float *base, int rows) {
+	return {(const char *)W, n, out, base, rows};
+}
+template <class WT>
+static PPush<WT, 1> make_push(const void *W, int n, const float *base, const TpX &t, int rows) {
+	return {(const char *)W, n, base, t, 0, rows};
+}
+template <class WT>
+static PQKV<WT> make_pqkv(const void *wq, const void *wk, const void *wv, int n, int n_heads, int n_kv_heads,
+                          int head_dim, float qkv_clip, const float *inv_freq, const StepState *step, float *q_out,
+                          uint16_t *kcache, uint16_t *vcache) {
+	const int q_dim = n_heads * head_dim, kv_dim = n_kv_heads * head_dim;
+	return {(const char *)wq, (const char *)wk, (const char *)wv, n, q_dim, kv_dim, head_dim, (q_dim + 2 * kv_dim) / 2,
+	        qkv_clip, inv_freq, step, q_out, kcache, vcache};
+}
+// W1 | W3 + GLU: the one place that maps `act` to PGlu's template argument
+template <class WT, bool NORM>
+static int launch_glu(const void *w1, const void *w3, int n, float *out, int hidden, int act, const float *x,
+                      const float *normw, float eps, int kind, const GemvCfg &want, hipStream_t st,
+                      const TpX &tin = TpX{}) {
+	if (act == YALM_SILU)
+		return launch_gemv<WT, PGlu<WT, 1>, NORM>({(const char *)w1, (const char *)w3, n, out, hidden}, x, normw, eps, kind,
+		                                          want, st, tin);
+	return launch_gemv<WT, PGlu<WT, 0>, NORM>({(const char *)w1, (const char *)w3, n, out, hidden}, x, normw, eps, kind,
+	                                          want, st, tin);
 }
 
 // ---- mixture of experts (moe.h): router, the selected experts' W1 | W3 + GLU, their W2
@@ -833,8 +823,9 @@ static void launch_attn_wo_g(yalm_decoder_s *d, const yalm_block_weights &w, con
 // the rank's partial (+ x on rank 0) -- into xs, then the RCCL all-reduce into x; or pushed
 // to the IPC exchange `ex` (consumed by the GLU GEMV's x staging, tp_exchange.h).
 template <class WT>
-static int launch_attn_wo(yalm_decoder_s *d, const yalm_block_weights &w, int layer, int ex) {
+static int launch_attn_wo(yalm_decoder_s *d, int layer, int ex) {
 	const yalm_config &c = d->c;
+	const yalm_block_weights &w = d->b[layer];
 	AttnWoArgs p;
 	p.n_heads = c.n_heads;
 	p.n_kv = c.n_kv_heads;
@@ -914,59 +905,30 @@ static int enqueue_exchange(yalm_decoder_s *d) {
 // every rank (identical bits). IPC: the partial is pushed to every rank's exchange slot
 // (PPush, exchange `ex`, tp_exchange.h); the next GEMV sums the slots while its weights
 // stream in. ex < 0 under IPC: a result nothing reads (the last W2 of a hydration forward)
-// stays local -- an exchange nobody consumes would break the slot-reuse order.
+// stays local -- an exchange nobody consumes would break the slot-reuse order. ex == EX_LOCAL
+// (the timing hook): this rank's own x += W v under either transport, no exchange, no all-reduce.
+enum { EX_LOCAL = -2 };
 template <class WT>
 static int enqueue_residual_gemv(yalm_decoder_s *d, const void *W, int n, const float *v, int kind, int ex) {
-	const yalm_config &c = d->c;
-	hipStream_t st = d->stream;
-	if constexpr (wt_dense_one_gpu<WT>()) { // one GPU only: yalm_decoder_create_tp / _tp_ipc refuse q4 and e4m3
-		PResidual<WT, 1> p;
-		p.W = (const char *)W;
-		p.n = n;
-		p.out = d->x;
-		p.n_groups = c.dim;
-		return launch_gemv_d<WT, PResidual<WT, 1>, false>(d, p, v, nullptr, 0.f, kind);
-	} else {
-		if (d->ipc && ex >= 0) {
-			PPush<WT, 1> p;
-			p.W = (const char *)W;
-			p.n = n;
-			p.base = d->tp_rank == 0 ? d->x : nullptr;
-			p.t = tpx_ex(d, ex);
-			p.offset = 0;
-			p.n_groups = c.dim;
-			return launch_gemv<WT, PPush<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st);
+	const int dim = d->c.dim;
+	if constexpr (!wt_dense_one_gpu<WT>()) { // (q4 and e4m3 run on one GPU only: yalm_decoder_create_tp / _tp_ipc refuse them)
+		if (d->ipc && ex >= 0)
+			return launch_gemv_d<WT, PPush<WT, 1>, false>(
+			    d, make_push<WT>(W, n, d->tp_rank == 0 ? d->x : nullptr, tpx_ex(d, ex), dim), v, nullptr, 0.f, kind);
+		if (d->comm && ex != EX_LOCAL) {
+			if (d->tp_rank == 0)
+				TRY((launch_gemv_d<WT, PAddTo<WT, 1>, false>(d, make_addto<WT>(W, n, d->xs, d->x, dim), v, nullptr, 0.f, kind)));
+			else
+				TRY((launch_gemv_d<WT, PStore<WT, 1>, false>(d, make_store<WT, 1>(W, n, d->xs, dim), v, nullptr, 0.f, kind)));
+			if (ncclAllReduce(d->xs, d->x, dim, ncclFloat, ncclSum, (ncclComm_t)d->comm, d->stream) != ncclSuccess) {
+				set_err("ncclAllReduce failed");
+				return YALM_ERR_HIP;
+			}
+			return YALM_OK;
 		}
-		if (!d->comm) { // one GPU (or the unread IPC case above)
-			PResidual<WT, 1> p;
-			p.W = (const char *)W;
-			p.n = n;
-			p.out = d->x;
-			p.n_groups = c.dim;
-			return launch_gemv_d<WT, PResidual<WT, 1>, false>(d, p, v, nullptr, 0.f, kind);
-		}
-		if (d->tp_rank == 0) {
-			PAddTo<WT, 1> p;
-			p.W = (const char *)W;
-			p.n = n;
-			p.out = d->xs;
-			p.base = d->x;
-			p.n_groups = c.dim;
-			TRY((launch_gemv<WT, PAddTo<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st)));
-		} else {
-			PStore<WT, 1> p;
-			p.W = (const char *)W;
-			p.n = n;
-			p.out = d->xs;
-			p.n_groups = c.dim;
-			TRY((launch_gemv<WT, PStore<WT, 1>, false>(p, v, nullptr, 0.f, kind, d->gemv[kind], st)));
-		}
-		if (ncclAllReduce(d->xs, d->x, c.dim, ncclFloat, ncclSum, (ncclComm_t)d->comm, st) != ncclSuccess) {
-			set_err("ncclAllReduce failed");
-			return YALM_ERR_HIP;
-		}
-		return YALM_OK;
 	}
+	// one GPU, the unread IPC case above, or the timing hook
+	return launch_gemv_d<WT, PResidual<WT, 1>, false>(d, make_residual<WT>(W, n, d->x, dim), v, nullptr, 0.f, kind);
 }
 
 // The exchange descriptor for a consumer launch (tp_exchange.h). Up to TPX_STAGE_MAX_RANKS
@@ -977,6 +939,8 @@ static int enqueue_residual_gemv(yalm_decoder_s *d, const void *W, int n, const 
 // hold every CU a peer's producer needs (a deadlock the bounded wait only reports). One GPU
 // per rank (the real configuration) needs no gate: the consumer waits inside its own launch.
 static TpX tpx_consume(yalm_decoder_s *d, int ex, int n) {
+	if (!d->ipc || ex < 0) // a local x: one GPU, RCCL (x all-reduced in place), the timing hook
+		return TpX{};
 	if (d->tpx_collect) { // many ranks: x summed once by a collect launch, the consumer stages it as on one GPU
 		tpx_collect_kernel<<<TPX_COLLECT_WG, 256, 0, d->stream>>>(tpx_ex(d, ex), n, 0, d->x);
 		return TpX{};
@@ -992,47 +956,71 @@ static MoeArgs moe_layer_args(const yalm_decoder_s *d, int l) {
 	               d->moe_sel + (size_t)l * d->moe_K, d->moe_wts + (size_t)l * d->moe_K, d->hb};
 }
 
-// The QKV policy of one layer's weights on the decoder's single-row state (the multi-row verify
+// ---- the launches of a layer, one function each: enqueue_layer_t calls them in order with the
+// layer's exchanges, the timing hook (enqueue_one_t) one of them with none. Beside each, the policy
+// name yalm_kernel_name reports for it, chosen by the same condition as the launch.
+
+// The QKV policy a decoder's layers run: q / k normed (yalm_decoder_set_qk_norm) and biased
+// (yalm_decoder_set_qkv_bias) models are never tensor parallel, and no form runs both.
+enum QkvForm { QKV_PLAIN, QKV_BIAS, QKV_NORM };
+static QkvForm qkv_form(const yalm_decoder_s *d) {
+	return !d->gq.empty() ? QKV_NORM : !d->bq.empty() ? QKV_BIAS : QKV_PLAIN;
+}
+static const char *qkv_policy_name(const yalm_decoder_s *d) {
+	static const char *const names[] = {", PQKV<", ", PQKVB<", ", PQKVN<"};
+	return names[qkv_form(d)];
+}
+static bool moe_ffn(const yalm_decoder_s *d) {
+	return d->moe_E > 0;
+}
+static const char *glu_policy_name(const yalm_decoder_s *d) {
+	return moe_ffn(d) ? ", PMoeGlu<" : ", PGlu<";
+}
+static const char *w2_policy_name(const yalm_decoder_s *d) {
+	return moe_ffn(d) ? ", PMoeW2" : ", PResidual<";
+}
+static const char *const WO_POLICY_NAME = ", PResidual<", *const CLS_POLICY_NAME = ", PStore<";
+// the router launch's kernel (moe_router_kernel<WT, NORM>) ahead of the weight type; none on a dense decoder
+static const char *router_kernel_name(const yalm_decoder_s *d) {
+	return moe_ffn(d) ? "moe_router_kernel<" : "";
+}
+
+// The QKV policy of layer l's weights on the decoder's single-row state (the multi-row verify
 // step points step / q_out at its row states).
 template <class WT>
-static PQKV<WT> make_pqkv(const yalm_decoder_s *d, const yalm_block_weights &w) {
+static PQKV<WT> make_pqkv(const yalm_decoder_s *d, int l) {
 	const yalm_config &c = d->c;
-	PQKV<WT> p;
-	p.wq = (const char *)w.wq;
-	p.wk = (const char *)w.wk;
-	p.wv = (const char *)w.wv;
-	p.n = c.dim;
-	p.q_dim = c.n_heads * c.head_dim;
-	p.kv_dim = c.n_kv_heads * c.head_dim;
-	p.head_dim = c.head_dim;
-	p.n_groups = (p.q_dim + 2 * p.kv_dim) / 2;
-	p.qkv_clip = c.qkv_clip;
-	p.inv_freq = d->inv_freq;
-	p.step = d->step;
-	p.q_out = d->q;
-	p.kcache = w.key_cache;
-	p.vcache = w.value_cache;
-	return p;
+	const yalm_block_weights &w = d->b[l];
+	return make_pqkv<WT>(w.wq, w.wk, w.wv, c.dim, c.n_heads, c.n_kv_heads, c.head_dim, c.qkv_clip, d->inv_freq, d->step,
+	                     d->q, w.key_cache, w.value_cache);
 }
 // ... with layer l's q / k / v bias (yalm_decoder_set_qkv_bias)
 template <class WT>
 static PQKVB<WT> make_pqkvb(const yalm_decoder_s *d, int l) {
-	PQKVB<WT> p;
-	static_cast<PQKV<WT> &>(p) = make_pqkv<WT>(d, d->b[l]);
-	p.bq = d->bq[l];
-	p.bk = d->bk[l];
-	p.bv = d->bv[l];
-	return p;
+	return {make_pqkv<WT>(d, l), d->bq[l], d->bk[l], d->bv[l]};
 }
-
 // ... ahead of layer l's q / k norm (yalm_decoder_set_qk_norm): q and k raw into qk_raw
 template <class WT>
 static PQKVN<WT> make_pqkvn(const yalm_decoder_s *d, int l) {
-	PQKVN<WT> p;
-	static_cast<PQKV<WT> &>(p) = make_pqkv<WT>(d, d->b[l]);
-	p.raw = d->qk_raw;
-	return p;
+	return {make_pqkv<WT>(d, l), d->qk_raw};
 }
+
+// QKV GEMV of layer l; consume_ex >= 0 (IPC tensor parallelism): its x is that exchange.
+template <class WT>
+static int enqueue_qkv(yalm_decoder_s *d, int l, int consume_ex) {
+	const yalm_config &c = d->c;
+	const float *nw = d->b[l].rms_att;
+	const TpX tin = tpx_consume(d, consume_ex, c.dim);
+	switch (qkv_form(d)) {
+	case QKV_NORM:
+		return launch_gemv_d<WT, PQKVN<WT>, true>(d, make_pqkvn<WT>(d, l), d->x, nw, c.norm_eps, GK_QKV, tin);
+	case QKV_BIAS:
+		return launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, nw, c.norm_eps, GK_QKV, tin);
+	default:
+		return launch_gemv_d<WT, PQKV<WT>, true>(d, make_pqkv<WT>(d, l), d->x, nw, c.norm_eps, GK_QKV, tin);
+	}
+}
+
 // The q / k norm launch of layer l over `rows` rows (qk_norm.h): raw rows of qk_raw, the step
 // states step[0 .. rows), q rows of q_dim at q_out. One wave per workgroup, n_heads + n_kv_heads
 // workgroups per row: four waves per workgroup over a quarter as many CUs measured the same at
@@ -1047,61 +1035,73 @@ static int launch_qk_norm(yalm_decoder_s *d, int l, int rows, const StepState *s
 	return YALM_OK;
 }
 
+// Attention of layer l for one row: its step state and q, its output row.
+static int enqueue_attn(yalm_decoder_s *d, int l, const float *q, const StepState *step, float *out) {
+	const yalm_config &c = d->c;
+	return launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, q, d->b[l].key_cache, d->b[l].value_cache, step,
+	                   c.max_seq_len, d->part, l, c.n_layers, d->awo_err, nullptr, out, d->stream);
+}
+
+// x += Wo xb2; ex: the exchange its partial is (enqueue_residual_gemv).
+template <class WT>
+static int enqueue_wo(yalm_decoder_s *d, int l, int ex) {
+	return enqueue_residual_gemv<WT>(d, d->b[l].wo, d->c.n_heads * d->c.head_dim, d->xb2, GK_WO, ex);
+}
+
+// Router of layer l's experts (never tensor parallel; no q4 or e4m3 experts: yalm_decoder_create_moe refuses).
+template <class WT>
+static int enqueue_router(yalm_decoder_s *d, int l) {
+	if constexpr (!wt_dense_one_gpu<WT>()) {
+		if (moe_ffn(d))
+			return launch_moe_router<WT, true>(moe_layer_args(d, l), d->x, d->b[l].rms_ffn, d->c.norm_eps, d->stream);
+	}
+	set_err("internal: the expert router needs a mixture-of-experts decoder");
+	return YALM_ERR_ARG;
+}
+
+// hb = act(W1 xn) * (W3 xn), xn the normed x: the selected experts' on layer l's last routing, or
+// the dense GLU, which consumes exchange consume_ex (the Wo partial) under IPC tensor parallelism.
+template <class WT>
+static int enqueue_glu(yalm_decoder_s *d, int l, int consume_ex) {
+	const yalm_config &c = d->c;
+	const yalm_block_weights &w = d->b[l];
+	if constexpr (!wt_dense_one_gpu<WT>()) {
+		if (moe_ffn(d))
+			return launch_moe_glu<WT, true>(moe_layer_args(d, l), d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], d->stream);
+	}
+	return launch_glu<WT, true>(w.w1, w.w3, c.dim, d->hb, c.hidden_dim, c.act, d->x, w.rms_ffn, c.norm_eps, GK_GLU,
+	                            d->gemv[GK_GLU], d->stream, tpx_consume(d, consume_ex, c.dim));
+}
+
+// x += W2 hb (the selected experts' W2 on their hb rows); ex: the exchange its partial is.
+template <class WT>
+static int enqueue_w2(yalm_decoder_s *d, int l, int ex) {
+	if constexpr (!wt_dense_one_gpu<WT>()) {
+		if (moe_ffn(d))
+			return launch_moe_w2<WT>(moe_layer_args(d, l), d->x, d->gemv[GK_W2], d->stream);
+	}
+	return enqueue_residual_gemv<WT>(d, d->b[l].w2, d->c.hidden_dim, d->hb, GK_W2, ex);
+}
+
 // One layer. IPC tensor parallelism (tp_exchange.h): the Wo partial is exchange ex0 (the GLU
 // consumes it), the W2 partial exchange ex0 + 1 (push_w2; the next QKV or the logits GEMV
 // consumes it); x_exchanged: the layer's input x is exchange ex0 - 1 (the QKV GEMV consumes
 // it), not a local x (the embedding of layer 0, or the x yalm_block / yalm_set_x left).
 template <class WT>
 static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, bool push_w2) {
-	const yalm_config &c = d->c;
-	const yalm_block_weights &w = d->b[l];
-	hipStream_t st = d->stream;
-	const int q_dim = c.n_heads * c.head_dim;
-	const TpX none{};
-	if (!d->gq.empty()) { // a q / k normed model (yalm_decoder_set_qk_norm; never tensor parallel, never biased)
-		TRY((launch_gemv_d<WT, PQKVN<WT>, true>(d, make_pqkvn<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV, none)));
+	TRY(enqueue_qkv<WT>(d, l, x_exchanged ? ex0 - 1 : -1));
+	if (qkv_form(d) == QKV_NORM)
 		TRY(launch_qk_norm(d, l, 1, d->step, d->q));
-	} else if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias; never tensor parallel)
-		TRY((launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV, none)));
-	} else {
-		const PQKV<WT> p = make_pqkv<WT>(d, w);
-		TRY((launch_gemv_d<WT, PQKV<WT>, true>(d, p, d->x, w.rms_att, c.norm_eps, GK_QKV,
-		                                         d->ipc && x_exchanged ? tpx_consume(d, ex0 - 1, c.dim) : none)));
-	}
 	if (d->attn_wo && wt_fused_wo<WT>()) {
-		TRY(launch_attn_wo<WT>(d, w, l, ex0));
+		TRY(launch_attn_wo<WT>(d, l, ex0));
 	} else {
-		TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, d->q, w.key_cache, w.value_cache, d->step, c.max_seq_len,
-		                d->part, l, c.n_layers, d->awo_err, nullptr, d->xb2, st));
-		TRY(enqueue_residual_gemv<WT>(d, w.wo, q_dim, d->xb2, GK_WO, ex0));
+		TRY(enqueue_attn(d, l, d->q, d->step, d->xb2));
+		TRY(enqueue_wo<WT>(d, l, ex0));
 	}
-	if constexpr (!wt_dense_one_gpu<WT>()) { // (no q4 or e4m3 experts: yalm_decoder_create_moe refuses)
-		if (d->moe_E > 0) { // router, then the selected experts' FFN (never tensor parallel)
-			const MoeArgs a = moe_layer_args(d, l);
-			TRY((launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, st)));
-			TRY((launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], st)));
-			return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], st);
-		}
-	}
-	// the GLU consumes the Wo exchange under IPC tensor parallelism
-	if (c.act == YALM_SILU) {
-		PGlu<WT, 1> p;
-		p.w1 = (const char *)w.w1;
-		p.w3 = (const char *)w.w3;
-		p.n = c.dim;
-		p.out = d->hb;
-		p.n_groups = c.hidden_dim;
-		TRY((launch_gemv_d<WT, PGlu<WT, 1>, true>(d, p, d->x, w.rms_ffn, c.norm_eps, GK_GLU, d->ipc ? tpx_consume(d, ex0, c.dim) : none)));
-	} else {
-		PGlu<WT, 0> p;
-		p.w1 = (const char *)w.w1;
-		p.w3 = (const char *)w.w3;
-		p.n = c.dim;
-		p.out = d->hb;
-		p.n_groups = c.hidden_dim;
-		TRY((launch_gemv_d<WT, PGlu<WT, 0>, true>(d, p, d->x, w.rms_ffn, c.norm_eps, GK_GLU, d->ipc ? tpx_consume(d, ex0, c.dim) : none)));
-	}
-	return enqueue_residual_gemv<WT>(d, w.w2, c.hidden_dim, d->hb, GK_W2, push_w2 ? ex0 + 1 : -1);
+	if (moe_ffn(d))
+		TRY(enqueue_router<WT>(d, l));
+	TRY(enqueue_glu<WT>(d, l, ex0));
+	return enqueue_w2<WT>(d, l, push_w2 ? ex0 + 1 : -1);
 }
 
 // Final norm + classifier rows of this rank. IPC tensor parallelism: consume_ex >= 0 = the
@@ -1110,34 +1110,18 @@ static int enqueue_layer_t(yalm_decoder_s *d, int l, int ex0, bool x_exchanged, 
 template <class WT>
 static int enqueue_logits_t(yalm_decoder_s *d, int consume_ex, int push_ex) {
 	const yalm_config &c = d->c;
-	const TpX tin = consume_ex >= 0 ? tpx_consume(d, consume_ex, c.dim) : TpX{};
+	const TpX tin = tpx_consume(d, consume_ex, c.dim);
 	if constexpr (!wt_dense_one_gpu<WT>()) {
-		if (push_ex >= 0) {
-			PPush<WT, 1> p;
-			p.W = (const char *)d->wcls;
-			p.n = c.dim;
-			p.base = nullptr;
-			p.t = tpx_ex(d, push_ex);
-			p.offset = 0;
-			p.n_groups = c.vocab_size;
-			return launch_gemv<WT, PPush<WT, 1>, true>(p, d->x, d->rms_final, c.norm_eps, GK_CLS, d->gemv[GK_CLS],
-			                                           d->stream, tin);
-		}
+		if (push_ex >= 0)
+			return launch_gemv_d<WT, PPush<WT, 1>, true>(
+			    d, make_push<WT>(d->wcls, c.dim, nullptr, tpx_ex(d, push_ex), c.vocab_size), d->x, d->rms_final, c.norm_eps,
+			    GK_CLS, tin);
 	}
-	if (c.vocab_size % 2 == 0) {
-		PStore<WT, 2> p;
-		p.W = (const char *)d->wcls;
-		p.n = c.dim;
-		p.out = d->logits_local;
-		p.n_groups = c.vocab_size / 2;
-		return launch_gemv_d<WT, PStore<WT, 2>, true>(d, p, d->x, d->rms_final, c.norm_eps, GK_CLS, tin);
-	}
-	PStore<WT, 1> p;
-	p.W = (const char *)d->wcls;
-	p.n = c.dim;
-	p.out = d->logits_local;
-	p.n_groups = c.vocab_size;
-	return launch_gemv_d<WT, PStore<WT, 1>, true>(d, p, d->x, d->rms_final, c.norm_eps, GK_CLS, tin);
+	if (c.vocab_size % 2 == 0)
+		return launch_gemv_d<WT, PStore<WT, 2>, true>(d, make_store<WT, 2>(d->wcls, c.dim, d->logits_local, c.vocab_size),
+		                                              d->x, d->rms_final, c.norm_eps, GK_CLS, tin);
+	return launch_gemv_d<WT, PStore<WT, 1>, true>(d, make_store<WT, 1>(d->wcls, c.dim, d->logits_local, c.vocab_size),
+	                                              d->x, d->rms_final, c.norm_eps, GK_CLS, tin);
 }
 
 template <class WT>
@@ -1254,9 +1238,7 @@ static int validate_config(const yalm_config *c) {
 	           c->vocab_size > 0 && c->max_seq_len > 2,
 	       "config: non-positive dimension");
 	ARGCHK(c->n_heads % c->n_kv_heads == 0, "config: n_heads % n_kv_heads != 0");
-	ARGCHK(c->weight_dtype == YALM_F32 || c->weight_dtype == YALM_F16 || c->weight_dtype == YALM_F8E5M2 ||
-	           c->weight_dtype == YALM_Q4 || c->weight_dtype == YALM_E4M3,
-	       "config: weight_dtype must be F32, F16, F8E5M2, Q4 or E4M3");
+	ARGCHK(dtype_ok(c->weight_dtype), "config: weight_dtype must be F32, F16, F8E5M2, Q4 or E4M3");
 	ARGCHK(c->dim % 16 == 0 && c->hidden_dim % 16 == 0 && (c->n_heads * c->head_dim) % 16 == 0,
 	       "config: dim, hidden_dim and n_heads*head_dim must be multiples of 16 (infer.cpp:66)");
 	ARGCHK(c->weight_dtype != YALM_Q4 ||
@@ -1959,8 +1941,7 @@ extern "C" int yalm_rows_plan(int dtype, int n, int n_groups, int T, int cus, in
 		set_err(std::string("yalm_rows_plan") + ROWS_Q4_WHY);
 		return YALM_ERR_UNSUPPORTED;
 	}
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_E4M3,
-	       "yalm_rows_plan: bad dtype");
+	ARGCHK(dtype_ok(dtype), "yalm_rows_plan: bad dtype");
 	ARGCHK(n > 0 && n_groups > 0 && cus >= 0 && T >= 1 && T <= ROWS_MAX_T, "yalm_rows_plan: bad argument");
 	const int EPL = dtype == YALM_F32 ? WF32::EPL : dtype == YALM_F16 ? WF16::EPL : WF8::EPL; // (e4m3: WF8's)
 	static_assert(WE4M3::EPL == WF8::EPL, "e4m3 plans as fp8");
@@ -1995,17 +1976,36 @@ static int launch_rows(const P &p, const float *x, int xstride, const float *nor
 	return YALM_OK;
 }
 
+// ---- the multi-row policies, filled (the rows forward and yalm_matmul_rows build theirs here): `rows`
+// weight rows of n elements, the T outputs ostride floats apart
+template <class WT>
+static RStore<WT> make_rstore(const void *W, int n, int rows, float *out, int ostride) {
+	return {(const char *)W, n, rows, (rows + 1) / 2, out, ostride};
+}
+template <class WT>
+static RResidual<WT> make_rresidual(const void *W, int n, int rows, float *out, int ostride) {
+	return {(const char *)W, n, rows, (rows + 1) / 2, out, ostride};
+}
 template <class WT, int ACT>
-static int launch_rows_glu(yalm_decoder_s *d, const yalm_block_weights &w, int T) {
-	const yalm_config &c = d->c;
-	RGlu<WT, ACT> p;
-	p.w1 = (const char *)w.w1;
-	p.w3 = (const char *)w.w3;
-	p.n = c.dim;
-	p.n_groups = c.hidden_dim;
-	p.out = d->rhb;
-	p.ostride = c.hidden_dim;
-	return launch_rows<WT, RGlu<WT, ACT>, true>(p, d->rx, c.dim, w.rms_ffn, c.norm_eps, T, d->stream);
+static RGlu<WT, ACT> make_rglu(const void *w1, const void *w3, int n, int hidden, float *out, int ostride) {
+	return {(const char *)w1, (const char *)w3, n, hidden, out, ostride};
+}
+// a PQKV, PQKVB or PQKVN base as RQKV, RQKVB or RQKVN on the T row states: q rows (RQKVN: raw rows) `stride` apart
+// (RQKVN gets q_out = rq as the others do: PQKVN's epilogue and the V path of PQKV's never read q_out)
+template <class RP, class BP>
+static RP make_rqkv(BP base, const StepState *rstep, float *rq, int stride) {
+	base.step = rstep;
+	base.q_out = rq;
+	return {base, base.n, base.n_groups, stride};
+}
+template <class WT, bool NORM>
+static int launch_rows_glu(const void *w1, const void *w3, int n, int hidden, float *out, int ostride, int act,
+                           const float *x, int xstride, const float *normw, float eps, int T, hipStream_t st) {
+	if (act == YALM_SILU)
+		return launch_rows<WT, RGlu<WT, 1>, NORM>(make_rglu<WT, 1>(w1, w3, n, hidden, out, ostride), x, xstride, normw, eps,
+		                                          T, st);
+	return launch_rows<WT, RGlu<WT, 0>, NORM>(make_rglu<WT, 0>(w1, w3, n, hidden, out, ostride), x, xstride, normw, eps, T,
+	                                          st);
 }
 
 // T rows through every layer: rows begin, then per layer QKV (+ clip, RoPE, KV write), one
@@ -2026,71 +2026,32 @@ static int enqueue_rows_forward_t(yalm_decoder_s *d, int T, int from_step) {
 		HIPCHK(hipGetLastError());
 		for (int l = 0; l < c.n_layers; ++l) {
 			const yalm_block_weights &w = d->b[l];
-			if (!d->gq.empty()) { // a q / k normed model: raw rows, then one norm launch for all T rows
-				RQKVN<WT> p;
-				p.base = make_pqkvn<WT>(d, l);
-				p.base.step = d->rstep;
-				p.n = c.dim;
-				p.n_groups = p.base.n_groups;
-				p.raw_stride = q_dim + c.n_kv_heads * c.head_dim;
-				TRY((launch_rows<WT, RQKVN<WT>, true>(p, d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
+			switch (qkv_form(d)) {
+			case QKV_NORM: // raw rows, then one norm launch for all T rows
+				TRY((launch_rows<WT, RQKVN<WT>, true>(
+				    make_rqkv<RQKVN<WT>>(make_pqkvn<WT>(d, l), d->rstep, d->rq, q_dim + c.n_kv_heads * c.head_dim), d->rx,
+				    c.dim, w.rms_att, c.norm_eps, T, st)));
 				TRY(launch_qk_norm(d, l, T, d->rstep, d->rq));
-			} else if (!d->bq.empty()) { // a biased model (yalm_decoder_set_qkv_bias)
-				RQKVB<WT> p;
-				p.base = make_pqkvb<WT>(d, l);
-				p.base.step = d->rstep;
-				p.base.q_out = d->rq;
-				p.n = c.dim;
-				p.n_groups = p.base.n_groups;
-				p.q_stride = q_dim;
-				TRY((launch_rows<WT, RQKVB<WT>, true>(p, d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
-			} else {
-				RQKV<WT> p;
-				p.base = make_pqkv<WT>(d, w);
-				p.base.step = d->rstep;
-				p.base.q_out = d->rq;
-				p.n = c.dim;
-				p.n_groups = p.base.n_groups;
-				p.q_stride = q_dim;
-				TRY((launch_rows<WT, RQKV<WT>, true>(p, d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
+				break;
+			case QKV_BIAS:
+				TRY((launch_rows<WT, RQKVB<WT>, true>(make_rqkv<RQKVB<WT>>(make_pqkvb<WT>(d, l), d->rstep, d->rq, q_dim),
+				                                      d->rx, c.dim, w.rms_att, c.norm_eps, T, st)));
+				break;
+			default:
+				TRY((launch_rows<WT, RQKV<WT>, true>(make_rqkv<RQKV<WT>>(make_pqkv<WT>(d, l), d->rstep, d->rq, q_dim), d->rx,
+				                                     c.dim, w.rms_att, c.norm_eps, T, st)));
 			}
 			for (int t = 0; t < T; ++t)
-				TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, d->rq + (size_t)t * q_dim, w.key_cache,
-				                w.value_cache, d->rstep + t, c.max_seq_len, d->part, l, c.n_layers, d->awo_err, nullptr,
-				                d->rxb2 + (size_t)t * q_dim, st));
-			{
-				RResidual<WT> p;
-				p.W = (const char *)w.wo;
-				p.n = q_dim;
-				p.n_rows = c.dim;
-				p.n_groups = (c.dim + 1) / 2;
-				p.out = d->rx;
-				p.ostride = c.dim;
-				TRY((launch_rows<WT, RResidual<WT>, false>(p, d->rxb2, q_dim, nullptr, 0.f, T, st)));
-			}
-			if (c.act == YALM_SILU)
-				TRY((launch_rows_glu<WT, 1>(d, w, T)));
-			else
-				TRY((launch_rows_glu<WT, 0>(d, w, T)));
-			{
-				RResidual<WT> p;
-				p.W = (const char *)w.w2;
-				p.n = c.hidden_dim;
-				p.n_rows = c.dim;
-				p.n_groups = (c.dim + 1) / 2;
-				p.out = d->rx;
-				p.ostride = c.dim;
-				TRY((launch_rows<WT, RResidual<WT>, false>(p, d->rhb, c.hidden_dim, nullptr, 0.f, T, st)));
-			}
+				TRY(enqueue_attn(d, l, d->rq + (size_t)t * q_dim, d->rstep + t, d->rxb2 + (size_t)t * q_dim));
+			TRY((launch_rows<WT, RResidual<WT>, false>(make_rresidual<WT>(w.wo, q_dim, c.dim, d->rx, c.dim), d->rxb2, q_dim,
+			                                           nullptr, 0.f, T, st)));
+			TRY((launch_rows_glu<WT, true>(w.w1, w.w3, c.dim, c.hidden_dim, d->rhb, c.hidden_dim, c.act, d->rx, c.dim,
+			                               w.rms_ffn, c.norm_eps, T, st)));
+			TRY((launch_rows<WT, RResidual<WT>, false>(make_rresidual<WT>(w.w2, c.hidden_dim, c.dim, d->rx, c.dim), d->rhb,
+			                                           c.hidden_dim, nullptr, 0.f, T, st)));
 		}
-		RStore<WT> p;
-		p.W = (const char *)d->wcls;
-		p.n = c.dim;
-		p.n_rows = c.vocab_size;
-		p.n_groups = (c.vocab_size + 1) / 2;
-		p.out = d->rlogits;
-		p.ostride = c.vocab_size;
-		return launch_rows<WT, RStore<WT>, true>(p, d->rx, c.dim, d->rms_final, c.norm_eps, T, st);
+		return launch_rows<WT, RStore<WT>, true>(make_rstore<WT>(d->wcls, c.dim, c.vocab_size, d->rlogits, c.vocab_size),
+		                                         d->rx, c.dim, d->rms_final, c.norm_eps, T, st);
 	}
 }
 
@@ -2349,71 +2310,42 @@ extern "C" int yalm_get_logits(yalm_decoder d, float *host) {
 	return YALM_OK;
 }
 
+// One launch of kernel_id on layer l: the forward's own launch functions with a local x (the
+// timing hooks never take part in an exchange, except kernels 6 and 8); written out here are only
+// the launches without a counterpart in the forward, each on its scratch step state.
 template <class WT>
 static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 	const yalm_config &c = d->c;
-	const yalm_block_weights &w = d->b[l];
-	const int q_dim = c.n_heads * c.head_dim;
-	if constexpr (!wt_dense_one_gpu<WT>()) {
-		if (d->moe_E > 0 && (kernel_id == 3 || kernel_id == 4 || kernel_id == 9)) { // the layer's last routing
-			const MoeArgs a = moe_layer_args(d, l);
-			if (kernel_id == 9)
-				return launch_moe_router<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->stream);
-			if (kernel_id == 3)
-				return launch_moe_glu<WT, true>(a, d->x, w.rms_ffn, c.norm_eps, d->gemv[GK_GLU], d->stream);
-			return launch_moe_w2<WT>(a, d->x, d->gemv[GK_W2], d->stream);
-		}
-	}
 	switch (kernel_id) {
-	case 0:
-	case 2:
-	case 3:
-	case 4: {
-		// reuse the layer enqueue path for exactly one kernel
-		if (kernel_id == 0) {
-			if (!d->gq.empty())
-				return launch_gemv_d<WT, PQKVN<WT>, true>(d, make_pqkvn<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV);
-			if (!d->bq.empty())
-				return launch_gemv_d<WT, PQKVB<WT>, true>(d, make_pqkvb<WT>(d, l), d->x, w.rms_att, c.norm_eps, GK_QKV);
-			return launch_gemv_d<WT, PQKV<WT>, true>(d, make_pqkv<WT>(d, w), d->x, w.rms_att, c.norm_eps, GK_QKV);
-		}
-		if (kernel_id == 2 || kernel_id == 4) {
-			PResidual<WT, 1> p;
-			p.W = (const char *)(kernel_id == 2 ? w.wo : w.w2);
-			p.n = kernel_id == 2 ? q_dim : c.hidden_dim;
-			p.out = d->x;
-			p.n_groups = c.dim;
-			return launch_gemv_d<WT, PResidual<WT, 1>, false>(d, p, kernel_id == 2 ? d->xb2 : d->hb, nullptr, 0.f,
-			                                                  kernel_id == 2 ? GK_WO : GK_W2);
-		}
-		PGlu<WT, 1> p;
-		p.w1 = (const char *)w.w1;
-		p.w3 = (const char *)w.w3;
-		p.n = c.dim;
-		p.out = d->hb;
-		p.n_groups = c.hidden_dim;
-		return launch_gemv_d<WT, PGlu<WT, 1>, true>(d, p, d->x, w.rms_ffn, c.norm_eps, GK_GLU);
-	}
-	case 1:
-		return launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, d->q, w.key_cache, w.value_cache, d->step,
-		                   c.max_seq_len, d->part, l, c.n_layers, d->awo_err, nullptr, d->xb2, d->stream);
-	case 5: // (local x: the timing hooks never take part in an exchange, except kernels 6 and 8)
+	case KID_QKV:
+		return enqueue_qkv<WT>(d, l, -1);
+	case KID_ATTN:
+		return enqueue_attn(d, l, d->q, d->step, d->xb2);
+	case KID_WO:
+		return enqueue_wo<WT>(d, l, EX_LOCAL);
+	case KID_GLU: // (experts: on the layer's last routing)
+		return enqueue_glu<WT>(d, l, -1);
+	case KID_W2:
+		return enqueue_w2<WT>(d, l, EX_LOCAL);
+	case KID_CLS:
 		return enqueue_logits_t<WT>(d, -1, -1);
-	case 6:
+	case KID_EXCHANGE:
 		return enqueue_exchange(d);
-	case 8: // fused attention + Wo (IPC: pushing exchange 0 of the bumped sequence, unread)
+	case KID_ATTN_WO: // fused attention + Wo (IPC: pushing exchange 0 of the bumped sequence, unread)
 		if constexpr (wt_fused_wo<WT>())
-			return launch_attn_wo<WT>(d, w, l, 0);
+			return launch_attn_wo<WT>(d, l, 0);
 		break;
-	case 11: // the q / k norm launch on whatever the last QKV launch left in qk_raw
+	case KID_ROUTER:
+		return enqueue_router<WT>(d, l);
+	case KID_QK_NORM: // the q / k norm launch on whatever the last QKV launch left in qk_raw
 		return launch_qk_norm(d, l, 1, d->step, d->q);
-	case 10: // the sampling launch on the current logits; commits into a scratch step state
+	case KID_SAMPLE: // the sampling launch on the current logits; commits into a scratch step state
 		sample_kernel<<<1, SMP_THREADS, 0, d->stream>>>(d->logits, c.vocab_size, d->smp_params, d->smp_u, 1,
 		                                                d->smp_step, nullptr, 0, nullptr, nullptr);
 		HIPCHK(hipGetLastError());
 		return YALM_OK;
 	// the launches that end a 4-row speculative step, on the rows' current logits and a scratch step state
-	case 12:
+	case KID_SPEC_SAMPLE:
 		if (c.vocab_size % 4 == 0)
 			spec_sample_rows_kernel<true><<<SPEC_MAX_ROWS, SMP_THREADS, 0, d->stream>>>(
 			    d->rlogits, c.vocab_size, c.vocab_size, d->smp_params, d->smp_u, 1, d->smp_step, d->spec, nullptr);
@@ -2422,11 +2354,11 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 			    d->rlogits, c.vocab_size, c.vocab_size, d->smp_params, d->smp_u, 1, d->smp_step, d->spec, nullptr);
 		HIPCHK(hipGetLastError());
 		return YALM_OK;
-	case 13:
+	case KID_SPEC_ACCEPT:
 		spec_accept_kernel<<<1, 64, 0, d->stream>>>(SPEC_MAX_ROWS, d->smp_step, d->spec, d->tokens, 0);
 		HIPCHK(hipGetLastError());
 		return YALM_OK;
-	case 14:
+	case KID_SPEC_VERIFY:
 		spec_verify_kernel<<<1, 1024, 0, d->stream>>>(d->rlogits, c.vocab_size, SPEC_MAX_ROWS, d->smp_step, d->spec,
 		                                              d->tokens, 0);
 		HIPCHK(hipGetLastError());
@@ -2519,21 +2451,22 @@ static int time_loop(yalm_decoder_s *d, int kernel_id, int iters, bool bump, boo
 }
 
 extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms) {
-	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= 14 && kernel_id != 7,
+	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= KID_LAST && kernel_id != 7,
 	       "bad argument (kernel ids 0-6, 8-14)");
-	ARGCHK(kernel_id != 11 || !d->gq.empty(), "kernel 11 (q / k norm) needs yalm_decoder_set_qk_norm");
-	ARGCHK(kernel_id != 10 || (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
+	ARGCHK(kernel_id != KID_QK_NORM || qkv_form(d) == QKV_NORM, "kernel 11 (q / k norm) needs yalm_decoder_set_qk_norm");
+	ARGCHK(kernel_id != KID_SAMPLE || (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
 	       "kernel 10 (device sampling) needs a one-GPU decoder and a vocabulary of at most 131072");
-	if (kernel_id >= 12) { // the speculative step's last launches: a decoder with a multi-row form, its row buffers
+	if (kernel_id >= KID_SPEC_SAMPLE) { // the speculative step's last launches: a decoder with a multi-row form, its row buffers
 		TRY(rows_supported(d, "yalm_time_kernel (kernels 12-14)"));
 		ARGCHK(d->c.vocab_size <= SMP_MAX_N, "kernels 12-14 need a vocabulary of at most 131072");
 		TRY(rows_init(d));
 	}
-	ARGCHK(kernel_id != 9 || d->moe_E > 0, "kernel 9 (expert router) needs a mixture-of-experts decoder");
-	ARGCHK(kernel_id != 6 || d->comm || d->ipc, "kernel 6 (tensor-parallel exchange) needs a tensor-parallel decoder");
-	ARGCHK(kernel_id != 8 || d->attn_wo, "kernel 8 (fused attention + Wo) needs yalm_decoder_attn_wo");
+	ARGCHK(kernel_id != KID_ROUTER || moe_ffn(d), "kernel 9 (expert router) needs a mixture-of-experts decoder");
+	ARGCHK(kernel_id != KID_EXCHANGE || d->comm || d->ipc,
+	       "kernel 6 (tensor-parallel exchange) needs a tensor-parallel decoder");
+	ARGCHK(kernel_id != KID_ATTN_WO || d->attn_wo, "kernel 8 (fused attention + Wo) needs yalm_decoder_attn_wo");
 	// in-launch hand-offs and the IPC exchange: fresh tags per launch (one exchange per bump)
-	const bool bump = kernel_id == 1 || kernel_id == 8 || (kernel_id == 6 && d->ipc);
+	const bool bump = kernel_id == KID_ATTN || kernel_id == KID_ATTN_WO || (kernel_id == KID_EXCHANGE && d->ipc);
 	// the warm-up gets a fresh epoch too: under IPC it pushes exchange xbase + 0, whose slot
 	// parity the previous forward's argmax exchange (2 L, even) used -- without the bump a
 	// peer still reading that slot could see it overwritten (tp_exchange.h reuse rule)
@@ -2564,55 +2497,60 @@ extern "C" int yalm_set_gemv_config(yalm_decoder d, int kind, int threads, int u
 	return YALM_OK;
 }
 
+template <class WT>
+static const char *wt_name() {
+	return WT::NAME;
+}
+
 extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 	if (!d)
 		return "";
-	const char *wt = d->c.weight_dtype == YALM_F32   ? "WF32"
-	                 : d->c.weight_dtype == YALM_F16 ? "WF16"
-	                 : d->c.weight_dtype == YALM_Q4  ? "WQ4"
-	                 : d->c.weight_dtype == YALM_E4M3 ? "WE4M3"
-	                                                 : "WF8";
+	const char *wt = DISPATCH_WT(d->c.weight_dtype, wt_name);
 	const std::string gk = std::string("gemv_rb_kernel<") + wt;
 	std::string s;
 	switch (kernel_id) {
-	case 0:
-		s = gk + (!d->gq.empty() ? ", PQKVN<" : d->bq.empty() ? ", PQKV<" : ", PQKVB<");
+	case KID_QKV:
+		s = gk + qkv_policy_name(d);
 		break;
-	case 1:
+	case KID_ATTN:
 		s = "attn_decode_kernel<";
 		break;
-	case 2:
-	case 4:
-		s = gk + (kernel_id == 4 && d->moe_E > 0 ? ", PMoeW2" : ", PResidual<");
+	case KID_WO:
+		s = gk + WO_POLICY_NAME;
 		break;
-	case 3:
-		s = gk + (d->moe_E > 0 ? ", PMoeGlu<" : ", PGlu<");
+	case KID_GLU:
+		s = gk + glu_policy_name(d);
 		break;
-	case 9:
-		s = d->moe_E > 0 ? std::string("moe_router_kernel<") + wt : "";
+	case KID_W2:
+		s = gk + w2_policy_name(d);
 		break;
-	case 5:
-		s = gk + ", PStore<";
+	case KID_CLS:
+		s = gk + CLS_POLICY_NAME;
 		break;
-	case 6:
+	case KID_EXCHANGE:
 		s = d->ipc ? "tpx_collect_kernel" : d->comm ? "AllReduce" : "";
 		break;
-	case 8:
+	case KID_ATTN_WO:
 		s = std::string("attn_wo_kernel<") + wt + ", ";
 		break;
-	case 10:
+	case KID_ROUTER:
+		s = router_kernel_name(d);
+		if (!s.empty())
+			s += wt;
+		break;
+	case KID_SAMPLE:
 		s = "sample_kernel";
 		break;
-	case 11:
-		s = d->gq.empty() ? "" : "qk_norm_rope_kernel<";
+	case KID_QK_NORM:
+		s = qkv_form(d) == QKV_NORM ? "qk_norm_rope_kernel<" : "";
 		break;
-	case 12:
+	case KID_SPEC_SAMPLE:
 		s = "spec_sample_rows_kernel<";
 		break;
-	case 13:
+	case KID_SPEC_ACCEPT:
 		s = "spec_accept_kernel";
 		break;
-	case 14:
+	case KID_SPEC_VERIFY:
 		s = "spec_verify_kernel";
 		break;
 	default:
@@ -2623,9 +2561,9 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 }
 
 namespace {
-struct DevBufT {
+struct DevBuf { // a device allocation freed on scope exit
 	void *p = nullptr;
-	~DevBufT() {
+	~DevBuf() {
 		if (p)
 			(void)hipFree(p);
 	}
@@ -2662,7 +2600,7 @@ __global__ __launch_bounds__(512) void stream_read_kernel(const u32x4_t *__restr
 extern "C" int yalm_stream_envelope(size_t bytes, int iters, float *avg_ms) {
 	ARGCHK(avg_ms && iters > 0 && bytes >= (1u << 20), "yalm_stream_envelope: bad argument");
 	bytes &= ~(size_t)4095;
-	DevBufT buf[2];
+	DevBuf buf[2];
 	unsigned *out = nullptr;
 	for (auto &b : buf) {
 		HIPCHK(hipMalloc(&b.p, bytes));
@@ -2712,13 +2650,6 @@ extern "C" int yalm_stream_envelope(size_t bytes, int iters, float *avg_ms) {
 
 // ------------------------------------------------------------------ test API (host pointers)
 namespace {
-struct DevBuf {
-	void *p = nullptr;
-	~DevBuf() {
-		if (p)
-			(void)hipFree(p);
-	}
-};
 int up(DevBuf &b, const void *host, size_t bytes) {
 	HIPCHK(hipMalloc(&b.p, bytes ? bytes : 4));
 	if (host)
@@ -2727,25 +2658,17 @@ int up(DevBuf &b, const void *host, size_t bytes) {
 		HIPCHK(hipMemset(b.p, 0, bytes ? bytes : 4));
 	return YALM_OK;
 }
-size_t wbytes(int dtype) {
-	return dtype == YALM_F32 ? 4 : dtype == YALM_F16 ? 2 : 1;
-}
 } // namespace
 
 template <class WT>
 static int matmul_t(float *out, const float *x, const void *w, int n, int d) {
-	PStore<WT, 1> p;
-	p.W = (const char *)w;
-	p.n = n;
-	p.out = out;
-	p.n_groups = d;
-	return launch_gemv<WT, PStore<WT, 1>, false>(p, x, nullptr, 0.f, GK_GLU, GemvCfg{}, nullptr);
+	return launch_gemv<WT, PStore<WT, 1>, false>(make_store<WT, 1>(w, n, out, d), x, nullptr, 0.f, GK_GLU, GemvCfg{},
+	                                             nullptr);
 }
 
 extern "C" int yalm_matmul(float *xout, const float *x, const void *w, int n, int d, int dtype) {
 	ARGCHK(xout && x && w && n > 0 && d > 0, "bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3,
-	       "bad dtype");
+	ARGCHK(dtype_ok(dtype), "bad dtype");
 	ARGCHK(n % 16 == 0, "n must be a multiple of 16 (infer.cpp:66)");
 	ARGCHK(dtype != YALM_Q4 || n % 32 == 0, "q4: n must be a multiple of 32");
 	DevBuf dx, dw, dout;
@@ -2767,20 +2690,12 @@ static int matmul_rows_launch(const P &p, const float *x, int xstride, const flo
 template <class WT>
 static int matmul_rows_t(float *out, const float *x, const void *w, const void *w3, const float *normw, float eps,
                          int T, int n, int d, int xstride, int ostride, int epilogue, int act) {
-	if (epilogue == YALM_ROWS_GLU) {
-		if (act == YALM_SILU) {
-			RGlu<WT, 1> p{(const char *)w, (const char *)w3, n, d, out, ostride};
-			return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
-		}
-		RGlu<WT, 0> p{(const char *)w, (const char *)w3, n, d, out, ostride};
-		return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
-	}
-	if (epilogue == YALM_ROWS_RESIDUAL) {
-		RResidual<WT> p{(const char *)w, n, d, (d + 1) / 2, out, ostride};
-		return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
-	}
-	RStore<WT> p{(const char *)w, n, d, (d + 1) / 2, out, ostride};
-	return matmul_rows_launch<WT>(p, x, xstride, normw, eps, T);
+	if (epilogue == YALM_ROWS_GLU)
+		return normw ? launch_rows_glu<WT, true>(w, w3, n, d, out, ostride, act, x, xstride, normw, eps, T, nullptr)
+		             : launch_rows_glu<WT, false>(w, w3, n, d, out, ostride, act, x, xstride, nullptr, 0.f, T, nullptr);
+	if (epilogue == YALM_ROWS_RESIDUAL)
+		return matmul_rows_launch<WT>(make_rresidual<WT>(w, n, d, out, ostride), x, xstride, normw, eps, T);
+	return matmul_rows_launch<WT>(make_rstore<WT>(w, n, d, out, ostride), x, xstride, normw, eps, T);
 }
 
 extern "C" int yalm_matmul_rows(float *out, const float *x, const void *w, const void *w3, const float *normw,
@@ -2791,8 +2706,7 @@ extern "C" int yalm_matmul_rows(float *out, const float *x, const void *w, const
 		return YALM_ERR_UNSUPPORTED;
 	}
 	ARGCHK(out && x && w && n > 0 && d > 0, "yalm_matmul_rows: bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_E4M3,
-	       "yalm_matmul_rows: bad dtype");
+	ARGCHK(dtype_ok(dtype), "yalm_matmul_rows: bad dtype");
 	ARGCHK(T >= 1 && T <= ROWS_MAX_T, "yalm_matmul_rows: 1 <= T <= 4 rows");
 	ARGCHK(n % 16 == 0, "yalm_matmul_rows: n must be a multiple of 16 (infer.cpp:66)");
 	ARGCHK(xstride >= n && xstride % 4 == 0, "yalm_matmul_rows: xstride must be at least n and a multiple of 4");
@@ -2846,8 +2760,7 @@ static GemvPlan gemv_plan_dt(int policy, bool norm, int n, int n_groups, int kin
 static int gemv_cfg_check(const char *who, int dtype, int policy, int kind, int n, int threads, int unroll, int wpc,
                           int cus, int rows) {
 	const std::string w(who);
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3,
-	       w + ": bad dtype");
+	ARGCHK(dtype_ok(dtype), w + ": bad dtype");
 	ARGCHK(policy >= YALM_GEMV_STORE1 && policy <= YALM_GEMV_QKVN, w + ": bad policy");
 	ARGCHK(kind >= 0 && kind < GK_N, w + ": bad kind");
 	ARGCHK(n > 0 && n % 16 == 0, w + ": n must be a multiple of 16 (infer.cpp:66)");
@@ -2895,71 +2808,30 @@ static int gemv_one_launch(const yalm_gemv_args &a, const P &p, const GemvOneDev
 		return launch_gemv<WT, P, true>(p, v.x, v.normw, a.eps, a.kind, cfg, nullptr);
 	return launch_gemv<WT, P, false>(p, v.x, nullptr, 0.f, a.kind, cfg, nullptr);
 }
-template <class WT, class P>
-static void gemv_one_qkv(const yalm_gemv_args &a, const GemvOneDev &v, P &p) {
-	p.wq = (const char *)v.wq;
-	p.wk = (const char *)v.wk;
-	p.wv = (const char *)v.wv;
-	p.n = a.n;
-	p.q_dim = a.n_heads * a.head_dim;
-	p.kv_dim = a.n_kv_heads * a.head_dim;
-	p.head_dim = a.head_dim;
-	p.n_groups = (p.q_dim + 2 * p.kv_dim) / 2;
-	p.qkv_clip = a.qkv_clip;
-	p.inv_freq = nullptr; // (the epilogue reads the step's tables)
-	p.step = v.step;
-	p.q_out = v.q_out;
-	p.kcache = v.kc;
-	p.vcache = v.vc;
-}
 template <class WT>
 static int gemv_one_t(const yalm_gemv_args &a, const GemvOneDev &v, const GemvCfg &cfg) {
-	const char *w = (const char *)v.w;
 	switch (a.policy) {
-	case YALM_GEMV_STORE1: {
-		PStore<WT, 1> p{w, a.n, v.out, a.d};
+	case YALM_GEMV_STORE1:
+		return gemv_one_launch<WT>(a, make_store<WT, 1>(v.w, a.n, v.out, a.d), v, cfg);
+	case YALM_GEMV_STORE2:
+		return gemv_one_launch<WT>(a, make_store<WT, 2>(v.w, a.n, v.out, a.d), v, cfg);
+	case YALM_GEMV_RESIDUAL:
+		return gemv_one_launch<WT>(a, make_residual<WT>(v.w, a.n, v.out, a.d), v, cfg);
+	case YALM_GEMV_ADDTO:
+		return launch_gemv<WT, PAddTo<WT, 1>, false>(make_addto<WT>(v.w, a.n, v.out, v.base, a.d), v.x, nullptr, 0.f,
+		                                             a.kind, cfg, nullptr);
+	case YALM_GEMV_GLU:
+		return a.norm ? launch_glu<WT, true>(v.w, v.w3, a.n, v.out, a.d, a.act, v.x, v.normw, a.eps, a.kind, cfg, nullptr)
+		              : launch_glu<WT, false>(v.w, v.w3, a.n, v.out, a.d, a.act, v.x, nullptr, 0.f, a.kind, cfg, nullptr);
+	}
+	// the QKV policies (inv_freq null: the epilogue reads the step's tables)
+	const PQKV<WT> p = make_pqkv<WT>(v.wq, v.wk, v.wv, a.n, a.n_heads, a.n_kv_heads, a.head_dim, a.qkv_clip, nullptr,
+	                                 v.step, v.q_out, v.kc, v.vc);
+	if (a.policy == YALM_GEMV_QKV)
 		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	case YALM_GEMV_STORE2: {
-		PStore<WT, 2> p{w, a.n, v.out, a.d / 2};
-		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	case YALM_GEMV_RESIDUAL: {
-		PResidual<WT, 1> p{w, a.n, v.out, a.d};
-		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	case YALM_GEMV_ADDTO: {
-		PAddTo<WT, 1> p{w, a.n, v.out, v.base, a.d};
-		return launch_gemv<WT, PAddTo<WT, 1>, false>(p, v.x, nullptr, 0.f, a.kind, cfg, nullptr);
-	}
-	case YALM_GEMV_GLU: {
-		if (a.act == YALM_SILU) {
-			PGlu<WT, 1> p{w, (const char *)v.w3, a.n, v.out, a.d};
-			return gemv_one_launch<WT>(a, p, v, cfg);
-		}
-		PGlu<WT, 0> p{w, (const char *)v.w3, a.n, v.out, a.d};
-		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	case YALM_GEMV_QKV: {
-		PQKV<WT> p;
-		gemv_one_qkv<WT>(a, v, p);
-		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	case YALM_GEMV_QKVB: {
-		PQKVB<WT> p;
-		gemv_one_qkv<WT>(a, v, p);
-		p.bq = v.bq;
-		p.bk = v.bk;
-		p.bv = v.bv;
-		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	default: {
-		PQKVN<WT> p;
-		gemv_one_qkv<WT>(a, v, p);
-		p.raw = v.raw;
-		return gemv_one_launch<WT>(a, p, v, cfg);
-	}
-	}
+	if (a.policy == YALM_GEMV_QKVB)
+		return gemv_one_launch<WT>(a, PQKVB<WT>{p, v.bq, v.bk, v.bv}, v, cfg);
+	return gemv_one_launch<WT>(a, PQKVN<WT>{p, v.raw}, v, cfg);
 }
 
 extern "C" int yalm_gemv_one(const yalm_gemv_args *ap) {
@@ -3204,36 +3076,15 @@ extern "C" int yalm_spec_sample_rows(const float *logits, int n, int T, const ya
 template <class WT>
 static int ffn_t(float *out, const float *x, const void *w1, const void *w2, const void *w3, float *hb, int hidden,
                  int dim, int act) {
-	if (act == YALM_SILU) {
-		PGlu<WT, 1> p;
-		p.w1 = (const char *)w1;
-		p.w3 = (const char *)w3;
-		p.n = dim;
-		p.out = hb;
-		p.n_groups = hidden;
-		TRY((launch_gemv<WT, PGlu<WT, 1>, false>(p, x, nullptr, 0.f, GK_GLU, GemvCfg{}, nullptr)));
-	} else {
-		PGlu<WT, 0> p;
-		p.w1 = (const char *)w1;
-		p.w3 = (const char *)w3;
-		p.n = dim;
-		p.out = hb;
-		p.n_groups = hidden;
-		TRY((launch_gemv<WT, PGlu<WT, 0>, false>(p, x, nullptr, 0.f, GK_GLU, GemvCfg{}, nullptr)));
-	}
-	PStore<WT, 1> p;
-	p.W = (const char *)w2;
-	p.n = hidden;
-	p.out = out;
-	p.n_groups = dim;
-	return launch_gemv<WT, PStore<WT, 1>, false>(p, hb, nullptr, 0.f, GK_GLU, GemvCfg{}, nullptr);
+	TRY((launch_glu<WT, false>(w1, w3, dim, hb, hidden, act, x, nullptr, 0.f, GK_GLU, GemvCfg{}, nullptr)));
+	return launch_gemv<WT, PStore<WT, 1>, false>(make_store<WT, 1>(w2, hidden, out, dim), hb, nullptr, 0.f, GK_GLU,
+	                                             GemvCfg{}, nullptr);
 }
 
 extern "C" int yalm_ffn(float *xout, const float *x, const void *w1, const void *w2, const void *w3, int hidden_dim,
                         int dim, int act, int dtype) {
 	ARGCHK(xout && x && w1 && w2 && w3 && hidden_dim > 0 && dim > 0, "bad argument");
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3,
-	       "bad dtype");
+	ARGCHK(dtype_ok(dtype), "bad dtype");
 	ARGCHK(dim % 16 == 0 && hidden_dim % 16 == 0, "dims must be multiples of 16");
 	ARGCHK(dtype != YALM_Q4 || (dim % 32 == 0 && hidden_dim % 32 == 0), "q4: dims must be multiples of 32");
 	const size_t wb = yalm_row_bytes(dtype, dim) * (size_t)hidden_dim;   // w1, w3: hidden_dim rows of dim
@@ -3271,14 +3122,14 @@ extern "C" int yalm_moe_ffn(float *xout, int *experts, float *weights, const flo
 		set_err("yalm_moe_ffn: e4m3 weights have no mixture-of-experts form");
 		return YALM_ERR_UNSUPPORTED;
 	}
-	ARGCHK(dtype == YALM_F32 || dtype == YALM_F16 || dtype == YALM_F8E5M2, "bad dtype");
+	ARGCHK(dtype_ok(dtype), "bad dtype");
 	ARGCHK(dim % 16 == 0 && hidden_dim % 16 == 0, "dims must be multiples of 16");
 	ARGCHK(act == YALM_SILU || act == YALM_GELU, "bad activation");
 	TRY(validate_moe(n_experts, n_active));
-	const size_t wb = wbytes(dtype) * (size_t)n_experts * hidden_dim * dim;
+	const size_t wb = yalm_row_bytes(dtype, dim) * (size_t)n_experts * hidden_dim; // (E, hidden, dim); w2 (E, dim, hidden): as many
 	DevBuf dx, dg, d1, d2, d3, dhb, dout, dsel, dwts;
 	TRY(up(dx, x, sizeof(float) * dim));
-	TRY(up(dg, moegate, wbytes(dtype) * (size_t)n_experts * dim));
+	TRY(up(dg, moegate, yalm_row_bytes(dtype, dim) * (size_t)n_experts));
 	TRY(up(d1, w1, wb));
 	TRY(up(d2, w2, wb));
 	TRY(up(d3, w3, wb));
