@@ -587,6 +587,73 @@ int yalm_spec_sample_rows(const float *logits, int n, int T, const yalm_sampling
  * 1 <= m <= 131072; drafts_out[k - 1] = d_k for k = 1..rows-1, -1 for none. */
 int yalm_spec_draft(const int *history, int m, int rows, int ngram_max, int ngram_min, int *drafts_out);
 
+/* ---------------- batched decode: up to four independent sequences per weight pass ----------------
+ * A batch runs n_seq = 1..4 sequences through the multi-row path of yalm_forward_rows (csrc/batch.h):
+ * every weight matrix is streamed ONCE per step for all sequences, and every row yields a token on
+ * every step. Row s belongs to sequence s and to nothing else: it attends to its own KV cache, is
+ * fed its own (token, pos) and appends to its own token buffer. A row of the multi-row GEMV depends
+ * on neither the row count nor the other rows, so row s of a step equals yalm_forward_rows(T = 1)
+ * of the same token at the same position over the same history, bit for bit (logits and the KV row).
+ * Scope: that of yalm_forward_rows. Dense decoders on one GPU with f32, f16, fp8 (E5M2) or e4m3
+ * weights, with or without a q / k / v bias or the q / k norm. YALM_ERR_UNSUPPORTED, with a
+ * yalm_last_error naming the reason: q4 weights, mixture-of-experts decoders, tensor-parallel
+ * decoders. A decoder that never creates a batch launches exactly what it launched before. */
+typedef struct yalm_batch_s *yalm_batch;
+/* The batch owns, per sequence: a KV cache set (n_layers x K and V, max_seq_len x n_kv_heads x
+ * head_dim f16, the decoder's layout, zeroed), a device step state (token, pos, tokens produced), a
+ * token buffer of the decoder's capacity (65536) and a split-KV partial buffer; and the [n_seq][..]
+ * activation and logits buffers. It uses the decoder's stream, weights and model-family forms as
+ * they are when a call is made. The decoder must outlive the batch: destroying the decoder first is
+ * the caller's error (the batch then points at freed memory). yalm_batch_destroy syncs the stream.
+ * YALM_ERR_ARG: n_seq outside 1..4. */
+int yalm_batch_create(yalm_decoder d, int n_seq, yalm_batch *out);
+int yalm_batch_destroy(yalm_batch b);
+/* Copies KV rows [0, n_positions) of every layer from the DECODER's own caches into sequence seq
+ * (seq == -1: into every sequence): device to device, asynchronous on the decoder's stream. This is
+ * how prompts arrive -- hydrate the decoder with yalm_prefill / yalm_forward, then load -- and the
+ * fork for several completions of one prompt. Rows from n_positions on are not touched.
+ * YALM_ERR_ARG: n_positions outside [0, max_seq_len], seq outside -1 .. n_seq - 1. */
+int yalm_batch_load(yalm_batch b, int seq, int n_positions);
+/* One step without a commit. tokens, pos: host arrays of n_seq; row s feeds tokens[s] at pos[s],
+ * attends to keys 0 .. pos[s] of sequence s's cache and writes that cache's row pos[s].
+ * logits_host: [n_seq][vocab_size] floats (then the call is synchronous) or NULL. Each sequence's
+ * device (token, pos) is set to (tokens[s], pos[s]) and does not advance, as after
+ * yalm_forward_rows. YALM_ERR_ARG: a token out of range, pos[s] outside [0, max_seq_len). */
+int yalm_batch_forward(yalm_batch b, const int *tokens, const int *pos, float *logits_host);
+typedef struct yalm_batch_stats {
+	int launches_per_step; /* kernel launches of one step: 3 + n_layers * 5 with the one-launch attention,
+	                          3 + n_layers * (4 + n_seq) with YALM_BATCH_ATTN_PER_SEQ; the q / k norm adds
+	                          n_layers */
+} yalm_batch_stats;
+/* n_steps steps enqueued back to back with no host round trip (the state is device-resident, as in
+ * yalm_generate_greedy) and ONE read-back at the end. Sequence s starts by feeding tokens[s] at
+ * pos[s]; each step commits row s's first-maximum argmax (the rule of yalm_argmax) to sequence s,
+ * which continues at (that token, pos + 1). out_tokens: host [n_seq][n_steps]. stats may be NULL.
+ * A step is begin, per layer QKV / attention / Wo / W1|W3 / W2, norm + logits, commit.
+ * YALM_ERR_ARG: pos[s] + n_steps > max_seq_len for any s (a batched step never wraps the ring or
+ * rotates the sinks: the sliding window past max_seq_len stays with the single-sequence loops), a
+ * token out of range, n_steps above the token buffer (65536). */
+int yalm_batch_generate_greedy(yalm_batch b, const int *tokens, const int *pos, int n_steps, int *out_tokens,
+                               yalm_batch_stats *stats);
+/* The same with row s of step i drawn by the rule of yalm_generate_sampled with
+ * uniforms[s * n_steps + i] (host, [n_seq][n_steps] values in [0, 1]); one workgroup per row, in
+ * the commit launch's place. YALM_ERR_ARG: the greedy call's, and those of yalm_generate_sampled
+ * (temperature, top_k, top_p, a uniform outside [0, 1], a vocabulary above 131072). */
+int yalm_batch_generate_sampled(yalm_batch b, const int *tokens, const int *pos, int n_steps, const yalm_sampling *s,
+                                const float *uniforms, int *out_tokens, yalm_batch_stats *stats);
+/* Every sequence's next (token, pos) after a sync: host arrays of n_seq, either may be NULL. */
+int yalm_batch_state(yalm_batch b, int *tokens, int *pos);
+/* Launch switch of one batch (default 0). YALM_BATCH_ATTN_PER_SEQ: one attention launch per
+ * sequence (the decode kernel, as the verify step of yalm_generate_speculative runs it) where the
+ * single launch for all sequences would run. Both forms give the same bits (A/B runs and tests). */
+#define YALM_BATCH_ATTN_PER_SEQ 1
+int yalm_batch_set_launch(yalm_batch b, int flags);
+/* Test hook: the device pointers of sequence seq's K and V cache of `layer` and of its token buffer
+ * (each may be NULL). Every one of these buffers has YALM_BATCH_GUARD_BYTES bytes of 0xA5 directly
+ * before it and directly after its last byte, which nothing ever writes. */
+#define YALM_BATCH_GUARD_BYTES 256
+int yalm_batch_buffers(yalm_batch b, int seq, int layer, uint16_t **kcache, uint16_t **vcache, int **tokens);
+
 /* ---------------- test API: replaces infer.cu:890-1019 (model.h:370-384) ---------------- */
 /* Host pointers in and out; synchronous. dtype selects the weight type
  * (matmul_cuda<float|half|uint8_t>; YALM_Q4 / YALM_E4M3: w is d rows of yalm_row_bytes(dtype, n)). */

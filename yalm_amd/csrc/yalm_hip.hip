@@ -19,6 +19,7 @@
 
 #include "attention.h"
 #include "attn_wo.h"
+#include "batch.h"
 #include "decoder.h"
 #include "device_common.h"
 #include "gemv.h"
@@ -2245,6 +2246,371 @@ extern "C" int yalm_generate_speculative_sampled(yalm_decoder d, int token, int 
 	ARGCHK(s && (uniforms || n_tokens == 0), "yalm_generate_speculative_sampled: null argument");
 	return generate_speculative(d, "yalm_generate_speculative_sampled", token, pos, n_tokens, cfg, s, uniforms, context,
 	                            n_context, out_tokens, stats);
+}
+
+// ------------------------------------------------------------------ batched decode (batch.h)
+// Up to ROWS_MAX_T independent sequences per pass over the decoder's weights. The batch owns every
+// per-sequence buffer; it uses the decoder's stream, weights, frequency table, error word and (the
+// q / k norm form) raw QKV scratch, and nothing else of it: a decoder without a batch launches
+// what it launched before.
+#define BATCH_GUARD_BYTES YALM_BATCH_GUARD_BYTES
+struct yalm_batch_s {
+	yalm_decoder_s *d = nullptr;
+	int n_seq = 0, flags = 0;
+	StepState *seq = nullptr;              // [n_seq] sequence = row states
+	float *x = nullptr, *q = nullptr, *xb2 = nullptr, *hb = nullptr, *logits = nullptr; // [n_seq][...]
+	float *logits_pinned = nullptr;        // [n_seq][vocab] host
+	std::vector<BatchKV> kv;               // [n_layers]
+	BatchTok tok{};
+	BatchPart part{};
+	SampleParams *smp_params = nullptr;
+	float *smp_u = nullptr;                // [n_seq][tokens_cap]
+	std::vector<void *> allocs;
+};
+
+static void batch_free(yalm_batch_s *b) {
+	for (void *p : b->allocs)
+		(void)hipFree(p);
+	if (b->logits_pinned)
+		(void)hipHostFree(b->logits_pinned);
+	delete b;
+}
+
+// a zeroed device allocation owned by the batch, with BATCH_GUARD_BYTES of 0xA5 on either side
+// when guarded (the caches and token buffers: nothing may write there, the tests read them back)
+static int batch_alloc(yalm_batch_s *b, void **p, size_t bytes, bool guarded = false) {
+	const size_t g = guarded ? BATCH_GUARD_BYTES : 0, payload = (bytes + 255) & ~(size_t)255;
+	char *base = nullptr;
+	HIPCHK(hipMalloc((void **)&base, payload + 2 * g + 4));
+	b->allocs.push_back(base);
+	HIPCHK(hipMemset(base, 0, payload + 2 * g + 4));
+	if (g) {
+		HIPCHK(hipMemset(base, 0xA5, g));
+		HIPCHK(hipMemset(base + g + bytes, 0xA5, g));
+	}
+	*p = base + g;
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_create(yalm_decoder d, int n_seq, yalm_batch *out) {
+	ARGCHK(d && out, "yalm_batch_create: null argument");
+	TRY(rows_supported(d, "yalm_batch_create"));
+	ARGCHK(n_seq >= 1 && n_seq <= ROWS_MAX_T, "yalm_batch_create: 1 <= n_seq <= 4 sequences");
+	const yalm_config &c = d->c;
+	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
+	yalm_batch_s *b = new yalm_batch_s();
+	b->d = d;
+	b->n_seq = n_seq;
+	b->kv.resize(c.n_layers);
+	auto build = [&]() -> int {
+		const size_t N = (size_t)n_seq;
+		TRY(batch_alloc(b, (void **)&b->seq, sizeof(StepState) * N));
+		TRY(batch_alloc(b, (void **)&b->x, sizeof(float) * N * c.dim));
+		TRY(batch_alloc(b, (void **)&b->q, sizeof(float) * N * q_dim));
+		TRY(batch_alloc(b, (void **)&b->xb2, sizeof(float) * N * q_dim));
+		TRY(batch_alloc(b, (void **)&b->hb, sizeof(float) * N * c.hidden_dim));
+		TRY(batch_alloc(b, (void **)&b->logits, sizeof(float) * N * c.vocab_size));
+		TRY(batch_alloc(b, (void **)&b->smp_params, sizeof(SampleParams)));
+		TRY(batch_alloc(b, (void **)&b->smp_u, sizeof(float) * N * d->tokens_cap));
+		const size_t kvb = sizeof(uint16_t) * (size_t)c.max_seq_len * kv_dim;
+		const size_t pb = sizeof(unsigned long long) * (size_t)c.n_heads * attn_nsplit(c.max_seq_len) * (c.head_dim + 2);
+		for (int s = 0; s < ROWS_MAX_T; ++s) { // rows past n_seq alias sequence 0's buffers: never used, never null
+			if (s >= n_seq) {
+				for (int l = 0; l < c.n_layers; ++l)
+					b->kv[l].k[s] = b->kv[l].k[0], b->kv[l].v[s] = b->kv[l].v[0];
+				b->tok.p[s] = b->tok.p[0];
+				b->part.p[s] = b->part.p[0];
+				continue;
+			}
+			for (int l = 0; l < c.n_layers; ++l) {
+				TRY(batch_alloc(b, (void **)&b->kv[l].k[s], kvb, true));
+				TRY(batch_alloc(b, (void **)&b->kv[l].v[s], kvb, true));
+			}
+			TRY(batch_alloc(b, (void **)&b->tok.p[s], sizeof(int) * d->tokens_cap, true));
+			TRY(batch_alloc(b, (void **)&b->part.p[s], pb));
+		}
+		HIPCHK(hipHostMalloc((void **)&b->logits_pinned, sizeof(float) * N * c.vocab_size, hipHostMallocDefault));
+		if (qkv_form(d) == QKV_NORM && !d->qk_raw)
+			TRY(dalloc(d, (void **)&d->qk_raw, sizeof(float) * ROWS_MAX_T * (size_t)(q_dim + kv_dim)));
+		return YALM_OK;
+	};
+	const int r = build();
+	if (r != YALM_OK) {
+		batch_free(b);
+		return r;
+	}
+	*out = b;
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_destroy(yalm_batch b) {
+	if (!b)
+		return YALM_OK;
+	(void)hipStreamSynchronize(b->d->stream);
+	batch_free(b);
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_set_launch(yalm_batch b, int flags) {
+	ARGCHK(b, "yalm_batch_set_launch: null batch");
+	ARGCHK((flags & ~YALM_BATCH_ATTN_PER_SEQ) == 0, "yalm_batch_set_launch: unknown flag");
+	b->flags = flags;
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_buffers(yalm_batch b, int seq, int layer, uint16_t **kcache, uint16_t **vcache,
+                                  int **tokens) {
+	ARGCHK(b, "yalm_batch_buffers: null batch");
+	ARGCHK(seq >= 0 && seq < b->n_seq && layer >= 0 && layer < b->d->c.n_layers, "yalm_batch_buffers: bad seq or layer");
+	if (kcache)
+		*kcache = b->kv[layer].k[seq];
+	if (vcache)
+		*vcache = b->kv[layer].v[seq];
+	if (tokens)
+		*tokens = b->tok.p[seq];
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_load(yalm_batch b, int seq, int n_positions) {
+	ARGCHK(b, "yalm_batch_load: null batch");
+	const yalm_decoder_s *d = b->d;
+	ARGCHK(seq >= -1 && seq < b->n_seq, "yalm_batch_load: seq must be -1 (every sequence) or 0 .. n_seq - 1");
+	ARGCHK(n_positions >= 0 && n_positions <= d->c.max_seq_len, "yalm_batch_load: n_positions outside [0, max_seq_len]");
+	const size_t bytes = sizeof(uint16_t) * (size_t)n_positions * d->c.n_kv_heads * d->c.head_dim;
+	if (bytes == 0)
+		return YALM_OK;
+	for (int s = seq < 0 ? 0 : seq; s < (seq < 0 ? b->n_seq : seq + 1); ++s)
+		for (int l = 0; l < d->c.n_layers; ++l) {
+			HIPCHK(hipMemcpyAsync(b->kv[l].k[s], d->b[l].key_cache, bytes, hipMemcpyDeviceToDevice, d->stream));
+			HIPCHK(hipMemcpyAsync(b->kv[l].v[s], d->b[l].value_cache, bytes, hipMemcpyDeviceToDevice, d->stream));
+		}
+	return YALM_OK;
+}
+
+// The attention of every sequence as one launch: launch_attn_D's choices of S, hmax and nsplit.
+template <int D>
+static void launch_attn_batch_D(const yalm_batch_s *b, int l) {
+	const yalm_decoder_s *d = b->d;
+	const yalm_config &c = d->c;
+	const int G = c.n_heads / c.n_kv_heads, q_dim = c.n_heads * c.head_dim;
+	static const int splits = ab_env("YALM_ATTN_SPLITS") ? std::max(1, std::min(ATTN_MAX_SPLITS, atoi(ab_env("YALM_ATTN_SPLITS")))) : ATTN_SPLITS;
+	const int nchunks = (c.max_seq_len + attn_chunk<D>() - 1) / attn_chunk<D>();
+	const int S = std::min(nchunks, splits);
+	const int per_seq = c.n_kv_heads * (S + G - 1) + c.n_heads;
+	const int hmax = attn_head_max(S, nchunks);
+#define YALM_ATTN_B(GT)                                                                                                \
+	attn_decode_batch_kernel<D, GT><<<per_seq * b->n_seq, ATTN_THREADS, 0, d->stream>>>(                              \
+	    b->q, q_dim, b->kv[l], b->seq, per_seq, c.n_heads, c.n_kv_heads, c.max_seq_len, attn_nsplit(c.max_seq_len), S, \
+	    hmax, b->part, l, c.n_layers, d->awo_err, b->xb2)
+	if (G <= 1)
+		YALM_ATTN_B(1);
+	else if (G <= 2)
+		YALM_ATTN_B(2);
+	else if (G <= 4)
+		YALM_ATTN_B(4);
+	else
+		YALM_ATTN_B(8);
+#undef YALM_ATTN_B
+}
+
+static int enqueue_batch_attn(const yalm_batch_s *b, int l) {
+	const yalm_decoder_s *d = b->d;
+	const yalm_config &c = d->c;
+	const int q_dim = c.n_heads * c.head_dim;
+	if (b->flags & YALM_BATCH_ATTN_PER_SEQ) {
+		for (int s = 0; s < b->n_seq; ++s)
+			TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, b->q + (size_t)s * q_dim, b->kv[l].k[s], b->kv[l].v[s],
+			                b->seq + s, c.max_seq_len, b->part.p[s], l, c.n_layers, d->awo_err, nullptr,
+			                b->xb2 + (size_t)s * q_dim, d->stream));
+		return YALM_OK;
+	}
+	switch (c.head_dim) {
+	case 16: launch_attn_batch_D<16>(b, l); break;
+	case 32: launch_attn_batch_D<32>(b, l); break;
+	case 64: launch_attn_batch_D<64>(b, l); break;
+	case 128: launch_attn_batch_D<128>(b, l); break;
+	case 256: launch_attn_batch_D<256>(b, l); break;
+	default:
+		set_err("unsupported head_dim");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+// One batch step up to the logits: begin, then per layer QKV (+ the q / k norm launch), attention
+// (one launch, or one per sequence), Wo, W1|W3, W2; then norm + logits into logits [n_seq][vocab].
+template <class WT>
+static int enqueue_batch_forward_t(yalm_batch_s *b) {
+	yalm_decoder_s *d = b->d;
+	if constexpr (WT::Q4) {
+		return rows_supported(d, "batched forward");
+	} else {
+		const yalm_config &c = d->c;
+		hipStream_t st = d->stream;
+		const int T = b->n_seq, q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
+		batch_begin_kernel<WT><<<T, 256, 0, st>>>(b->seq, d->emb, c.dim, b->x, d->inv_freq, c.head_dim / 2);
+		HIPCHK(hipGetLastError());
+		for (int l = 0; l < c.n_layers; ++l) {
+			const yalm_block_weights &w = d->b[l];
+			switch (qkv_form(d)) {
+			case QKV_NORM: { // raw rows, then one norm launch for all rows, each K row into its sequence's cache
+				PQKVN<WT> base = make_pqkvn<WT>(d, l);
+				base.step = b->seq;
+				TRY((launch_rows<WT, BQKVN<WT>, true>({base, base.n, base.n_groups, q_dim + kv_dim, b->kv[l]}, b->x, c.dim,
+				                                      w.rms_att, c.norm_eps, T, st)));
+				batch_qk_norm_rope_kernel<<<dim3(c.n_heads + c.n_kv_heads, T), YALM_WAVE, 0, st>>>(
+				    d->qk_raw, q_dim + kv_dim, d->gq[l], d->gk[l], c.n_heads, c.n_kv_heads, c.head_dim, c.norm_eps, b->seq,
+				    b->q, q_dim, b->kv[l]);
+				HIPCHK(hipGetLastError());
+				break;
+			}
+			case QKV_BIAS: {
+				PQKVB<WT> base = make_pqkvb<WT>(d, l);
+				base.step = b->seq;
+				base.q_out = b->q;
+				TRY((launch_rows<WT, BQKVB<WT>, true>({base, base.n, base.n_groups, q_dim, b->kv[l]}, b->x, c.dim, w.rms_att,
+				                                      c.norm_eps, T, st)));
+				break;
+			}
+			default: {
+				PQKV<WT> base = make_pqkv<WT>(d, l);
+				base.step = b->seq;
+				base.q_out = b->q;
+				TRY((launch_rows<WT, BQKV<WT>, true>({base, base.n, base.n_groups, q_dim, b->kv[l]}, b->x, c.dim, w.rms_att,
+				                                     c.norm_eps, T, st)));
+			}
+			}
+			TRY(enqueue_batch_attn(b, l));
+			TRY((launch_rows<WT, RResidual<WT>, false>(make_rresidual<WT>(w.wo, q_dim, c.dim, b->x, c.dim), b->xb2, q_dim,
+			                                           nullptr, 0.f, T, st)));
+			TRY((launch_rows_glu<WT, true>(w.w1, w.w3, c.dim, c.hidden_dim, b->hb, c.hidden_dim, c.act, b->x, c.dim, w.rms_ffn,
+			                               c.norm_eps, T, st)));
+			TRY((launch_rows<WT, RResidual<WT>, false>(make_rresidual<WT>(w.w2, c.hidden_dim, c.dim, b->x, c.dim), b->hb,
+			                                           c.hidden_dim, nullptr, 0.f, T, st)));
+		}
+		return launch_rows<WT, RStore<WT>, true>(make_rstore<WT>(d->wcls, c.dim, c.vocab_size, b->logits, c.vocab_size), b->x,
+		                                         c.dim, d->rms_final, c.norm_eps, T, st);
+	}
+}
+
+static int enqueue_batch_forward(yalm_batch_s *b) {
+	return DISPATCH_WT(b->d->c.weight_dtype, enqueue_batch_forward_t, b);
+}
+
+static int batch_launches(const yalm_batch_s *b) {
+	const int L = b->d->c.n_layers, attn = (b->flags & YALM_BATCH_ATTN_PER_SEQ) ? b->n_seq : 1;
+	return 3 + L * (4 + attn + (b->d->gq.empty() ? 0 : 1));
+}
+
+static int batch_set(yalm_batch_s *b, const int *tokens, const int *pos, int reset_gen) {
+	int tk[ROWS_MAX_T] = {0, 0, 0, 0}, ps[ROWS_MAX_T] = {0, 0, 0, 0};
+	for (int s = 0; s < b->n_seq; ++s)
+		tk[s] = tokens[s], ps[s] = pos[s];
+	batch_set_kernel<<<1, 1, 0, b->d->stream>>>(b->seq, b->n_seq, tk[0], tk[1], tk[2], tk[3], ps[0], ps[1], ps[2], ps[3],
+	                                            reset_gen);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_forward(yalm_batch b, const int *tokens, const int *pos, float *logits_host) {
+	ARGCHK(b && tokens && pos, "yalm_batch_forward: null argument");
+	yalm_decoder_s *d = b->d;
+	for (int s = 0; s < b->n_seq; ++s) {
+		ARGCHK(tokens[s] >= 0 && tokens[s] < d->vocab_full, "yalm_batch_forward: token out of range");
+		ARGCHK(pos[s] >= 0 && pos[s] < d->c.max_seq_len,
+		       "yalm_batch_forward: pos must be in [0, max_seq_len) (a batched step never wraps the ring or rotates the sinks)");
+	}
+	TRY(batch_set(b, tokens, pos, 0));
+	TRY(enqueue_batch_forward(b));
+	if (logits_host) {
+		const size_t bytes = sizeof(float) * (size_t)b->n_seq * d->c.vocab_size;
+		HIPCHK(hipMemcpyAsync(b->logits_pinned, b->logits, bytes, hipMemcpyDeviceToHost, d->stream));
+		HIPCHK(hipStreamSynchronize(d->stream));
+		TRY(awo_check(d));
+		memcpy(logits_host, b->logits_pinned, bytes);
+	}
+	return YALM_OK;
+}
+
+// The batched loop, greedy (smp == nullptr) or sampled: n_steps steps back to back, one read-back.
+static int batch_generate(yalm_batch_s *b, const char *name, const int *tokens, const int *pos, int n_steps,
+                          const yalm_sampling *smp, const float *uniforms, int *out_tokens, yalm_batch_stats *stats) {
+	const std::string who(name);
+	ARGCHK(b && tokens && pos && (out_tokens || n_steps == 0), who + ": null argument");
+	yalm_decoder_s *d = b->d;
+	ARGCHK(n_steps >= 0, who + ": bad n_steps");
+	ARGCHK(n_steps <= d->tokens_cap, who + ": n_steps exceeds the token buffer (65536)");
+	for (int s = 0; s < b->n_seq; ++s) {
+		ARGCHK(tokens[s] >= 0 && tokens[s] < d->vocab_full, who + ": token out of range");
+		ARGCHK(pos[s] >= 0 && (long long)pos[s] + n_steps <= d->c.max_seq_len,
+		       who + ": pos + n_steps must not exceed max_seq_len (a batched step never wraps the ring or rotates the sinks)");
+	}
+	if (smp) {
+		TRY(validate_sampling(smp, uniforms, b->n_seq * n_steps));
+		ARGCHK(d->c.vocab_size <= SMP_MAX_N, who + ": vocabulary above 131072");
+	}
+	if (stats)
+		stats->launches_per_step = batch_launches(b);
+	if (n_steps == 0)
+		return YALM_OK;
+	hipStream_t st = d->stream;
+	const int V = d->c.vocab_size, T = b->n_seq;
+	if (smp) {
+		HIPCHK(hipMemcpyAsync(b->smp_params, smp, sizeof(SampleParams), hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(b->smp_u, uniforms, sizeof(float) * (size_t)T * n_steps, hipMemcpyHostToDevice, st));
+	}
+	TRY(batch_set(b, tokens, pos, 1));
+	for (int i = 0; i < n_steps; ++i) {
+		TRY(enqueue_batch_forward(b));
+		if (smp) {
+			if (V % 4 == 0)
+				batch_sample_kernel<true><<<T, SMP_THREADS, 0, st>>>(b->logits, V, b->smp_params, b->smp_u, n_steps, b->seq,
+				                                                    b->tok, d->tokens_cap);
+			else
+				batch_sample_kernel<false><<<T, SMP_THREADS, 0, st>>>(b->logits, V, b->smp_params, b->smp_u, n_steps, b->seq,
+				                                                     b->tok, d->tokens_cap);
+		} else if (V % 4 == 0) {
+			batch_commit_kernel<true><<<T, 1024, 0, st>>>(b->logits, V, b->seq, b->tok, d->tokens_cap);
+		} else {
+			batch_commit_kernel<false><<<T, 1024, 0, st>>>(b->logits, V, b->seq, b->tok, d->tokens_cap);
+		}
+		HIPCHK(hipGetLastError());
+	}
+	for (int s = 0; s < T; ++s)
+		HIPCHK(hipMemcpyAsync(out_tokens + (size_t)s * n_steps, b->tok.p[s], sizeof(int) * n_steps, hipMemcpyDeviceToHost,
+		                      st));
+	HIPCHK(hipStreamSynchronize(st));
+	return awo_check(d);
+}
+
+extern "C" int yalm_batch_generate_greedy(yalm_batch b, const int *tokens, const int *pos, int n_steps, int *out_tokens,
+                                          yalm_batch_stats *stats) {
+	return batch_generate(b, "yalm_batch_generate_greedy", tokens, pos, n_steps, nullptr, nullptr, out_tokens, stats);
+}
+
+extern "C" int yalm_batch_generate_sampled(yalm_batch b, const int *tokens, const int *pos, int n_steps,
+                                           const yalm_sampling *s, const float *uniforms, int *out_tokens,
+                                           yalm_batch_stats *stats) {
+	ARGCHK(s && (uniforms || n_steps == 0), "yalm_batch_generate_sampled: null argument");
+	static const float none = 0.0f;
+	return batch_generate(b, "yalm_batch_generate_sampled", tokens, pos, n_steps, s, uniforms ? uniforms : &none,
+	                      out_tokens, stats);
+}
+
+extern "C" int yalm_batch_state(yalm_batch b, int *tokens, int *pos) {
+	ARGCHK(b, "yalm_batch_state: null batch");
+	HIPCHK(hipStreamSynchronize(b->d->stream));
+	TRY(awo_check(b->d));
+	std::vector<StepState> s(b->n_seq);
+	HIPCHK(hipMemcpy(s.data(), b->seq, sizeof(StepState) * b->n_seq, hipMemcpyDeviceToHost));
+	for (int i = 0; i < b->n_seq; ++i) {
+		if (tokens)
+			tokens[i] = s[i].token;
+		if (pos)
+			pos[i] = s[i].pos;
+	}
+	return YALM_OK;
 }
 
 extern "C" int yalm_device_step(yalm_decoder d, int *token, int *pos) {

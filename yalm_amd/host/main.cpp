@@ -48,6 +48,9 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -s <int>   speculative decode with this many rows per step, 2..4 (0 - off, the default);\n"
 	                "             needs -t 0 (greedy), or -t > 0 with -k or -p (sampled on the device: the\n"
 	                "             same tokens as without -s)\n");
+	fprintf(stderr, "  -N <int>   completions of one prompt decoded together, 2..4 (0 - off, the default): one pass\n"
+	                "             over the weights per step for all of them; needs -t > 0 with -k or -p (greedy\n"
+	                "             completions would be identical); not with -s\n");
 	fprintf(stderr, "  Choose one:\n    -i <string> input prompt\n    -f <filepath> input file with prompt\n");
 	fprintf(stderr, "Passkey mode options:\n  -n <int>    number of junk lines to insert (default - 250)\n");
 	fprintf(stderr, "  -l <int>    passkey position (-1 - random)\n");
@@ -91,7 +94,7 @@ static std::vector<int> encode_prompt(const Tokenizer &tok, const std::string &p
 
 static void run_completion(const std::string &path, const std::string &device, const std::string &prompt,
                            int context, int num_steps, float temperature, bool device_sampling, int top_k,
-                           float top_p, int spec_rows) {
+                           float top_p, int spec_rows, int n_completions) {
 	YALMData data;
 	if (data.from_file(path) != 0) {
 		fprintf(stderr, "error: cannot load %s\n", path.c_str());
@@ -135,8 +138,8 @@ static void run_completion(const std::string &path, const std::string &device, c
 		std::srand((unsigned)sampler_seed());
 	for (size_t pos = first; pos < encoding.size(); ++pos) {
 		const bool last = pos + 1 == encoding.size();
-		if (last && spec_rows > 0)
-			break; // the speculative loop below feeds the last prompt token itself
+		if (last && (spec_rows > 0 || n_completions > 0))
+			break; // the speculative / batched loop below feeds the last prompt token itself
 		if (last && greedy)
 			next = model.forward_greedy(state, encoding[pos], (int)pos);
 		else if (last && sampled)
@@ -172,6 +175,60 @@ static void run_completion(const std::string &path, const std::string &device, c
 			encoding.push_back(out[j]);
 			stop = out[j] == tokenizer.eos_id || out[j] == tokenizer.eot_id;
 		}
+	}
+	// -N: the prompt's KV rows, hydrated once above, are loaded into every sequence of a batch; the
+	// sequences then decode together in chunks of BATCH_CHUNK steps (one call each). The seeded
+	// host RNG hands out the uniforms chunk by chunk, inside a chunk sequence by sequence
+	// (sequence 0's BATCH_CHUNK draws, then sequence 1's, ...), a finished sequence included: its
+	// row keeps running and its tokens are dropped, so the others' draws do not depend on it.
+	// A batched step never leaves the window: the completions end at max_seq_len.
+	if (n_completions > 0) {
+		constexpr int BATCH_CHUNK = 16;
+		const int N = n_completions, pos0 = (int)encoding.size() - 1;
+		const int room = model.config->max_seq_len - pos0;
+		const int total = num_steps == -1 ? room : std::min(num_steps, room);
+		std::vector<std::vector<int>> seqs(N);
+		std::vector<int> tok(N, encoding.back()), pos(N, pos0), stopped(N, 0);
+		for (int done = 0; done < total && std::count(stopped.begin(), stopped.end(), 0) > 0;) {
+			const int chunk = std::min(BATCH_CHUNK, total - done);
+			std::vector<float> u((size_t)N * chunk);
+			std::vector<int> out((size_t)N * chunk);
+			for (int q = 0; q < N; ++q)
+				for (int j = 0; j < chunk; ++j)
+					u[(size_t)q * chunk + j] = uniform();
+			model.generate_batch_sampled(state, N, done == 0 ? pos0 : -1, tok.data(), pos.data(), chunk, temperature, top_k,
+			                             top_p, u.data(), out.data());
+			for (int q = 0; q < N; ++q) {
+				for (int j = 0; j < chunk && !stopped[q]; ++j) {
+					const int t = out[(size_t)q * chunk + j];
+					seqs[q].push_back(t);
+					stopped[q] = t == tokenizer.eos_id || t == tokenizer.eot_id;
+				}
+				tok[q] = out[(size_t)q * chunk + chunk - 1];
+				pos[q] += chunk;
+			}
+			done += chunk;
+		}
+		size_t produced = 0;
+		for (int q = 0; q < N; ++q) {
+			printf("--- completion %d of %d ---\n", q + 1, N);
+			int prev = encoding.back();
+			std::string line;
+			for (int t : seqs[q]) {
+				std::cout << tokenizer.decode_one(prev, t);
+				line += std::to_string(t) + " ";
+				prev = t;
+			}
+			std::cout << "\n" << std::endl;
+			if (print_token_ids())
+				fprintf(stderr, "TOKENS[%d]: %s\n", q, line.c_str());
+			produced += seqs[q].size();
+		}
+		const double el = (now_ms() - start) / 1000.0;
+		printf("Generation stats:\n  %zu prompt + %zu generated tokens in %d completions\n  throughput: %.5gtok/s\n"
+		       "  hydrate: %.5gs\n  total: %.5gs\n\n",
+		       encoding.size(), produced, N, (encoding.size() + produced) / el, (end_hydrate - start) / 1000.0, el);
+		return;
 	}
 	for (int i = 0; spec_rows == 0 && (i < num_steps || num_steps == -1); ++i) {
 		const int token = greedy || sampled ? next : sampler.sample(state, temperature);
@@ -341,7 +398,7 @@ static void run_passkey(const std::string &path, const std::string &device, int 
 
 int main(int argc, char *argv[]) {
 	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path;
-	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0, spec_rows = 0;
+	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0, spec_rows = 0, n_completions = 0;
 	float temperature = 1.0f, top_p = 1.0f;
 	bool device_sampling = false;
 	if (argc < 2)
@@ -382,6 +439,7 @@ int main(int argc, char *argv[]) {
 			device_sampling = true;
 			break;
 		case 's': spec_rows = std::stoi(v); break;
+		case 'N': n_completions = std::stoi(v); break;
 		case 'f': prompt_path = v; break;
 		case 'T': context = std::stoi(v); break;
 		case 'l': passkey_pos = std::stoi(v); break;
@@ -396,6 +454,11 @@ int main(int argc, char *argv[]) {
 	// host sampler (-t > 0 alone) reads the logits of one row and has no speculative form
 	if (spec_rows != 0 && (spec_rows < 2 || spec_rows > 4 || (temperature != 0.0f && !device_sampling) ||
 	                       temperature < 0.0f || mode != "completion"))
+		error_usage();
+	// -N: completion mode, sampled on the device (-t > 0 with -k or -p): greedy completions of one
+	// prompt would be identical, and the host sampler reads one row's logits
+	if (n_completions != 0 && (n_completions < 2 || n_completions > 4 || !(temperature > 0.0f) || !device_sampling ||
+	                           spec_rows != 0 || mode != "completion"))
 		error_usage();
 	const int has_prompt = prompt.size() > 0, has_path = prompt_path.size() > 0;
 	if (mode == "completion" || mode == "perplexity") {
@@ -419,7 +482,7 @@ int main(int argc, char *argv[]) {
 	try {
 		if (mode == "completion")
 			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p,
-			               spec_rows);
+			               spec_rows, n_completions);
 		else if (mode == "passkey")
 			run_passkey(checkpoint, device, context, n_junk, passkey_pos);
 		else

@@ -172,6 +172,8 @@ InferenceState::InferenceState(std::shared_ptr<Config> config) : _config(std::mo
 }
 
 InferenceState::~InferenceState() {
+	if (_batch) // before the decoder it runs on
+		yalm_batch_destroy(_batch);
 	if (_decoder)
 		yalm_decoder_destroy(_decoder);
 	if (_device == Device::HIP)
@@ -429,6 +431,23 @@ void Model::generate_speculative_sampled(InferenceState &s, int token, int pos, 
 		*accepted += st.accepted_drafts;
 	if (plain)
 		*plain += st.plain_steps;
+}
+
+void Model::generate_batch_sampled(InferenceState &s, int n_seq, int load, const int *tokens, const int *pos, int n,
+                                   float temperature, int top_k, float top_p, const float *uniforms, int *out) {
+	ensure_decoder(s);
+	if (s._batch && s._batch_n != n_seq) {
+		check(yalm_batch_destroy(s._batch), "batch destroy");
+		s._batch = nullptr;
+	}
+	if (!s._batch) {
+		check(yalm_batch_create(s._decoder, n_seq, &s._batch), "batch create");
+		s._batch_n = n_seq;
+	}
+	if (load >= 0)
+		check(yalm_batch_load(s._batch, -1, load), "batch load");
+	const yalm_sampling sp{temperature, top_k, top_p};
+	check(yalm_batch_generate_sampled(s._batch, tokens, pos, n, &sp, uniforms, out, nullptr), "batched sampled steps");
 }
 
 int Model::forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u) {

@@ -92,6 +92,8 @@ private:
 	InferenceMode _mode = InferenceMode::OUTPUT_LOGITS;
 	float *_logits = nullptr;
 	yalm_decoder _decoder = nullptr;
+	yalm_batch _batch = nullptr; // batched decode (Model::generate_batch_sampled), created on first use
+	int _batch_n = 0;
 };
 
 struct Block {
@@ -154,6 +156,13 @@ struct Model {
 	void generate_speculative_sampled(InferenceState &s, int token, int pos, int n, int rows, float temperature,
 	                                  int top_k, float top_p, const float *uniforms, const int *context, int n_context,
 	                                  int *out, int *steps, int *accepted, int *plain);
+	// n_seq completions side by side (yalm_batch_generate_sampled: one pass over the weights per
+	// step for all of them). load >= 0: first copy KV rows [0, load) of the state's own cache into
+	// every sequence (the prompt, hydrated once by forward / prefill). Sequence q feeds tokens[q] at
+	// pos[q] and draws step i with uniforms[q * n + i]; out is [n_seq][n]. A later call with load
+	// < 0 continues the same sequences. Dense models on one GPU, not q4 (yalm_batch_create).
+	void generate_batch_sampled(InferenceState &s, int n_seq, int load, const int *tokens, const int *pos, int n,
+	                            float temperature, int top_k, float top_p, const float *uniforms, int *out);
 	// Batched MFMA prefill of tokens[0..n) at positions pos0.. (yalm_prefill):
 	// fills the KV cache; logprobs (may be null) gets log p(tokens[i+1]) per
 	// position; split: the split-operand precision form (yalm_set_prefill_precision).

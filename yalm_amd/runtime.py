@@ -82,6 +82,12 @@ class SpecStats(ctypes.Structure):
                 ("launches_per_step", c_int)]
 
 
+class BatchStats(ctypes.Structure):
+    """yalm_batch_stats."""
+
+    _fields_ = [("launches_per_step", c_int)]
+
+
 class GemvGeometry(ctypes.Structure):
     """yalm_gemv_geometry: the plan of one single-row GEMV launch."""
 
@@ -216,6 +222,16 @@ _sig("yalm_rows_plan", c_int, [c_int] * 5 + [ctypes.POINTER(c_int)] * 4 + [ctype
 _sig("yalm_matmul_rows", c_int, [c_void_p] * 5 + [c_float] + [c_int] * 8)
 _sig("yalm_gemv_plan", c_int, [c_int] * 11 + [ctypes.POINTER(GemvGeometry)])
 _sig("yalm_gemv_one", c_int, [ctypes.POINTER(GemvArgs)])
+_sig("yalm_batch_create", c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)])
+_sig("yalm_batch_destroy", c_int, [c_void_p])
+_sig("yalm_batch_load", c_int, [c_void_p, c_int, c_int])
+_sig("yalm_batch_forward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p])
+_sig("yalm_batch_generate_greedy", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(BatchStats)])
+_sig("yalm_batch_generate_sampled", c_int, [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(Sampling), c_void_p,
+                                             c_void_p, ctypes.POINTER(BatchStats)])
+_sig("yalm_batch_state", c_int, [c_void_p, c_void_p, c_void_p])
+_sig("yalm_batch_set_launch", c_int, [c_void_p, c_int])
+_sig("yalm_batch_buffers", c_int, [c_void_p, c_int, c_int] + [ctypes.POINTER(c_void_p)] * 3)
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -239,7 +255,13 @@ EXPORTED = [
     "yalm_rows_plan", "yalm_matmul_rows",
     "yalm_gemv_plan", "yalm_gemv_one",
     "yalm_attn_prefill_rows",
+    "yalm_batch_create", "yalm_batch_destroy", "yalm_batch_load", "yalm_batch_forward",
+    "yalm_batch_generate_greedy", "yalm_batch_generate_sampled", "yalm_batch_state", "yalm_batch_set_launch",
+    "yalm_batch_buffers",
 ]
+BATCH_ATTN_PER_SEQ = 1  # yalm_batch_set_launch
+BATCH_GUARD_BYTES = 256  # YALM_BATCH_GUARD_BYTES
+BATCH_MAX_SEQ = 4
 PREFILL_FAST, PREFILL_SPLIT = 0, 1  # yalm_set_prefill_precision
 
 HYDRATE_KV_CACHE, OUTPUT_LOGITS = 0, 1
@@ -1051,6 +1073,106 @@ class Decoder:
         if getattr(self, "stream", None) is not None:
             self.stream.close()
             self.stream = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Batch:
+    """Up to four independent sequences decoded together on one Decoder (yalm_batch_*): every
+    weight matrix is streamed once per step for all of them. Prompts arrive through the decoder:
+    hydrate it (Decoder.prefill / forward), then load(). The decoder must outlive the batch."""
+
+    def __init__(self, decoder: Decoder, n_seq: int, launch: int = 0):
+        self.decoder = decoder
+        self.cfg = decoder.cfg
+        self.n_seq = n_seq
+        self.h = None
+        h = c_void_p()
+        check(lib.yalm_batch_create(decoder.h, n_seq, ctypes.byref(h)))
+        self.h = h
+        self.launch = 0
+        if launch:
+            self.set_launch(launch)
+
+    def _rows(self, values, name: str) -> np.ndarray:
+        a = np.ascontiguousarray(values, dtype=np.int32).reshape(-1)
+        if a.size != self.n_seq:
+            raise ValueError(f"Batch: {name} needs one entry per sequence ({self.n_seq}), got {a.size}")
+        return a
+
+    def set_launch(self, flags: int) -> None:
+        """yalm_batch_set_launch: BATCH_ATTN_PER_SEQ or 0."""
+        check(lib.yalm_batch_set_launch(self.h, flags))
+        self.launch = flags
+
+    def load(self, n_positions: int, seq: int = -1) -> None:
+        """KV rows [0, n_positions) of the decoder's caches into sequence seq (-1: all)."""
+        check(lib.yalm_batch_load(self.h, seq, n_positions))
+
+    def forward(self, tokens, pos, logits: bool = True):
+        """One step without a commit: row s feeds tokens[s] at pos[s]; logits (n_seq, vocab) or None."""
+        t, p = self._rows(tokens, "tokens"), self._rows(pos, "pos")
+        out = np.empty((self.n_seq, self.cfg.vocab_size), np.float32) if logits else None
+        check(lib.yalm_batch_forward(self.h, _ptr(t), _ptr(p), _ptr(out) if logits else None))
+        return out
+
+    def generate_greedy(self, tokens, pos, n: int):
+        """n greedy steps of every sequence: (tokens (n_seq, n) int32, stats dict)."""
+        t, p = self._rows(tokens, "tokens"), self._rows(pos, "pos")
+        out = np.zeros((self.n_seq, max(n, 1)), np.int32)
+        st = BatchStats()
+        check(lib.yalm_batch_generate_greedy(self.h, _ptr(t), _ptr(p), n, _ptr(out) if n > 0 else None,
+                                             ctypes.byref(st)))
+        res = np.ascontiguousarray(out[:, :n]) if n > 0 else np.zeros((self.n_seq, 0), np.int32)
+        return res, {"launches_per_step": st.launches_per_step}
+
+    def generate_sampled(self, tokens, pos, n: int, temperature: float, top_k: int = 0, top_p: float = 1.0,
+                         uniforms=None, seed: int = 0):
+        """n sampled steps of every sequence, row s of step i drawn with uniforms[s][i]
+        (uniforms None: numpy.random.default_rng(seed).random((n_seq, n), float32))."""
+        t, p = self._rows(tokens, "tokens"), self._rows(pos, "pos")
+        if uniforms is None:
+            uniforms = np.random.default_rng(seed).random((self.n_seq, n), dtype=np.float32)
+        u = np.ascontiguousarray(uniforms, dtype=np.float32)
+        if u.shape != (self.n_seq, n):
+            raise ValueError(f"Batch.generate_sampled: uniforms must be ({self.n_seq}, {n}), got {u.shape}")
+        if u.size == 0:
+            u = np.zeros(1, np.float32)
+        s = Sampling(temperature, top_k, top_p)
+        out = np.zeros((self.n_seq, max(n, 1)), np.int32)
+        st = BatchStats()
+        check(lib.yalm_batch_generate_sampled(self.h, _ptr(t), _ptr(p), n, ctypes.byref(s), _ptr(u),
+                                              _ptr(out) if n > 0 else None, ctypes.byref(st)))
+        res = np.ascontiguousarray(out[:, :n]) if n > 0 else np.zeros((self.n_seq, 0), np.int32)
+        return res, {"launches_per_step": st.launches_per_step}
+
+    def state(self):
+        """(tokens, pos): every sequence's next token and position (lists)."""
+        t, p = np.zeros(self.n_seq, np.int32), np.zeros(self.n_seq, np.int32)
+        check(lib.yalm_batch_state(self.h, _ptr(t), _ptr(p)))
+        return t.tolist(), p.tolist()
+
+    def stats(self) -> dict:
+        """The launch count of one step in the current attention form."""
+        z = np.zeros(self.n_seq, np.int32)
+        st = BatchStats()
+        check(lib.yalm_batch_generate_greedy(self.h, _ptr(z), _ptr(z), 0, None, ctypes.byref(st)))
+        return {"launches_per_step": st.launches_per_step}
+
+    def buffers(self, seq: int, layer: int = 0):
+        """Test hook (yalm_batch_buffers): device pointers (kcache, vcache, tokens) of sequence seq."""
+        k, v, t = c_void_p(), c_void_p(), c_void_p()
+        check(lib.yalm_batch_buffers(self.h, seq, layer, ctypes.byref(k), ctypes.byref(v), ctypes.byref(t)))
+        return k.value, v.value, t.value
+
+    def close(self):
+        if self.h:
+            check(lib.yalm_batch_destroy(self.h))
+            self.h = None
 
     def __del__(self):
         try:
