@@ -576,6 +576,57 @@ int yalm_generate_speculative(yalm_decoder d, int token, int pos, int n_tokens, 
 int yalm_generate_speculative_sampled(yalm_decoder d, int token, int pos, int n_tokens, const yalm_spec *cfg,
                                       const yalm_sampling *s, const float *uniforms, const int *context,
                                       int n_context, int *out_tokens, yalm_spec_stats *stats);
+/* Speculative decode with a draft model: a second, smaller decoder `draft` on the SAME stream
+ * proposes a token at every row of every step (csrc/spec.h). s == NULL is the greedy call (every
+ * row's argmax, as yalm_generate_speculative); otherwise the sampled one (every row drawn with
+ * uniforms[p + t] by output index, as yalm_generate_speculative_sampled, with its argument checks).
+ * A step, all on the one stream with no host synchronisation:
+ *   1. sync (1 launch): draft's device step = the target's current (token, pos), nothing produced.
+ *      A token the draft does not have (>= its vocab_size) is fed as token 0 and the step's drafts
+ *      are none: the draft's embedding is never read out of range.
+ *   2. rows - 1 greedy forwards of `draft` from its device state (the path of yalm_enqueue_greedy):
+ *      they yield d_1 .. d_(rows-1) and write its KV rows pos .. pos + rows - 2. Then one KV-only
+ *      forward (the YALM_HYDRATE_KV_CACHE form at the state they left) feeds d_(rows-1) at
+ *      pos + rows - 1.
+ *   3. gather (1 launch): rows k = 1..rows-1 of the target's step get d_k; a d_k the target does
+ *      not have (>= its vocab_size) is none. With draft_stream set the drafts are
+ *      draft_stream[p + k - 1] instead, as in yalm_spec (the draft's forwards still run: a
+ *      benchmark pays a draft model's true cost at a chosen acceptance).
+ *   4. the rows forward and verify (or draw + accept) of the n-gram calls, unchanged.
+ * The delivered tokens do not depend on the draft: a row of the multi-row GEMV depends on
+ * neither the row count nor the other rows, so the call returns exactly the tokens of
+ * yalm_generate_speculative / _sampled at the same rows (hence of the plain loops, with their
+ * caveats). A stale, wrong or unhydrated draft cache only costs acceptance. After a step that
+ * accepts a tokens the draft's KV rows pos .. pos + a - 1 hold the delivered tokens (accepted
+ * drafts equal them); later rows are overwritten by later steps, as in the target. For drafts
+ * worth accepting the caller hydrates positions [0, pos) on BOTH decoders (yalm_prefill or
+ * yalm_forward on each).
+ * Toward the target the contract of yalm_generate_speculative: batches of up to 64 steps with
+ * one count read-back each, the overshoot dropped, and from the first p with p + rows >
+ * max_seq_len the plain steps of the target alone (plain_steps; the draft does not run).
+ * Afterwards the draft's device (token, pos) and token buffer are unspecified; its KV rows
+ * [0, pos + n_tokens) are valid unless plain steps ran.
+ * launches_per_step = (s ? 5 : 4) + n_layers * (4 + rows) [+ n_layers with the q / k norm]
+ *                     + 1 + (rows - 1) * G + H,
+ * the n-gram step with sync + gather in the drafter launch's place, G and H the kernel counts
+ * of the draft's yalm_graph_kernels modes 2 (greedy) and 0 (KV-only).
+ * Target: what yalm_forward_rows accepts. Draft: any dense one-GPU decoder, any weight format
+ * (q4 included), with its own bias, q / k norm or RoPE scaling; the vocabulary sizes may differ.
+ * YALM_ERR_UNSUPPORTED: a target the multi-row path refuses; a tensor-parallel or
+ * mixture-of-experts draft. YALM_ERR_ARG: draft == d; decoders on different streams (create the
+ * draft on yalm_decoder_get_stream(d)); the draft's max_seq_len below the target's; rows outside
+ * 2..4; a null cfg; the argument errors of the n-gram calls. */
+typedef struct yalm_spec_model {
+	int rows;                 /* 2..4 */
+	const int *draft_stream;  /* test / benchmark hook, host, or NULL: as in yalm_spec */
+	int draft_stream_len;
+} yalm_spec_model;
+int yalm_generate_speculative_model(yalm_decoder d, yalm_decoder draft, int token, int pos, int n_tokens,
+                                    const yalm_spec_model *cfg, const yalm_sampling *s, const float *uniforms,
+                                    int *out_tokens, yalm_spec_stats *stats);
+/* The stream decoder d enqueues on (its own, or the one it was created on). Not owned by the
+ * caller when the decoder created it: do not destroy it. */
+int yalm_decoder_get_stream(yalm_decoder d, yalm_stream *out);
 /* Test hook (host pointers, synchronous, no decoder): the draw and the accept launch of a sampled
  * speculative step exactly as the loop makes them, on logits [T][n] (stride n, n <= 131072, 1 <=
  * T <= 4) with no token produced yet: row t is drawn with uniforms[t]; drafts[k - 1] = d_k for k

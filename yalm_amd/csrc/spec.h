@@ -31,6 +31,7 @@ struct SpecState {
 	int steps;                // speculative steps run since the loop began
 	int accepted;             // drafts accepted since the loop began
 	int drawn[SPEC_MAX_ROWS]; // the sampled loop: the token drawn from each row (spec_sample_rows_kernel)
+	int none;                 // the draft-model loop: this step's drafts are none (spec_model_sync_kernel)
 };
 
 // yalm_forward_rows: the host's row tokens (kernel arguments: no host buffer to outlive the call).
@@ -153,6 +154,51 @@ __global__ __launch_bounds__(SPEC_DRAFT_THREADS) void spec_draft_kernel(const St
 			sp->draft[threadIdx.x] = -1;
 		sp->tok[threadIdx.x] = ok ? dk : 0;
 	}
+}
+
+// The draft-model drafter (yalm_generate_speculative_model): a second decoder on the same stream
+// proposes the rows. A step is sync (1 launch) -> rows - 1 greedy forwards of the draft decoder
+// from its own device state -> one KV-only forward of it -> gather (1) -> the rows forward and the
+// verify (or draw + accept) launches as above.
+//
+// Sync: the draft decoder's step becomes the target's (token, pos) with nothing produced, so its
+// greedy forwards write d_1 .. d_(T-1) to its token buffer [0, T - 1) and its KV rows pos ..
+// pos + T - 2; the KV-only forward then feeds d_(T-1) at pos + T - 1, so a fully accepted step
+// leaves no hole in the draft's cache. A token the draft does not have is fed as token 0 and the
+// step's drafts are none (sp->none): the draft's embedding is never read out of range.
+__global__ __launch_bounds__(64) void spec_model_sync_kernel(const StepState *st, SpecState *sp, StepState *dst,
+                                                             int draft_vocab) {
+	if (threadIdx.x == 0) {
+		const int token = st->token;
+		const bool ok = token >= 0 && token < draft_vocab;
+		dst->token = ok ? token : 0;
+		dst->pos = st->pos;
+		dst->n_gen = 0;
+		sp->none = ok ? 0 : 1;
+	}
+}
+
+// Gather: sp->draft and sp->tok of rows 1..T-1 as spec_draft_kernel leaves them, d_k =
+// dtok[k - 1] (the draft decoder's token buffer), none when sp->none is set or the target does
+// not have the token. stream != null (test / benchmark hook): d_k = stream[n_gen + k - 1]
+// instead, none past its end, whatever the draft decoder produced.
+__global__ __launch_bounds__(64) void spec_model_gather_kernel(const StepState *st, SpecState *sp,
+                                                               const int *__restrict__ dtok, int gen_cap, int T,
+                                                               const int *__restrict__ stream, int stream_len,
+                                                               int vocab) {
+	const int k = threadIdx.x;
+	if (k < 1 || k >= T)
+		return;
+	int dk;
+	if (stream) {
+		const int j = min(st->n_gen, gen_cap) + k - 1;
+		dk = j < stream_len ? stream[j] : -1;
+	} else {
+		dk = sp->none ? -1 : dtok[k - 1];
+	}
+	const bool ok = dk >= 0 && dk < vocab;
+	sp->draft[k] = ok ? dk : -1;
+	sp->tok[k] = ok ? dk : 0;
 }
 
 // yalm_spec_draft: the drafter on a given history alone.

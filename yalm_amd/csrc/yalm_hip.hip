@@ -2119,15 +2119,97 @@ extern "C" int yalm_spec_draft(const int *history, int m, int rows, int ngram_ma
 	return YALM_OK;
 }
 
+// ---- the draft-model drafter (spec.h): a second decoder on the target's stream proposes the rows
+static int model_drafts_check(const yalm_decoder_s *d, const yalm_decoder_s *draft, const std::string &who) {
+	ARGCHK(draft != d, who + ": the draft decoder must not be the target decoder");
+	const char *why = nullptr;
+	if (draft->moe_E > 0)
+		why = ": a mixture-of-experts draft decoder is not supported (the draft is a dense one-GPU decoder)";
+	else if (draft->tp_size > 1 || draft->comm || draft->ipc)
+		why = ": a tensor-parallel draft decoder is not supported (the draft is a dense one-GPU decoder)";
+	if (why) {
+		set_err(who + why);
+		return YALM_ERR_UNSUPPORTED;
+	}
+	ARGCHK(draft->stream == d->stream,
+	       who + ": the two decoders must share one stream (create the draft on yalm_decoder_get_stream of the target)");
+	ARGCHK(draft->c.max_seq_len >= d->c.max_seq_len, who + ": the draft's max_seq_len is below the target's");
+	return YALM_OK;
+}
+
+// Kernel launches of one greedy and of one KV-only forward of the draft decoder: the kernel
+// nodes of its own graphs (what yalm_graph_kernels reports in modes 2 and 0; an eagerly
+// launching decoder captures the sequence once to count it). Leaves the KV-only graph ready.
+static int graph_kernel_count(hipGraph_t g, int *kernels, int *nodes) {
+	size_t n = 0;
+	HIPCHK(hipGraphGetNodes(g, nullptr, &n));
+	std::vector<hipGraphNode_t> v(n);
+	if (n)
+		HIPCHK(hipGraphGetNodes(g, v.data(), &n));
+	int k = 0;
+	for (auto node : v) {
+		hipGraphNodeType t;
+		HIPCHK(hipGraphNodeGetType(node, &t));
+		k += t == hipGraphNodeTypeKernel;
+	}
+	*kernels = k;
+	if (nodes)
+		*nodes = (int)n;
+	return YALM_OK;
+}
+
+static int model_drafts_kernels(yalm_decoder_s *draft, int *greedy, int *hydrate) {
+	const int which[2] = {GRAPH_GREEDY, GRAPH_HYDRATE};
+	int *const out[2] = {greedy, hydrate};
+	for (int i = 0; i < 2; ++i) {
+		if (!draft->eager) {
+			TRY(ensure_graph(draft, which[i]));
+			TRY(graph_kernel_count(draft->graph[which[i]], out[i], nullptr));
+			continue;
+		}
+		HIPCHK(hipStreamBeginCapture(draft->stream, hipStreamCaptureModeRelaxed));
+		const int r = enqueue_forward(draft, which[i]);
+		hipGraph_t g = nullptr;
+		const hipError_t e = hipStreamEndCapture(draft->stream, &g);
+		if (r != YALM_OK)
+			return r;
+		HIPCHK(e);
+		const int rc = graph_kernel_count(g, out[i], nullptr);
+		(void)hipGraphDestroy(g);
+		TRY(rc);
+	}
+	return YALM_OK;
+}
+
+// One step's drafts: sync, rows - 1 greedy forwards of the draft from its device state (the
+// path of yalm_enqueue_greedy, position unknown to the host), the KV-only forward of the last
+// draft at the state they left, gather. No host synchronisation.
+static int enqueue_model_drafts(yalm_decoder_s *d, yalm_decoder_s *draft, int rows, const int *stream, int stream_len) {
+	hipStream_t st = d->stream;
+	spec_model_sync_kernel<<<1, 64, 0, st>>>(d->step, d->spec, draft->step, draft->c.vocab_size);
+	HIPCHK(hipGetLastError());
+	TRY(replay_greedy(draft, rows - 1, -1));
+	TRY(replay(draft, GRAPH_HYDRATE));
+	spec_model_gather_kernel<<<1, 64, 0, st>>>(d->step, d->spec, draft->tokens, d->tokens_cap, rows, stream, stream_len,
+	                                           d->c.vocab_size);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
 // The speculative loop, greedy (smp == nullptr: every row's argmax, spec_verify_kernel) or sampled
 // (every row drawn with the uniform of its output index, spec_sample_rows_kernel, then
 // spec_accept_kernel; the plain steps past the window are sample_kernel steps).
+// The drafter is the loop's one hook: the n-gram launch (draft == nullptr), or a draft decoder's
+// forwards between a sync and a gather launch (model_drafts_check / enqueue_model_drafts).
 static int generate_speculative(yalm_decoder_s *d, const char *name, int token, int pos, int n_tokens,
                                 const yalm_spec *cfg, const yalm_sampling *smp, const float *uniforms,
-                                const int *context, int n_context, int *out_tokens, yalm_spec_stats *stats) {
+                                const int *context, int n_context, int *out_tokens, yalm_spec_stats *stats,
+                                yalm_decoder_s *draft = nullptr) {
 	const std::string who(name);
 	ARGCHK(d && cfg && (out_tokens || n_tokens == 0), who + ": null argument");
 	TRY(rows_supported(d, name));
+	if (draft)
+		TRY(model_drafts_check(d, draft, who));
 	ARGCHK(token >= 0 && token < d->vocab_full && pos >= 0 && n_tokens >= 0, who + ": bad token/pos/n_tokens");
 	ARGCHK(cfg->rows >= 2 && cfg->rows <= SPEC_MAX_ROWS, who + ": rows must be 2..4");
 	ARGCHK(cfg->ngram_min >= 1 && cfg->ngram_min <= cfg->ngram_max && cfg->ngram_max <= SPEC_MAX_NGRAM,
@@ -2143,6 +2225,11 @@ static int generate_speculative(yalm_decoder_s *d, const char *name, int token, 
 	const int rows = cfg->rows, L = d->c.n_layers, n = n_tokens;
 	yalm_spec_stats s{};
 	s.launches_per_step = (smp ? 5 : 4) + L * ((d->gq.empty() ? 4 : 5) + rows);
+	if (draft) { // sync + gather in the n-gram launch's place, and the draft's forwards
+		int kg = 0, kh = 0;
+		TRY(model_drafts_kernels(draft, &kg, &kh));
+		s.launches_per_step += 1 + (rows - 1) * kg + kh;
+	}
 	if (n == 0) {
 		if (stats)
 			*stats = s;
@@ -2186,10 +2273,14 @@ static int generate_speculative(yalm_decoder_s *d, const char *name, int token, 
 		}
 		const int batch = std::min(std::min((n - done + rows - 1) / rows, room), 64);
 		for (int i = 0; i < batch; ++i) {
-			spec_draft_kernel<<<1, SPEC_DRAFT_THREADS, 0, st>>>(d->step, d->spec, d->spec_ctx, n_ctx, d->tokens,
-			                                                    d->tokens_cap, rows, cfg->ngram_max, cfg->ngram_min,
-			                                                    stream, stream_len, V);
-			HIPCHK(hipGetLastError());
+			if (draft) {
+				TRY(enqueue_model_drafts(d, draft, rows, stream, stream_len));
+			} else {
+				spec_draft_kernel<<<1, SPEC_DRAFT_THREADS, 0, st>>>(d->step, d->spec, d->spec_ctx, n_ctx, d->tokens,
+				                                                    d->tokens_cap, rows, cfg->ngram_max, cfg->ngram_min,
+				                                                    stream, stream_len, V);
+				HIPCHK(hipGetLastError());
+			}
 			TRY(enqueue_rows_forward(d, rows, 1));
 			if (smp) { // rows past output index n - 1 read the clamped last uniform; their tokens are dropped below
 				if (V % 4 == 0)
@@ -2209,6 +2300,8 @@ static int generate_speculative(yalm_decoder_s *d, const char *name, int token, 
 		HIPCHK(hipMemcpyAsync(&produced, &d->step->n_gen, sizeof(int), hipMemcpyDeviceToHost, st));
 		HIPCHK(hipStreamSynchronize(st));
 		TRY(awo_check(d));
+		if (draft)
+			TRY(awo_check(draft));
 		if (produced <= done) {
 			set_err(who + ": internal: a batch produced no token");
 			return YALM_ERR_HIP;
@@ -2226,6 +2319,8 @@ static int generate_speculative(yalm_decoder_s *d, const char *name, int token, 
 		HIPCHK(hipStreamSynchronize(st));
 	}
 	d->host_pos = (long long)pos + n;
+	if (draft)
+		draft->host_pos = -1; // its device (token, pos) is wherever the last step's forwards left it
 	s.spec_steps = sp.steps;
 	s.accepted_drafts = sp.accepted - std::max(0, done - n);
 	if (stats)
@@ -2246,6 +2341,23 @@ extern "C" int yalm_generate_speculative_sampled(yalm_decoder d, int token, int 
 	ARGCHK(s && (uniforms || n_tokens == 0), "yalm_generate_speculative_sampled: null argument");
 	return generate_speculative(d, "yalm_generate_speculative_sampled", token, pos, n_tokens, cfg, s, uniforms, context,
 	                            n_context, out_tokens, stats);
+}
+
+extern "C" int yalm_generate_speculative_model(yalm_decoder d, yalm_decoder draft, int token, int pos, int n_tokens,
+                                               const yalm_spec_model *cfg, const yalm_sampling *s, const float *uniforms,
+                                               int *out_tokens, yalm_spec_stats *stats) {
+	static const char *const who = "yalm_generate_speculative_model";
+	ARGCHK(d && draft && cfg, std::string(who) + ": null argument");
+	ARGCHK(!s || uniforms || n_tokens == 0, std::string(who) + ": null argument");
+	const yalm_spec spec{cfg->rows, 1, 1, cfg->draft_stream, cfg->draft_stream_len}; // (the n-gram bounds are unused)
+	return generate_speculative(d, who, token, pos, n_tokens, &spec, s, s ? uniforms : nullptr, nullptr, 0, out_tokens,
+	                            stats, draft);
+}
+
+extern "C" int yalm_decoder_get_stream(yalm_decoder d, yalm_stream *out) {
+	ARGCHK(d && out, "yalm_decoder_get_stream: null argument");
+	*out = reinterpret_cast<yalm_stream>(d->stream);
+	return YALM_OK;
 }
 
 // ------------------------------------------------------------------ batched decode (batch.h)
@@ -2742,21 +2854,7 @@ extern "C" int yalm_graph_kernels(yalm_decoder d, int mode, int *kernels, int *n
 		return YALM_ERR_UNSUPPORTED;
 	}
 	TRY(ensure_graph(d, mode));
-	size_t n = 0;
-	HIPCHK(hipGraphGetNodes(d->graph[mode], nullptr, &n));
-	std::vector<hipGraphNode_t> v(n);
-	if (n)
-		HIPCHK(hipGraphGetNodes(d->graph[mode], v.data(), &n));
-	int k = 0;
-	for (auto node : v) {
-		hipGraphNodeType t;
-		HIPCHK(hipGraphNodeGetType(node, &t));
-		k += t == hipGraphNodeTypeKernel;
-	}
-	*kernels = k;
-	if (nodes)
-		*nodes = (int)n;
-	return YALM_OK;
+	return graph_kernel_count(d->graph[mode], kernels, nodes);
 }
 
 extern "C" int yalm_decoder_set_launch(yalm_decoder d, int flags) {

@@ -5,7 +5,8 @@
 // device sampling for -t > 0: only the token comes back per step. -s <rows> runs the greedy
 // (-t 0) or the device-sampled (-t > 0 with -k / -p) completion by speculative steps of 2..4
 // rows with n-gram drafts from the prompt and the output so far: the same tokens, several per
-// pass over the weights where drafts hit.
+// pass over the weights where drafts hit. -D <draft checkpoint> (with -s) takes the drafts from a
+// second, smaller model of the same family instead: it proposes a token at every row.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -14,6 +15,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <sstream>
 
 #include "model.h"
@@ -48,6 +50,8 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -s <int>   speculative decode with this many rows per step, 2..4 (0 - off, the default);\n"
 	                "             needs -t 0 (greedy), or -t > 0 with -k or -p (sampled on the device: the\n"
 	                "             same tokens as without -s)\n");
+	fprintf(stderr, "  -D <path>  draft model checkpoint for -s: a smaller model of the same family (loaded with the\n"
+	                "             same -T) proposes every row's draft in place of the n-gram lookup; needs -s\n");
 	fprintf(stderr, "  -N <int>   completions of one prompt decoded together, 2..4 (0 - off, the default): one pass\n"
 	                "             over the weights per step for all of them; needs -t > 0 with -k or -p (greedy\n"
 	                "             completions would be identical); not with -s\n");
@@ -94,7 +98,7 @@ static std::vector<int> encode_prompt(const Tokenizer &tok, const std::string &p
 
 static void run_completion(const std::string &path, const std::string &device, const std::string &prompt,
                            int context, int num_steps, float temperature, bool device_sampling, int top_k,
-                           float top_p, int spec_rows, int n_completions) {
+                           float top_p, int spec_rows, int n_completions, const std::string &draft_path) {
 	YALMData data;
 	if (data.from_file(path) != 0) {
 		fprintf(stderr, "error: cannot load %s\n", path.c_str());
@@ -132,6 +136,33 @@ static void run_completion(const std::string &path, const std::string &device, c
 		for (size_t pos = 0; pos < first; ++pos)
 			read_bytes += model.config->active_bytes(pos);
 	}
+	// -D: the draft model, its decoder on the target's stream, hydrated with the same prompt
+	// (declared after the target's state: it is destroyed first, while the stream still exists)
+	YALMData draft_data;
+	std::unique_ptr<Model> draft_model;
+	std::unique_ptr<InferenceState> draft_state;
+	if (!draft_path.empty()) {
+		if (draft_data.from_file(draft_path) != 0) {
+			fprintf(stderr, "error: cannot load %s\n", draft_path.c_str());
+			exit(1);
+		}
+		draft_model = std::make_unique<Model>(draft_data, context);
+		draft_state = std::make_unique<InferenceState>(draft_model->config);
+		draft_model->cuda();
+		draft_state->cuda();
+		draft_model->share_stream(*draft_state, state);
+		const int dv = draft_model->config->vocab_size;
+		if (dv != model.config->vocab_size)
+			fprintf(stderr, "[yalm] note: the draft's vocabulary (%d) differs from the model's (%d); tokens one of them "
+			                "lacks are never drafted\n", dv, model.config->vocab_size);
+		std::vector<int> fed(encoding.begin(), encoding.end() - 1); // a token the draft lacks is fed as token 0
+		for (int &t : fed)
+			t = t < dv ? t : 0;
+		if (!(fed.size() >= 3 && (int)fed.size() <= draft_model->config->max_seq_len &&
+		      draft_model->prefill(*draft_state, fed.data(), (int)fed.size(), 0, nullptr)))
+			for (size_t pos = 0; pos < fed.size(); ++pos)
+				draft_model->forward(*draft_state, fed[pos], (int)pos, InferenceMode::HYDRATE_KV_CACHE);
+	}
 	// YALM_SEED (tests): re-seeded before the first draw, as in run_passkey, because the HIP
 	// runtime's initialisation above draws from std::rand too
 	if (sampled && getenv("YALM_SEED"))
@@ -158,10 +189,15 @@ static void run_completion(const std::string &path, const std::string &device, c
 		const int chunk = num_steps == -1 ? SPEC_CHUNK : std::min(SPEC_CHUNK, num_steps - done);
 		int out[SPEC_CHUNK];
 		const int pos = (int)encoding.size() - 1;
-		if (sampled) { // one draw per token of the chunk, in order: token j consumes the j-th draw, as without -s
-			float u[SPEC_CHUNK];
+		float u[SPEC_CHUNK];
+		if (sampled) // one draw per token of the chunk, in order: token j consumes the j-th draw, as without -s
 			for (int j = 0; j < chunk; ++j)
 				u[j] = uniform();
+		if (draft_model)
+			model.generate_speculative_model(state, *draft_model, *draft_state, encoding.back(), pos, chunk, spec_rows,
+			                                 temperature, top_k, top_p, sampled ? u : nullptr, out, &spec_steps,
+			                                 &spec_accepted, &spec_plain);
+		else if (sampled) {
 			model.generate_speculative_sampled(state, encoding.back(), pos, chunk, spec_rows, temperature, top_k, top_p, u,
 			                                   encoding.data(), (int)encoding.size(), out, &spec_steps, &spec_accepted,
 			                                   &spec_plain);
@@ -259,6 +295,9 @@ static void run_completion(const std::string &path, const std::string &device, c
 	if (spec_rows > 0)
 		printf("  speculative: %d steps of %d rows, %d accepted drafts, %d plain steps\n\n", spec_steps, spec_rows,
 		       spec_accepted, spec_plain);
+	if (draft_model)
+		printf("  draft model: %s, %d of its %d drafts accepted\n\n", draft_path.c_str(), spec_accepted,
+		       spec_steps * (spec_rows - 1));
 }
 
 static void run_perplexity(const std::string &path, const std::string &device, const std::string &prompt,
@@ -397,7 +436,7 @@ static void run_passkey(const std::string &path, const std::string &device, int 
 }
 
 int main(int argc, char *argv[]) {
-	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path;
+	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path, draft_path;
 	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0, spec_rows = 0, n_completions = 0;
 	float temperature = 1.0f, top_p = 1.0f;
 	bool device_sampling = false;
@@ -440,6 +479,7 @@ int main(int argc, char *argv[]) {
 			break;
 		case 's': spec_rows = std::stoi(v); break;
 		case 'N': n_completions = std::stoi(v); break;
+		case 'D': draft_path = v; break;
 		case 'f': prompt_path = v; break;
 		case 'T': context = std::stoi(v); break;
 		case 'l': passkey_pos = std::stoi(v); break;
@@ -454,6 +494,9 @@ int main(int argc, char *argv[]) {
 	// host sampler (-t > 0 alone) reads the logits of one row and has no speculative form
 	if (spec_rows != 0 && (spec_rows < 2 || spec_rows > 4 || (temperature != 0.0f && !device_sampling) ||
 	                       temperature < 0.0f || mode != "completion"))
+		error_usage();
+	// -D: the drafter of -s (whose checks above then cover the mode and the sampling)
+	if (!draft_path.empty() && spec_rows == 0)
 		error_usage();
 	// -N: completion mode, sampled on the device (-t > 0 with -k or -p): greedy completions of one
 	// prompt would be identical, and the host sampler reads one row's logits
@@ -482,7 +525,7 @@ int main(int argc, char *argv[]) {
 	try {
 		if (mode == "completion")
 			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p,
-			               spec_rows, n_completions);
+			               spec_rows, n_completions, draft_path);
 		else if (mode == "passkey")
 			run_passkey(checkpoint, device, context, n_junk, passkey_pos);
 		else

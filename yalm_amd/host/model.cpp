@@ -333,7 +333,7 @@ void Model::cuda() {
 	_device = Device::HIP;
 }
 
-void Model::ensure_decoder(InferenceState &s) {
+void Model::ensure_decoder(InferenceState &s, yalm_stream stream) {
 	if (s.device() != _device)
 		throw std::runtime_error("FATAL: inference state device mismatch");
 	if (_device != Device::HIP)
@@ -351,9 +351,9 @@ void Model::ensure_decoder(InferenceState &s) {
 		for (auto &b : blocks)
 			gates.push_back(b->moegate());
 		const yalm_moe_config mc{config->n_experts, config->n_experts_active};
-		check(yalm_decoder_create_moe(&cc, &mc, &mw, gates.data(), nullptr, &s._decoder), "decoder create");
+		check(yalm_decoder_create_moe(&cc, &mc, &mw, gates.data(), stream, &s._decoder), "decoder create");
 	} else {
-		check(yalm_decoder_create(&cc, &mw, nullptr, &s._decoder), "decoder create");
+		check(yalm_decoder_create(&cc, &mw, stream, &s._decoder), "decoder create");
 	}
 	if (config->rope_scaling.type)
 		check(yalm_decoder_set_rope_scaling(s._decoder, &config->rope_scaling), "rope scaling");
@@ -408,6 +408,35 @@ void Model::generate_speculative(InferenceState &s, int token, int pos, int n, i
 	const yalm_spec cfg{rows, 3, 1, nullptr, 0};
 	yalm_spec_stats st{};
 	check(yalm_generate_speculative(s._decoder, token, pos, n, &cfg, context, n_context, out, &st), "speculative steps");
+	if (steps)
+		*steps += st.spec_steps;
+	if (accepted)
+		*accepted += st.accepted_drafts;
+	if (plain)
+		*plain += st.plain_steps;
+}
+
+void Model::share_stream(InferenceState &s, const InferenceState &other) {
+	if (s._decoder)
+		throw std::runtime_error("share_stream: the inference state already has a decoder");
+	if (!other._decoder)
+		throw std::runtime_error("share_stream: the other inference state has no decoder yet (run a forward on it)");
+	yalm_stream st = nullptr;
+	check(yalm_decoder_get_stream(other._decoder, &st), "decoder stream");
+	ensure_decoder(s, st);
+}
+
+void Model::generate_speculative_model(InferenceState &s, Model &draft, InferenceState &ds, int token, int pos, int n,
+                                       int rows, float temperature, int top_k, float top_p, const float *uniforms,
+                                       int *out, int *steps, int *accepted, int *plain) {
+	ensure_decoder(s);
+	draft.ensure_decoder(ds);
+	const yalm_spec_model cfg{rows, nullptr, 0};
+	const yalm_sampling sp{temperature, top_k, top_p};
+	yalm_spec_stats st{};
+	check(yalm_generate_speculative_model(s._decoder, ds._decoder, token, pos, n, &cfg, uniforms ? &sp : nullptr, uniforms,
+	                                      out, &st),
+	      "speculative steps with a draft model");
 	if (steps)
 		*steps += st.spec_steps;
 	if (accepted)

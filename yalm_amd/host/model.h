@@ -156,6 +156,17 @@ struct Model {
 	void generate_speculative_sampled(InferenceState &s, int token, int pos, int n, int rows, float temperature,
 	                                  int top_k, float top_p, const float *uniforms, const int *context, int n_context,
 	                                  int *out, int *steps, int *accepted, int *plain);
+	// Speculative steps whose drafts come from a second, smaller model (yalm_generate_speculative_model):
+	// `draft` / `ds` propose a token at every row. uniforms == nullptr: greedy, the tokens of
+	// generate_speculative; else n uniforms, the tokens of generate_speculative_sampled. ds's decoder
+	// must sit on s's stream (draft.share_stream(ds, s) before anything else runs on ds), and the
+	// caller hydrates positions [0, pos) on both states.
+	void generate_speculative_model(InferenceState &s, Model &draft, InferenceState &ds, int token, int pos, int n,
+	                                int rows, float temperature, int top_k, float top_p, const float *uniforms, int *out,
+	                                int *steps, int *accepted, int *plain);
+	// Creates s's decoder (for this model) on the stream of `other`'s decoder, which must exist
+	// (any forward on it creates it) and outlive s. Throws if s already has a decoder.
+	void share_stream(InferenceState &s, const InferenceState &other);
 	// n_seq completions side by side (yalm_batch_generate_sampled: one pass over the weights per
 	// step for all of them). load >= 0: first copy KV rows [0, load) of the state's own cache into
 	// every sequence (the prompt, hydrated once by forward / prefill). Sequence q feeds tokens[q] at
@@ -181,7 +192,7 @@ struct Model {
 	}
 
 private:
-	void ensure_decoder(InferenceState &s);
+	void ensure_decoder(InferenceState &s, yalm_stream stream = nullptr);
 	Device _device = Device::CPU;
 	bool _tied = false;
 	std::vector<void *> _owned;

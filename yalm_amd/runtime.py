@@ -75,6 +75,12 @@ class Spec(ctypes.Structure):
                 ("draft_stream_len", c_int)]
 
 
+class SpecModel(ctypes.Structure):
+    """yalm_spec_model: rows 2..4, the draft_stream hook."""
+
+    _fields_ = [("rows", c_int), ("draft_stream", c_void_p), ("draft_stream_len", c_int)]
+
+
 class SpecStats(ctypes.Structure):
     """yalm_spec_stats."""
 
@@ -212,6 +218,10 @@ _sig("yalm_spec_draft", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p])
 _sig("yalm_generate_speculative_sampled", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Spec),
                                                    ctypes.POINTER(Sampling), c_void_p, c_void_p, c_int, c_void_p,
                                                    ctypes.POINTER(SpecStats)])
+_sig("yalm_generate_speculative_model", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SpecModel),
+                                                 ctypes.POINTER(Sampling), c_void_p, c_void_p,
+                                                 ctypes.POINTER(SpecStats)])
+_sig("yalm_decoder_get_stream", c_int, [c_void_p, ctypes.POINTER(c_void_p)])
 _sig("yalm_spec_sample_rows", c_int, [c_void_p, c_int, c_int, ctypes.POINTER(Sampling), c_void_p, c_void_p, c_void_p,
                                        c_void_p, ctypes.POINTER(c_int)])
 _sig("yalm_decoder_set_rope_scaling", c_int, [c_void_p, ctypes.POINTER(RopeScaling)])
@@ -258,6 +268,7 @@ EXPORTED = [
     "yalm_batch_create", "yalm_batch_destroy", "yalm_batch_load", "yalm_batch_forward",
     "yalm_batch_generate_greedy", "yalm_batch_generate_sampled", "yalm_batch_state", "yalm_batch_set_launch",
     "yalm_batch_buffers",
+    "yalm_generate_speculative_model", "yalm_decoder_get_stream",
 ]
 BATCH_ATTN_PER_SEQ = 1  # yalm_batch_set_launch
 BATCH_GUARD_BYTES = 256  # YALM_BATCH_GUARD_BYTES
@@ -421,7 +432,12 @@ class Stream:
     n_parts (yalm_stream_create_cu_part), so n_parts rank processes on one GPU run on
     disjoint CUs -- the one-GPU rehearsal of tensor parallelism."""
 
-    def __init__(self, cu_part=None):
+    def __init__(self, cu_part=None, borrowed=None):
+        """borrowed: the handle of a stream someone else owns (Decoder.get_stream); close() leaves it."""
+        self.owned = borrowed is None
+        if borrowed is not None:
+            self.h = c_void_p(borrowed)
+            return
         self.h = c_void_p()
         if cu_part is None:
             check(lib.yalm_stream_create(ctypes.byref(self.h)))
@@ -429,9 +445,9 @@ class Stream:
             check(lib.yalm_stream_create_cu_part(cu_part[0], cu_part[1], ctypes.byref(self.h)))
 
     def close(self):
-        if self.h:
+        if self.h and self.owned:
             check(lib.yalm_stream_destroy(self.h))
-            self.h = None
+        self.h = None
 
 
 def tp_unique_id() -> bytes:
@@ -781,7 +797,7 @@ class Decoder:
     """InferenceState on the device + Model::forward (graph-replayed)."""
 
     def __init__(self, model: DeviceModel, tp_id: bytes = None, tp_gather=None, kv_caches=None,
-                 cu_part=None, launch: int = 0):
+                 cu_part=None, launch: int = 0, stream=None):
         """Tensor parallel over model.tp = (rank, size), one of:
         tp_id: the RCCL unique id (tp_unique_id() on rank 0, shared with the
         other ranks); tp_gather: a function mapping this rank's 128-byte rank
@@ -792,7 +808,10 @@ class Decoder:
         Block::cuda() hands its own caches over (model.cpp:185-211); default: the
         decoder allocates zeroed caches. cu_part = (part, n_parts): decode on a
         stream restricted to that CU block (Stream). launch: yalm_decoder_set_launch
-        flags (LAUNCH_*)."""
+        flags (LAUNCH_*). stream: an existing Stream to create the decoder on (it stays the
+        caller's; e.g. another decoder's get_stream(), for generate_speculative_model)."""
+        if stream is not None and cu_part is not None:
+            raise ValueError("Decoder: pass cu_part or stream, not both")
         self.model = model
         self.cfg = model.cfg
         self._c = Config.from_model(self.cfg)
@@ -804,7 +823,8 @@ class Decoder:
         self._mw = mw
         self.h = None
         self.stream = Stream(cu_part) if cu_part is not None else None
-        sh = self.stream.h if self.stream else None
+        self._on_stream = stream  # kept alive, never closed here
+        sh = self.stream.h if self.stream else stream.h if stream is not None else None
         h = c_void_p()
         if tp_gather is not None:
             rank, size = getattr(model, "tp", (0, 1))
@@ -993,6 +1013,45 @@ class Decoder:
         check(lib.yalm_generate_speculative_sampled(self.h, token, pos, n, ctypes.byref(spec), ctypes.byref(s), _ptr(u),
                                                     _ptr(ctx) if ctx.size else None, ctx.size, out.ctypes.data,
                                                     ctypes.byref(st)))
+        return out[:n].tolist(), {"spec_steps": st.spec_steps, "accepted_drafts": st.accepted_drafts,
+                                  "plain_steps": st.plain_steps, "launches_per_step": st.launches_per_step}
+
+    def get_stream(self) -> Stream:
+        """The stream this decoder enqueues on (yalm_decoder_get_stream), as a borrowed Stream: pass
+        it as Decoder(..., stream=) to put a second decoder on it. It lives as long as its owner."""
+        h = c_void_p()
+        check(lib.yalm_decoder_get_stream(self.h, ctypes.byref(h)))
+        return Stream(borrowed=h.value)
+
+    def generate_speculative_model(self, draft: "Decoder", token: int, pos: int, n: int, rows: int = 4,
+                                   temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, uniforms=None,
+                                   draft_stream=None):
+        """n tokens by speculative steps of `rows` rows whose drafts come from the decoder `draft` on
+        the same stream (yalm_generate_speculative_model): (tokens, stats dict). temperature 0:
+        greedy, the tokens of generate_speculative; else sampled with `uniforms` (n values), the
+        tokens of generate_speculative_sampled. Hydrate [0, pos) on both decoders first.
+        draft_stream: the test / benchmark hook replacing the draft's tokens (its forwards still run)."""
+        ds = None if draft_stream is None else np.ascontiguousarray(draft_stream, dtype=np.int32).reshape(-1)
+        keep = np.zeros(1, np.int32)  # a non-NULL pointer for an empty stream
+        cfg = None if rows is None else SpecModel(  # rows None: a NULL cfg (the argument test)
+            rows, None if ds is None else (_ptr(ds) if ds.size else _ptr(keep)), 0 if ds is None else ds.size)
+        s, u = None, None
+        if temperature != 0.0:
+            if uniforms is None:
+                raise ValueError("generate_speculative_model: sampling needs uniforms")
+            u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+            if u.size < n:
+                raise ValueError(f"generate_speculative_model: {n} tokens need {n} uniforms, got {u.size}")
+            if u.size == 0:
+                u = np.zeros(1, np.float32)
+            s = Sampling(temperature, top_k, top_p)
+        st = SpecStats()
+        out = np.zeros(max(n, 1), np.int32)
+        check(lib.yalm_generate_speculative_model(self.h, draft.h if draft is not None else None, token, pos, n,
+                                                  ctypes.byref(cfg) if cfg is not None else None,
+                                                  ctypes.byref(s) if s is not None else None,
+                                                  _ptr(u) if u is not None else None, out.ctypes.data,
+                                                  ctypes.byref(st)))
         return out[:n].tolist(), {"spec_steps": st.spec_steps, "accepted_drafts": st.accepted_drafts,
                                   "plain_steps": st.plain_steps, "launches_per_step": st.launches_per_step}
 
