@@ -176,17 +176,17 @@ InferenceState::~InferenceState() {
 		yalm_batch_destroy(_batch);
 	if (_decoder)
 		yalm_decoder_destroy(_decoder);
-	if (_device == Device::HIP)
-		yalm_unregister_host(_logits);
 	delete[] _logits;
 }
 
 void InferenceState::cuda() {
 	if (_device != Device::CPU)
 		return;
+	// The logits stay ordinary host memory (the reference pins them, model.cpp:338): the decoder
+	// copies an OUTPUT forward's logits by DMA into a pinned buffer of its own and from there
+	// into the caller's, so registering this one buys nothing, and hipHostRegister is not
+	// supported everywhere (virtual machines with a passed-through GPU refuse it).
 	_device = Device::HIP;
-	// pinned logits so the OUTPUT copy is a straight DMA (model.cpp:338)
-	check(yalm_register_host(_logits, sizeof(float) * _config->vocab_size), "register logits");
 }
 
 Block::Block(int layer_i, std::shared_ptr<Config> config, const Tensor *rms_att_weight, const Tensor *rms_ffn_weight,
