@@ -849,6 +849,80 @@ int yalm_attn_prefill(uint16_t *o, const uint16_t *q, const uint16_t *kc, const 
  * argument. */
 int yalm_attn_prefill_rows(uint16_t *o, int o_rows, const uint16_t *q, const uint16_t *kc, const uint16_t *vc,
                            int cache_rows, int T, int pos0, int n_heads, int n_kv_heads, int head_dim, int split);
+/* One stage of a decoder's prefill, made by the function the prefill itself calls, on host arrays,
+ * synchronous. The forms are those of yalm_set_prefill_forms(NULL, ...), with `split` as given and
+ * the tile widths and the persistent grid sized for `cus` CUs (0 = this device's). Everything the
+ * stage may write is uploaded as given and returned whole. The A operand `a` is [T][lda] f16 bits as
+ * the decoder holds them: [hi | lo] rows where the stage reads them (QKV: lda = 2 dim always; the
+ * others: lda = K, or 2 K when split). Depths are multiples of 64, every other dim of 128.
+ *   NORM      xn[t] = f16(rmsnorm(x[t]) * normw), rows [hi | lo] when split; x [T][dim] f32; xn holds
+ *             xn_rows >= T rows; range: the operand's range slot (in / out, 1 word).
+ *   QKV       clip, RoPE (rope [T][head_dim / 2][2], row m = position pos0 + m), q to q [q_rows][q_dim]
+ *             ([hi | lo], 2 q_dim, when split), k / v to rows pos0 + m of kc / vc [cache_rows][kv_dim];
+ *             wq | wk | wv f16, bq / bk / bv f32 or all NULL; range: Q's slot.
+ *   RESIDUAL  xres [x_rows][n] f32 += scale * a . w^T, w [n][k] f16; kind YALM_PF_WO or YALM_PF_W2
+ *             selects the forms' width key.
+ *   GLU       h [h_rows][hidden] ([hi | lo], 2 hidden, when split) = f16(hscale * act(a . w1^T) *
+ *             (a . w3^T)); range: H's slot.
+ *   LOGPROB   the logits GEMM's per-tile (max, sum exp) into pmax / psum (T * vocab / 128 floats each,
+ *             the first T * ntiles used as [T][ntiles], ntiles = vocab / info->bn[0]), the target's
+ *             logit into tgt_logit [T], then lp [T] = log p(targets[t]) (targets -1: none, lp 0).
+ * info (may be NULL) reports the path taken: skinny (the split-K skinny GEMMs ran), ks / ks2 (their
+ * K splits; ks2 = the k | v GEMM's), n_gemm large-tile launches with widths bn[i], eight_phase (bit i:
+ * launch i ran the 8-phase kernel), two_depth (the one-launch two-depth QKV form); tiles, grid and
+ * persistent (grid < tiles: the persistent tile loop) of the last launch; norm_nv (the wave norm's
+ * float4s per lane, 0 = the workgroup kernel).
+ * YALM_ERR_ARG before anything is uploaded: a dim that is no such multiple, head_dim not 64 or 128,
+ * cache_rows < pos0 + T, q_rows / x_rows / h_rows / xn_rows < T, a target >= vocab, a scale that is
+ * no power of two. YALM_ERR_UNSUPPORTED where no tile width fits. */
+#define YALM_PF_STAGE_NORM 0
+#define YALM_PF_STAGE_QKV 1
+#define YALM_PF_STAGE_RESIDUAL 2
+#define YALM_PF_STAGE_GLU 3
+#define YALM_PF_STAGE_LOGPROB 4
+#define YALM_PF_WO 1
+#define YALM_PF_W2 3
+typedef struct yalm_prefill_stage_info {
+	int skinny, ks, ks2;
+	int n_gemm, bn[2];
+	int eight_phase, two_depth;
+	int tiles, grid, persistent;
+	int norm_nv;
+} yalm_prefill_stage_info;
+typedef struct {
+	int stage, T, cus, split;
+	int dim; /* NORM: row length; QKV, GLU, LOGPROB: the GEMM depth */
+	const uint16_t *a;
+	unsigned *range;
+	yalm_prefill_stage_info *info;
+	/* NORM */
+	const float *x, *normw;
+	float eps;
+	uint16_t *xn;
+	int xn_rows;
+	/* QKV */
+	int n_heads, n_kv_heads, head_dim, pos0, q_rows, cache_rows;
+	float clip;
+	const uint16_t *wq, *wk, *wv;
+	const float *rope, *bq, *bk, *bv;
+	uint16_t *q, *kc, *vc;
+	/* RESIDUAL */
+	int kind, n, k, x_rows;
+	const uint16_t *w;
+	float scale;
+	float *xres;
+	/* GLU */
+	int hidden, act, h_rows;
+	const uint16_t *w1, *w3;
+	float hscale;
+	uint16_t *h;
+	/* LOGPROB */
+	int vocab;
+	const uint16_t *wcls;
+	const int *targets;
+	float *lp, *pmax, *psum, *tgt_logit;
+} yalm_prefill_stage_args;
+int yalm_prefill_stage(const yalm_prefill_stage_args *args);
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,10 @@ struct PfForms {
 	bool split = false;     // split-operand precision form (yalm_set_prefill_precision): every f16
 							// activation operand as [hi | lo], the large-tile GEMMs at every T
 	bool wnorm = true;      // row norms: one wave per row, the row in registers (rmsnorm_rows_wave_kernel)
+	// set by the yalm_prefill_stage hook alone (no key of the forms spec): the CUs the tile widths and
+	// the persistent grid are sized for (0 = this device's), and the record of what was launched
+	int cus = 0;
+	yalm_prefill_stage_info *info = nullptr;
 };
 PfForms pf_forms_default(); // prefill.hip: the production forms (A/B build: YALM_PF_FORMS)
 

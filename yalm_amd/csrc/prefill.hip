@@ -1,7 +1,7 @@
 // prefill.hip — C ABI of the batched prefill / perplexity path (prefill.h):
 // yalm_prefill (prompt hydration + per-position log p(next), replacing the
 // reference's position-by-position loop in main.cpp:128-200 / 91-97) and
-// its kernel-level test hooks (yalm_gemm_f16, yalm_attn_prefill; mixture of experts:
+// its kernel-level test hooks (yalm_gemm_f16, yalm_attn_prefill, yalm_prefill_stage; mixture of experts:
 // yalm_moe_gemm_f16, yalm_moe_ffn_rows).
 #include <hip/hip_runtime.h>
 
@@ -123,7 +123,7 @@ int pick_bn(const PfForms &f, int kind, int M, int n_eff, bool glu) {
 	const int form = f.g16[kind];
 	if (form > 0 && fits(form) && (form == 128 || form == 192 || form == 256 || form == 320))
 		return form;
-	const long ncu = device_cu_count();
+	const long ncu = f.cus > 0 ? f.cus : device_cu_count();
 	const long tiles_m = (M + pf::G_BM - 1) / pf::G_BM;
 	int best = 0;
 	long best_cost = 0;
@@ -143,6 +143,22 @@ int pick_bn(const PfForms &f, int kind, int M, int n_eff, bool glu) {
 	return best;
 }
 
+// the yalm_prefill_stage hook's record of one large-tile launch (PfForms::info)
+void note_gemm(const PfForms &f, int bn, bool p8, bool two, int tiles, int grid) {
+	yalm_prefill_stage_info *i = f.info;
+	if (!i)
+		return;
+	if (i->n_gemm < 2) {
+		i->bn[i->n_gemm] = bn;
+		i->eight_phase |= (int)p8 << i->n_gemm;
+	}
+	++i->n_gemm;
+	i->two_depth = two;
+	i->tiles = tiles;
+	i->grid = grid;
+	i->persistent = grid < tiles;
+}
+
 // c_split / K2: columns [c_split, N) run K2 (gemm8p_kernel); c_split = N: one depth
 // grp / tile_bound: row groups (prefill_gemm.h RowGroups) and the host-side bound on their M tiles
 template <class EPI, class BMAP, int FJ0, int FJ1, class GRP = pf::NoGroup>
@@ -159,10 +175,11 @@ int launch_g8p(const PfForms &f, const uint16_t *A, int lda, int M, int K, int k
 	}
 	const int nwg = (GRP::ON ? tile_bound : (M + pf::G_BM - 1) / pf::G_BM) * (N / BN);
 	// more tiles than CUs: one persistent workgroup per CU walks them
-	const int ncu = (int)device_cu_count();
+	const int ncu = f.cus > 0 ? f.cus : (int)device_cu_count();
 	// (two depths: one workgroup per tile, so the hardware balances them longest first)
 	const bool two = c_split >= 0 && c_split < N;
 	const int grid = f.persist && nwg > ncu && !two ? ncu : nwg;
+	note_gemm(f, BN, true, two, nwg, grid);
 	hipLaunchKernelGGL(kern, dim3(grid), dim3(pf::G_THREADS), lds, st, A, lda, M, K, kb, bm, N, epi, c0,
 	                   two ? c_split : N, two ? K2 : K, grp);
 	HIPCHK(hipGetLastError());
@@ -190,6 +207,7 @@ int launch_g16_t(const PfForms &f, const uint16_t *A, int lda, int M, int K, int
 		attr = true;
 	}
 	const int nwg = (GRP::ON ? tile_bound : (M + pf::G_BM - 1) / pf::G_BM) * (N / BN);
+	note_gemm(f, BN, false, false, nwg, nwg);
 	hipLaunchKernelGGL(kern, dim3(nwg), dim3(pf::G_THREADS), lds, st, A, lda, M, K, kb, bm, N, epi, c0, grp);
 	HIPCHK(hipGetLastError());
 	return YALM_OK;
@@ -375,6 +393,8 @@ int launch_rmsnorm_t(const PfForms &f, const float *X, const float *w, int dim, 
                      unsigned *range, hipStream_t st) {
 	const int nv = (dim / 4 + 63) / 64; // float4 per lane
 	const int g = (T + 3) / 4;
+	if (f.info)
+		f.info->norm_nv = !(f.wnorm && nv <= 32) ? 0 : nv <= 4 ? 4 : nv <= 8 ? 8 : nv <= 12 ? 12 : nv <= 16 ? 16 : nv <= 24 ? 24 : 32;
 	if (f.wnorm && nv <= 32) {
 		if (nv <= 4)
 			pf::rmsnorm_rows_wave_kernel<SPLIT, 4><<<g, 256, 0, st>>>(X, w, dim, T, eps, Xn, range);
@@ -650,34 +670,184 @@ int ensure_bufs(yalm_decoder_s *d) {
 	return YALM_OK;
 }
 
+// ---- the stages of a prefill, each over explicit buffers: enqueue_prefill and the
+// yalm_prefill_stage test hook make the same launches through these functions
+
+// Short prompts run the split-K skinny GEMMs (the 256-row tiles would leave most CUs idle):
+// when every GEMM the caller runs that way has a K split (ks > 0). The split-operand form
+// takes the large tiles at every T.
+bool pf_small(const PfForms &f, int T, std::initializer_list<int> ks) {
+	bool ok = T <= SK_MAX_T && !f.no_skinny && !f.split;
+	for (int k : ks)
+		ok = ok && k > 0;
+	return ok;
+}
+int sk_ks(int N, int K, int T) { return sk_pick_ks({{N, K, 1}}, 16 * ((T + 15) / 16)); }
+int sk_ks_qkv(int dim, int q_dim, int kv_dim, int T) {
+	return sk_pick_ks({{q_dim, dim, 1}, {2 * kv_dim, 2 * dim, 2}}, 16 * ((T + 15) / 16));
+}
+void note_skinny(const PfForms &f, int ks, int ks2) {
+	if (f.info)
+		f.info->skinny = 1, f.info->ks = ks, f.info->ks2 = ks2;
+}
+
+// QKV + clip + RoPE + cache write of T rows at positions pos0 ..: Xn [T][2 dim] is the normalised
+// x as [hi | lo]; hi is the q columns' A operand, hi + lo the k | v columns' (their cache rows
+// then carry one f16 rounding, infer.cpp:299). small / ks: pf_small and sk_ks_qkv of the caller.
+struct PfQkv {
+	const uint16_t *Xn;
+	const void *wq, *wk, *wv;
+	const float *bq, *bk, *bv; // the biased form's (Qwen2)
+	const float *rope;         // [T][head_dim / 2][2]
+	uint16_t *Q, *kc, *vc;
+	unsigned *range;
+	float *skp; // the skinny path's partials: 2 ks slots of [16 ceil(T / 16)][q_dim + 2 kv_dim]
+	int dim, q_dim, kv_dim, head_dim, T, pos0;
+	float clip;
+	bool small;
+	int ks;
+};
+// every form over the epilogue with or without the q / k / v bias (yalm_decoder_set_qkv_bias): a
+// compile-time flag, so an unbiased model runs the instantiations it always ran
+template <bool B>
+int enqueue_qkv(const PfForms &f, const PfQkv &a, hipStream_t st) {
+	const int dim = a.dim, q_dim = a.q_dim, kv_dim = a.kv_dim, T = a.T;
+	pf::BSrc qkv{};
+	qkv.p[0] = (const uint16_t *)a.wq;
+	qkv.p[1] = (const uint16_t *)a.wk;
+	qkv.p[2] = (const uint16_t *)a.wv;
+	qkv.end[0] = q_dim;
+	qkv.end[1] = q_dim + kv_dim;
+	qkv.end[2] = q_dim + 2 * kv_dim;
+	pf::E16QKVt<false, B> e;
+	e.q = a.Q;
+	e.kc = a.kc;
+	e.vc = a.vc;
+	e.rope = a.rope;
+	e.M = T;
+	e.q_dim = q_dim;
+	e.kv_dim = kv_dim;
+	e.head_dim = a.head_dim;
+	e.pos0 = a.pos0;
+	e.clip = a.clip;
+	e.range = a.range;
+	if constexpr (B)
+		e.bq = a.bq, e.bk = a.bk, e.bv = a.bv;
+	// q and k | v in one two-depth launch at width 256 (gemm8p_kernel): the two launches'
+	// tiles balanced over the chip instead of one round each (Llama-3B at T 4096: q 82 us
+	// at width 192 + k | v 115 us at 128)
+	const bool qkv1 = f.qkv1 && f.p8 && f.g16[PG_QKV] < 0 && q_dim % 256 == 0 && (2 * kv_dim) % 256 == 0;
+	// two GEMMs: q (K = dim over hi) and k | v from column q_dim (K = 2 dim over hi | lo, the
+	// B rows wrapping at dim)
+	if (a.small) {
+		const pf::BRowsPlain bm{qkv};
+		const int np = q_dim + 2 * kv_dim;
+		note_skinny(f, a.ks, 2 * a.ks);
+		TRY(launch_skinny(f, a.Xn, 2 * dim, T, dim, dim, bm, q_dim, a.ks, 0, np, a.skp, st));
+		TRY(launch_skinny(f, a.Xn, 2 * dim, T, 2 * dim, dim, bm, 2 * kv_dim, 2 * a.ks, q_dim, np, a.skp, st));
+		TRY(launch_skinny_reduce<false>(a.skp, a.ks, 2 * a.ks, q_dim, T, np, e, st));
+	} else if (f.split) { // q | k | v all over [hi | lo], Q stored [hi | lo]
+		pf::E16QKVt<true, B> es;
+		es.q = e.q, es.kc = e.kc, es.vc = e.vc, es.rope = e.rope, es.M = e.M, es.q_dim = e.q_dim;
+		es.kv_dim = e.kv_dim, es.head_dim = e.head_dim, es.pos0 = e.pos0, es.clip = e.clip;
+		es.range = e.range, es.q_lo = q_dim;
+		if constexpr (B)
+			es.bq = e.bq, es.bk = e.bk, es.bv = e.bv;
+		TRY(launch_plain(f, pick_bn(f, PG_QKV, T, q_dim + 2 * kv_dim, false), a.Xn, 2 * dim, T, 2 * dim, dim, qkv,
+		                 q_dim + 2 * kv_dim, es, st));
+	} else if (qkv1) { // one launch: the k | v tiles (K = 2 dim) first, then the q tiles (K = dim)
+		TRY((launch_g8p<pf::E16QKVt<false, B>, pf::BRowsPlain, 2, 2>(f, a.Xn, 2 * dim, T, dim, dim, pf::BRowsPlain{qkv},
+		                                                              q_dim + 2 * kv_dim, e, st, 0, q_dim, 2 * dim)));
+	} else {
+		TRY(launch_plain(f, pick_bn(f, PG_QKV, T, q_dim, false), a.Xn, 2 * dim, T, dim, dim, qkv, q_dim, e, st));
+		TRY(launch_plain(f, pick_bn(f, PG_QKV, T, 2 * kv_dim, false), a.Xn, 2 * dim, T, 2 * dim, dim, qkv, 2 * kv_dim, e,
+		                 st, q_dim));
+	}
+	return YALM_OK;
+}
+
+// X[t] += scale * A[t] . W^T over T rows (Wo: kind PG_WO, W2: PG_W2): A [T][sp K] f16 ([hi | lo]
+// in the split-operand form), W [N][K], X [.][N] f32. small / ks: pf_small and sk_ks(N, K, T).
+int enqueue_residual(const PfForms &f, int kind, const uint16_t *A, int T, int K, const void *w, int N, float *X,
+                     float scale, bool small, int ks, float *skp, hipStream_t st) {
+	pf::E16Residual e;
+	e.x = X;
+	e.ldx = N;
+	e.M = T;
+	e.scale = scale;
+	if (small) {
+		note_skinny(f, ks, ks);
+		TRY(launch_skinny(f, A, K, T, K, K, pf::BRowsPlain{one(w, N)}, N, ks, 0, N, skp, st));
+		return launch_skinny_reduce<false>(skp, ks, ks, N, T, N, e, st);
+	}
+	const int sp = f.split ? 2 : 1;
+	return launch_plain(f, pick_bn(f, kind, T, N, false), A, sp * K, T, sp * K, K, one(w, N), N, e, st);
+}
+
+// H[t] = f16(hscale * act(Xn[t] . W1^T) * (Xn[t] . W3^T)): Xn [T][sp dim], H [.][sp hidden]
 template <int ACT, bool SPLIT>
-int enqueue_glu_t(yalm_decoder_s *d, const yalm_block_weights &w, int T, float hscale, unsigned *range) {
-	const yalm_config &c = d->c;
-	const PfForms &f = d->pf_forms;
-	const int bn = pick_bn(f, PG_GLU, T, 2 * c.hidden_dim, true);
+int launch_glu_t(const PfForms &f, const uint16_t *Xn, int dim, int hidden, const void *w1, const void *w3, int T,
+                 float hscale, unsigned *range, uint16_t *H, hipStream_t st) {
+	const int bn = pick_bn(f, PG_GLU, T, 2 * hidden, true);
 	const int sp = SPLIT ? 2 : 1; // split-operand form: A = [hi | lo] (K = 2 dim), H rows [hi | lo]
 	pf::E16Glu<ACT, SPLIT> e;
-	e.h = d->pf.H;
-	e.ldh = c.hidden_dim * sp;
+	e.h = H;
+	e.ldh = hidden * sp;
 	e.M = T;
 	e.hscale = hscale;
 	e.range = range;
-	e.lo_off = SPLIT ? c.hidden_dim : 0;
-	pf::BRowsGlu<64> bm{(const uint16_t *)w.w1, (const uint16_t *)w.w3};
+	e.lo_off = SPLIT ? hidden : 0;
+	pf::BRowsGlu<64> bm{(const uint16_t *)w1, (const uint16_t *)w3};
 	if (bn == 256)
-		return launch_g16_t<pf::E16Glu<ACT, SPLIT>, pf::BRowsGlu<64>, 256, 2>(f, d->pf.Xn, sp * c.dim, T, sp * c.dim, c.dim,
-                                                                     bm, 2 * c.hidden_dim, e, d->stream);
+		return launch_g16_t<pf::E16Glu<ACT, SPLIT>, pf::BRowsGlu<64>, 256, 2>(f, Xn, sp * dim, T, sp * dim, dim, bm,
+		                                                                      2 * hidden, e, st);
 	if (bn == 128)
-		return launch_g16_t<pf::E16Glu<ACT, SPLIT>, pf::BRowsGlu<64>, 128, 4>(f, d->pf.Xn, sp * c.dim, T, sp * c.dim, c.dim,
-                                                                     bm, 2 * c.hidden_dim, e, d->stream);
+		return launch_g16_t<pf::E16Glu<ACT, SPLIT>, pf::BRowsGlu<64>, 128, 4>(f, Xn, sp * dim, T, sp * dim, dim, bm,
+		                                                                      2 * hidden, e, st);
 	set_err("prefill GLU GEMM: 2 x hidden_dim must divide by 128 (or by a forced width of 128 / 256)");
 	return YALM_ERR_UNSUPPORTED;
 }
 
+// small / ks: pf_small and sk_ks(2 hidden, dim, T)
 template <int ACT>
-int enqueue_glu(yalm_decoder_s *d, const yalm_block_weights &w, int T, float hscale, unsigned *range) {
-	return d->pf_forms.split ? enqueue_glu_t<ACT, true>(d, w, T, hscale, range)
-	                         : enqueue_glu_t<ACT, false>(d, w, T, hscale, range);
+int enqueue_glu_act(const PfForms &f, const uint16_t *Xn, int dim, int hidden, const void *w1, const void *w3, int T,
+                    float hscale, unsigned *range, uint16_t *H, bool small, int ks, float *skp, hipStream_t st) {
+	if (small) {
+		const pf::BRowsGlu<64> bm{(const uint16_t *)w1, (const uint16_t *)w3};
+		note_skinny(f, ks, ks);
+		TRY(launch_skinny(f, Xn, dim, T, dim, dim, bm, 2 * hidden, ks, 0, 2 * hidden, skp, st));
+		pf::E16Glu<ACT> e;
+		e.h = H, e.ldh = hidden, e.M = T, e.hscale = hscale, e.range = range;
+		return launch_skinny_reduce<true>(skp, ks, ks, 2 * hidden, T, 2 * hidden, e, st);
+	}
+	return f.split ? launch_glu_t<ACT, true>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, st)
+	               : launch_glu_t<ACT, false>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, st);
+}
+int enqueue_glu(const PfForms &f, int act, const uint16_t *Xn, int dim, int hidden, const void *w1, const void *w3,
+                int T, float hscale, unsigned *range, uint16_t *H, bool small, int ks, float *skp, hipStream_t st) {
+	return act == YALM_SILU ? enqueue_glu_act<1>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, small, ks, skp, st)
+	                        : enqueue_glu_act<0>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, small, ks, skp, st);
+}
+
+// The logits GEMM's per-tile (max, sum exp, target logit) and log p(target) per row: Xn [T][sp dim],
+// wcls [V][dim] f16, pmax / psum [T][ntiles] (ntiles = V / the tile width, at most V / 128)
+int enqueue_logprob(const PfForms &f, const uint16_t *Xn, int dim, const void *wcls, int V, const int *tgt, float *pmax,
+                    float *psum, float *tgt_logit, float *lp, int T, hipStream_t st) {
+	const int sp = f.split ? 2 : 1;
+	const int cls_bn = pick_bn(f, PG_CLS, T, V, false);
+	const int ntiles = cls_bn ? V / cls_bn : 1;
+	pf::E16Logits e;
+	e.pmax = pmax;
+	e.psum = psum;
+	e.tgt_logit = tgt_logit;
+	e.targets = tgt;
+	e.M = T;
+	e.ntiles = ntiles;
+	e.red = nullptr;
+	TRY(launch_plain(f, cls_bn, Xn, sp * dim, T, sp * dim, dim, one(wcls, V), V, e, st));
+	pf::logprob_kernel<<<T, 256, 0, st>>>(pmax, psum, tgt_logit, tgt, T, ntiles, lp);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
 }
 
 
@@ -703,31 +873,19 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	const int half = c.head_dim / 2;
 	pf::rope_table_kernel<<<(T * half + 255) / 256, 256, 0, st>>>(d->inv_freq, half, T, pos0, b.rope);
 	HIPCHK(hipGetLastError());
-	// GEMM widths are the same for every layer
-	const int bn_q = pick_bn(f, PG_QKV, T, q_dim, false);
-	const int bn_kv = pick_bn(f, PG_QKV, T, 2 * kv_dim, false);
-	// q and k | v in one two-depth launch at width 256 (gemm8p_kernel): the two launches'
-	// tiles balanced over the chip instead of one round each (Llama-3B at T 4096: q 82 us
-	// at width 192 + k | v 115 us at 128)
-	const bool qkv1 = f.qkv1 && f.p8 && f.g16[PG_QKV] < 0 && q_dim % 256 == 0 && (2 * kv_dim) % 256 == 0;
-	const int bn_wo = pick_bn(f, PG_WO, T, c.dim, false);
-	const int bn_w2 = pick_bn(f, PG_W2, T, c.dim, false);
-	// short prompts: split-K skinny GEMMs (the 256-row tiles would leave most CUs idle)
-	const int TP = 16 * ((T + 15) / 16);
-	const int ks_qkv = sk_pick_ks({{q_dim, c.dim, 1}, {2 * kv_dim, 2 * c.dim, 2}}, TP);
-	const int ks_wo = sk_pick_ks({{c.dim, q_dim, 1}}, TP);
-	const int ks_glu = sk_pick_ks({{2 * c.hidden_dim, c.dim, 1}}, TP);
-	const int ks_w2 = sk_pick_ks({{c.dim, c.hidden_dim, 1}}, TP);
+	// short prompts: split-K skinny GEMMs (pf_small)
+	const int ks_qkv = sk_ks_qkv(c.dim, q_dim, kv_dim, T);
+	const int ks_wo = sk_ks(c.dim, q_dim, T);
+	const int ks_glu = sk_ks(2 * c.hidden_dim, c.dim, T);
+	const int ks_w2 = sk_ks(c.dim, c.hidden_dim, T);
 	// (expert models: the attention half only; their FFN half runs the grouped large tiles at every T)
 	const bool moe = d->moe_E > 0;
-	const bool small = T <= SK_MAX_T && !f.no_skinny && !f.split && ks_qkv > 0 && ks_wo > 0 &&
-	                   (moe || (ks_glu > 0 && ks_w2 > 0));
+	const bool small = moe ? pf_small(f, T, {ks_qkv, ks_wo}) : pf_small(f, T, {ks_qkv, ks_wo, ks_glu, ks_w2});
 	// the split-operand precision form (yalm_set_prefill_precision): every activation operand
 	// [hi | lo] -- the normalised x of all three norms, Q, P (attention.h SPLIT), O and H --
 	// each GEMM over K = 2 x its depth with the B rows wrapping (prefill_gemm.h), so no operand
-	// carries an f16 rounding the reference's f32 lacks; sp = operand width factor
+	// carries an f16 rounding the reference's f32 lacks
 	const bool split = f.split;
-	const int sp = split ? 2 : 1;
 	const int bn_qkv_all = pick_bn(f, PG_QKV, T, q_dim + 2 * kv_dim, false);
 	for (int l = 0; l < c.n_layers; ++l) {
 		yalm_block_weights w = d->b[l];
@@ -764,52 +922,14 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			qkv.end[0] = q_dim;
 			qkv.end[1] = q_dim + kv_dim;
 			qkv.end[2] = q_dim + 2 * kv_dim;
-			// every QKV form over the epilogue with or without the q / k / v bias (Qwen2,
-			// yalm_decoder_set_qkv_bias): a compile-time flag, so an unbiased model runs the
-			// instantiations it always ran
-			auto qkv_gemms = [&](auto biased) -> int {
-				constexpr bool B = decltype(biased)::value;
-				pf::E16QKVt<false, B> e;
-				e.q = b.Q;
-				e.kc = w.key_cache;
-				e.vc = w.value_cache;
-				e.rope = b.rope;
-				e.M = T;
-				e.q_dim = q_dim;
-				e.kv_dim = kv_dim;
-				e.head_dim = c.head_dim;
-				e.pos0 = pos0;
-				e.clip = c.qkv_clip;
-				e.range = rg + RG_Q;
-				if constexpr (B)
-					e.bq = d->bq[l], e.bk = d->bk[l], e.bv = d->bv[l];
-				// QKV + clip + RoPE as two GEMMs: q (K = dim over hi) and k | v from column
-				// q_dim (K = 2 dim over hi | lo, the B rows wrapping at dim)
-				if (small) {
-					const pf::BRowsPlain bm{qkv};
-					const int np = q_dim + 2 * kv_dim;
-					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, c.dim, c.dim, bm, q_dim, ks_qkv, 0, np, b.skp, st));
-					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, bm, 2 * kv_dim, 2 * ks_qkv, q_dim, np, b.skp,
-					                  st));
-					TRY(launch_skinny_reduce<false>(b.skp, ks_qkv, 2 * ks_qkv, q_dim, T, np, e, st));
-				} else if (split) { // q | k | v all over [hi | lo], Q stored [hi | lo]
-					pf::E16QKVt<true, B> es;
-					es.q = e.q, es.kc = e.kc, es.vc = e.vc, es.rope = e.rope, es.M = e.M, es.q_dim = e.q_dim;
-					es.kv_dim = e.kv_dim, es.head_dim = e.head_dim, es.pos0 = e.pos0, es.clip = e.clip;
-					es.range = e.range, es.q_lo = q_dim;
-					if constexpr (B)
-						es.bq = e.bq, es.bk = e.bk, es.bv = e.bv;
-					TRY(launch_plain(f, bn_qkv_all, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, q_dim + 2 * kv_dim, es, st));
-				} else if (qkv1) { // one launch: the k | v tiles (K = 2 dim) first, then the q tiles (K = dim)
-					TRY((launch_g8p<pf::E16QKVt<false, B>, pf::BRowsPlain, 2, 2>(f, b.Xn, 2 * c.dim, T, c.dim, c.dim,
-					                                                              pf::BRowsPlain{qkv}, q_dim + 2 * kv_dim, e,
-					                                                              st, 0, q_dim, 2 * c.dim)));
-				} else {
-					TRY(launch_plain(f, bn_q, b.Xn, 2 * c.dim, T, c.dim, c.dim, qkv, q_dim, e, st));
-					TRY(launch_plain(f, bn_kv, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, 2 * kv_dim, e, st, q_dim));
-				}
-				return YALM_OK;
-			};
+			PfQkv qa{};
+			qa.Xn = b.Xn, qa.wq = w.wq, qa.wk = w.wk, qa.wv = w.wv, qa.rope = b.rope;
+			qa.Q = b.Q, qa.kc = (uint16_t *)w.key_cache, qa.vc = (uint16_t *)w.value_cache;
+			qa.range = rg + RG_Q, qa.skp = b.skp;
+			qa.dim = c.dim, qa.q_dim = q_dim, qa.kv_dim = kv_dim, qa.head_dim = c.head_dim, qa.T = T, qa.pos0 = pos0;
+			qa.clip = c.qkv_clip, qa.small = small, qa.ks = ks_qkv;
+			if (!d->bq.empty())
+				qa.bq = d->bq[l], qa.bk = d->bk[l], qa.bv = d->bv[l];
 			// a q / k normed model (Qwen3; never biased): every form leaves raw f32 q | k | v rows --
 			// the large tiles as ONE GEMM over [hi | lo] (the split form's launch; q too, so the
 			// fast form's Q comes from the more exact operand), the skinny path through its own
@@ -840,23 +960,11 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			if (!d->gq.empty())
 				TRY(qkv_normed());
 			else
-				TRY(d->bq.empty() ? qkv_gemms(std::false_type{}) : qkv_gemms(std::true_type{}));
+				TRY(d->bq.empty() ? enqueue_qkv<false>(f, qa, st) : enqueue_qkv<true>(f, qa, st));
 		}
 		TRY(launch_attn_prefill(b.Q, w.key_cache, w.value_cache, T, pos0, c.n_heads, c.n_kv_heads, c.head_dim, b.O,
 								st, split));
-		{
-			pf::E16Residual e;
-			e.x = b.X;
-			e.ldx = c.dim;
-			e.M = T;
-			if (small) {
-				TRY(launch_skinny(f, b.O, q_dim, T, q_dim, q_dim, pf::BRowsPlain{one(w.wo, c.dim)}, c.dim, ks_wo, 0, c.dim,
-				                  b.skp, st));
-				TRY(launch_skinny_reduce<false>(b.skp, ks_wo, ks_wo, c.dim, T, c.dim, e, st));
-			} else {
-				TRY(launch_plain(f, bn_wo, b.O, sp * q_dim, T, sp * q_dim, q_dim, one(w.wo, c.dim), c.dim, e, st));
-			}
-		}
+		TRY(enqueue_residual(f, PG_WO, b.O, T, q_dim, w.wo, c.dim, b.X, 1.0f, small, ks_wo, b.skp, st));
 		TRY(launch_rmsnorm(split, f, b.X, w.rms_ffn, c.dim, T, c.norm_eps, b.Xn, rg + RG_XFFN, st));
 		const float hscale = ldexpf(1.0f, -he);
 		if (moe) {
@@ -873,53 +981,14 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			TRY(enqueue_moe_ffn(f, a, st));
 			continue;
 		}
-		if (small) {
-			const pf::BRowsGlu<64> bm{(const uint16_t *)w.w1, (const uint16_t *)w.w3};
-			TRY(launch_skinny(f, b.Xn, c.dim, T, c.dim, c.dim, bm, 2 * c.hidden_dim, ks_glu, 0, 2 * c.hidden_dim, b.skp,
-			                  st));
-			if (c.act == YALM_SILU) {
-				pf::E16Glu<1> e;
-				e.h = b.H, e.ldh = c.hidden_dim, e.M = T, e.hscale = hscale, e.range = rg + RG_H;
-				TRY(launch_skinny_reduce<true>(b.skp, ks_glu, ks_glu, 2 * c.hidden_dim, T, 2 * c.hidden_dim, e, st));
-			} else {
-				pf::E16Glu<0> e;
-				e.h = b.H, e.ldh = c.hidden_dim, e.M = T, e.hscale = hscale, e.range = rg + RG_H;
-				TRY(launch_skinny_reduce<true>(b.skp, ks_glu, ks_glu, 2 * c.hidden_dim, T, 2 * c.hidden_dim, e, st));
-			}
-		} else {
-			TRY(c.act == YALM_SILU ? enqueue_glu<1>(d, w, T, hscale, rg + RG_H)
-								   : enqueue_glu<0>(d, w, T, hscale, rg + RG_H));
-		}
-		{
-			pf::E16Residual e;
-			e.x = b.X;
-			e.ldx = c.dim;
-			e.M = T;
-			e.scale = ldexpf(1.0f, he);
-			if (small) {
-				TRY(launch_skinny(f, b.H, c.hidden_dim, T, c.hidden_dim, c.hidden_dim, pf::BRowsPlain{one(w.w2, c.dim)},
-				                  c.dim, ks_w2, 0, c.dim, b.skp, st));
-				TRY(launch_skinny_reduce<false>(b.skp, ks_w2, ks_w2, c.dim, T, c.dim, e, st));
-			} else {
-				TRY(launch_plain(f, bn_w2, b.H, sp * c.hidden_dim, T, sp * c.hidden_dim, c.hidden_dim, one(w.w2, c.dim),
-								 c.dim, e, st));
-			}
-		}
+		TRY(enqueue_glu(f, c.act, b.Xn, c.dim, c.hidden_dim, w.w1, w.w3, T, hscale, rg + RG_H, b.H, small, ks_glu, b.skp,
+		                st));
+		TRY(enqueue_residual(f, PG_W2, b.H, T, c.hidden_dim, w.w2, c.dim, b.X, ldexpf(1.0f, he), small, ks_w2, b.skp, st));
 	}
 	if (!want_lp)
 		return YALM_OK;
 	TRY(launch_rmsnorm(split, f, b.X, d->rms_final, c.dim, T, c.norm_eps, b.Xn,
 	                   b.range + (size_t)c.n_layers * RG_N + RG_XATT, st));
-	const int cls_bn = pick_bn(f, PG_CLS, T, c.vocab_size, false);
-	const int ntiles = cls_bn ? c.vocab_size / cls_bn : 1;
-	pf::E16Logits e;
-	e.pmax = b.pmax;
-	e.psum = b.psum;
-	e.tgt_logit = b.tgt_logit;
-	e.targets = b.tgt;
-	e.M = T;
-	e.ntiles = ntiles;
-	e.red = nullptr;
 	const void *wcls = d->wcls;
 	if (fp8) {
 		const uint16_t *p[1];
@@ -931,10 +1000,7 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 		TRY((e4m3 ? dequant_e4m3_into : dequant_q4_into)(d->pf.wdq, {{d->wcls, (size_t)c.vocab_size, c.dim}}, p, st));
 		wcls = p[0];
 	}
-	TRY(launch_plain(f, cls_bn, b.Xn, sp * c.dim, T, sp * c.dim, c.dim, one(wcls, c.vocab_size), c.vocab_size, e, st));
-	pf::logprob_kernel<<<T, 256, 0, st>>>(b.pmax, b.psum, b.tgt_logit, b.tgt, T, ntiles, b.lp);
-	HIPCHK(hipGetLastError());
-	return YALM_OK;
+	return enqueue_logprob(f, b.Xn, c.dim, wcls, c.vocab_size, b.tgt, b.pmax, b.psum, b.tgt_logit, b.lp, T, st);
 }
 
 struct HostDev { // scoped device copy for the test hooks
@@ -1238,7 +1304,175 @@ extern "C" int yalm_attn_prefill_rows(uint16_t *o, int o_rows, const uint16_t *q
 	return YALM_OK;
 }
 
-extern "C" int yalm_attn_prefill(uint16_t *o, const uint16_t *q, const uint16_t *kc, const uint16_t *vc, int T,
+namespace {
+bool pow2(float s) {
+	int e;
+	return s > 0.0f && std::isfinite(s) && frexpf(s, &e) == 0.5f;
+}
+int hd_back(void *host, const HostDev &b, size_t bytes) {
+	HIPCHK(hipMemcpy(host, b.p, bytes, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+} // namespace
+
+extern "C" int yalm_prefill_stage(const yalm_prefill_stage_args *ap) {
+	ARGCHK(ap, "yalm_prefill_stage: bad argument");
+	const yalm_prefill_stage_args &a = *ap;
+	ARGCHK(a.T > 0 && a.cus >= 0 && (a.split == 0 || a.split == 1), "yalm_prefill_stage: T > 0, cus >= 0, split 0 or 1");
+	yalm_prefill_stage_info info{};
+	PfForms f = g_test_forms; // a test hook: the forms set by yalm_set_prefill_forms(NULL, ...)
+	f.split = a.split != 0;
+	f.cus = a.cus;
+	f.info = &info;
+	const int T = a.T, sp = a.split ? 2 : 1;
+	const size_t TP = (size_t)16 * ((T + 15) / 16);
+	const size_t lim = (size_t)1 << 32; // the tile kernels address A rows by 32-bit element offsets
+	HostDev dA, dW[3], dB[3], dO[4], dR, dS, dT;
+	auto up_range = [&]() -> int { return hd(dR, a.range, 4); };
+	switch (a.stage) {
+	case YALM_PF_STAGE_NORM: {
+		ARGCHK(a.x && a.normw && a.xn && a.range, "yalm_prefill_stage: NORM needs x, normw, xn and range");
+		ARGCHK(a.dim > 0 && a.dim % pf::BN == 0, "yalm_prefill_stage: dim must be a multiple of 128");
+		ARGCHK(a.xn_rows >= T, "yalm_prefill_stage: xn_rows >= T");
+		const size_t xb = (size_t)a.xn_rows * sp * a.dim * 2;
+		TRY(hd(dA, a.x, (size_t)T * a.dim * 4));
+		TRY(hd(dW[0], a.normw, (size_t)a.dim * 4));
+		TRY(hd(dO[0], a.xn, xb));
+		TRY(up_range());
+		TRY(launch_rmsnorm(a.split != 0, f, (const float *)dA.p, (const float *)dW[0].p, a.dim, T, a.eps,
+		                   (uint16_t *)dO[0].p, (unsigned *)dR.p, nullptr));
+		HIPCHK(hipDeviceSynchronize());
+		TRY(hd_back(a.xn, dO[0], xb));
+		break;
+	}
+	case YALM_PF_STAGE_QKV: {
+		ARGCHK(a.a && a.wq && a.wk && a.wv && a.rope && a.q && a.kc && a.vc && a.range,
+		       "yalm_prefill_stage: QKV needs a, wq, wk, wv, rope, q, kc, vc and range");
+		ARGCHK((a.bq && a.bk && a.bv) || (!a.bq && !a.bk && !a.bv), "yalm_prefill_stage: bq, bk and bv, or none");
+		ARGCHK(a.head_dim == 64 || a.head_dim == 128, "yalm_prefill_stage: head_dim must be 64 or 128");
+		ARGCHK(a.n_heads > 0 && a.n_kv_heads > 0 && a.pos0 >= 0, "yalm_prefill_stage: bad argument");
+		const int q_dim = a.n_heads * a.head_dim, kv_dim = a.n_kv_heads * a.head_dim, np = q_dim + 2 * kv_dim;
+		ARGCHK(a.dim > 0 && a.dim % pf::BK == 0 && q_dim % pf::BN == 0 && kv_dim % pf::BN == 0,
+		       "yalm_prefill_stage: dim must be a multiple of 64, q and kv dims of 128");
+		ARGCHK((long long)a.cache_rows >= (long long)a.pos0 + T, "yalm_prefill_stage: cache_rows >= pos0 + T");
+		ARGCHK(a.q_rows >= T, "yalm_prefill_stage: q_rows >= T");
+		ARGCHK((size_t)T * 2 * a.dim < lim, "yalm_prefill_stage: T x row length exceeds 2^32 elements");
+		const size_t qb = (size_t)a.q_rows * sp * q_dim * 2, cb = (size_t)a.cache_rows * kv_dim * 2;
+		PfQkv qa{};
+		qa.ks = sk_ks_qkv(a.dim, q_dim, kv_dim, T);
+		qa.small = pf_small(f, T, {qa.ks});
+		TRY(hd(dA, a.a, (size_t)T * 2 * a.dim * 2));
+		TRY(hd(dW[0], a.wq, (size_t)q_dim * a.dim * 2));
+		TRY(hd(dW[1], a.wk, (size_t)kv_dim * a.dim * 2));
+		TRY(hd(dW[2], a.wv, (size_t)kv_dim * a.dim * 2));
+		TRY(hd(dT, a.rope, (size_t)T * a.head_dim * 4));
+		if (a.bq) {
+			TRY(hd(dB[0], a.bq, (size_t)q_dim * 4));
+			TRY(hd(dB[1], a.bk, (size_t)kv_dim * 4));
+			TRY(hd(dB[2], a.bv, (size_t)kv_dim * 4));
+		}
+		TRY(hd(dO[0], a.q, qb));
+		TRY(hd(dO[1], a.kc, cb));
+		TRY(hd(dO[2], a.vc, cb));
+		TRY(up_range());
+		if (qa.small)
+			TRY(hd(dS, nullptr, (size_t)2 * qa.ks * TP * np * 4));
+		qa.Xn = (const uint16_t *)dA.p, qa.wq = dW[0].p, qa.wk = dW[1].p, qa.wv = dW[2].p;
+		qa.bq = (const float *)dB[0].p, qa.bk = (const float *)dB[1].p, qa.bv = (const float *)dB[2].p;
+		qa.rope = (const float *)dT.p, qa.Q = (uint16_t *)dO[0].p, qa.kc = (uint16_t *)dO[1].p, qa.vc = (uint16_t *)dO[2].p;
+		qa.range = (unsigned *)dR.p, qa.skp = (float *)dS.p;
+		qa.dim = a.dim, qa.q_dim = q_dim, qa.kv_dim = kv_dim, qa.head_dim = a.head_dim, qa.T = T, qa.pos0 = a.pos0;
+		qa.clip = a.clip;
+		TRY(a.bq ? enqueue_qkv<true>(f, qa, nullptr) : enqueue_qkv<false>(f, qa, nullptr));
+		HIPCHK(hipDeviceSynchronize());
+		TRY(hd_back(a.q, dO[0], qb));
+		TRY(hd_back(a.kc, dO[1], cb));
+		TRY(hd_back(a.vc, dO[2], cb));
+		break;
+	}
+	case YALM_PF_STAGE_RESIDUAL: {
+		ARGCHK(a.a && a.w && a.xres, "yalm_prefill_stage: RESIDUAL needs a, w and xres");
+		ARGCHK(a.kind == YALM_PF_WO || a.kind == YALM_PF_W2, "yalm_prefill_stage: kind must be YALM_PF_WO or YALM_PF_W2");
+		ARGCHK(a.n > 0 && a.n % pf::BN == 0 && a.k > 0 && a.k % pf::BK == 0,
+		       "yalm_prefill_stage: n must be a multiple of 128, k of 64");
+		ARGCHK(a.x_rows >= T, "yalm_prefill_stage: x_rows >= T");
+		ARGCHK(pow2(a.scale), "yalm_prefill_stage: scale must be a power of two");
+		ARGCHK((size_t)T * sp * a.k < lim, "yalm_prefill_stage: T x row length exceeds 2^32 elements");
+		const size_t xb = (size_t)a.x_rows * a.n * 4;
+		const int ks = sk_ks(a.n, a.k, T);
+		const bool small = pf_small(f, T, {ks});
+		TRY(hd(dA, a.a, (size_t)T * sp * a.k * 2));
+		TRY(hd(dW[0], a.w, (size_t)a.n * a.k * 2));
+		TRY(hd(dO[0], a.xres, xb));
+		if (small)
+			TRY(hd(dS, nullptr, (size_t)ks * TP * a.n * 4));
+		TRY(enqueue_residual(f, a.kind, (const uint16_t *)dA.p, T, a.k, dW[0].p, a.n, (float *)dO[0].p, a.scale, small, ks,
+		                     (float *)dS.p, nullptr));
+		HIPCHK(hipDeviceSynchronize());
+		TRY(hd_back(a.xres, dO[0], xb));
+		break;
+	}
+	case YALM_PF_STAGE_GLU: {
+		ARGCHK(a.a && a.w1 && a.w3 && a.h && a.range, "yalm_prefill_stage: GLU needs a, w1, w3, h and range");
+		ARGCHK(a.act == YALM_SILU || a.act == YALM_GELU, "yalm_prefill_stage: bad activation");
+		ARGCHK(a.hidden > 0 && a.hidden % pf::BN == 0 && a.dim > 0 && a.dim % pf::BK == 0,
+		       "yalm_prefill_stage: hidden must be a multiple of 128, dim of 64");
+		ARGCHK(a.h_rows >= T, "yalm_prefill_stage: h_rows >= T");
+		ARGCHK(pow2(a.hscale), "yalm_prefill_stage: hscale must be a power of two");
+		ARGCHK((size_t)T * sp * a.dim < lim, "yalm_prefill_stage: T x row length exceeds 2^32 elements");
+		const size_t hb = (size_t)a.h_rows * sp * a.hidden * 2;
+		const int ks = sk_ks(2 * a.hidden, a.dim, T);
+		const bool small = pf_small(f, T, {ks});
+		TRY(hd(dA, a.a, (size_t)T * sp * a.dim * 2));
+		TRY(hd(dW[0], a.w1, (size_t)a.hidden * a.dim * 2));
+		TRY(hd(dW[1], a.w3, (size_t)a.hidden * a.dim * 2));
+		TRY(hd(dO[0], a.h, hb));
+		TRY(up_range());
+		if (small)
+			TRY(hd(dS, nullptr, (size_t)ks * TP * 2 * a.hidden * 4));
+		TRY(enqueue_glu(f, a.act, (const uint16_t *)dA.p, a.dim, a.hidden, dW[0].p, dW[1].p, T, a.hscale, (unsigned *)dR.p,
+		                (uint16_t *)dO[0].p, small, ks, (float *)dS.p, nullptr));
+		HIPCHK(hipDeviceSynchronize());
+		TRY(hd_back(a.h, dO[0], hb));
+		break;
+	}
+	case YALM_PF_STAGE_LOGPROB: {
+		ARGCHK(a.a && a.wcls && a.targets && a.lp && a.pmax && a.psum && a.tgt_logit,
+		       "yalm_prefill_stage: LOGPROB needs a, wcls, targets, lp, pmax, psum and tgt_logit");
+		ARGCHK(a.vocab > 0 && a.vocab % pf::BN == 0 && a.dim > 0 && a.dim % pf::BK == 0,
+		       "yalm_prefill_stage: vocab must be a multiple of 128, dim of 64");
+		for (int t = 0; t < T; ++t)
+			ARGCHK(a.targets[t] >= -1 && a.targets[t] < a.vocab, "yalm_prefill_stage: target out of range");
+		ARGCHK((size_t)T * sp * a.dim < lim, "yalm_prefill_stage: T x row length exceeds 2^32 elements");
+		const size_t pb = (size_t)T * (a.vocab / pf::BN) * 4, tb = (size_t)T * 4;
+		TRY(hd(dA, a.a, (size_t)T * sp * a.dim * 2));
+		TRY(hd(dW[0], a.wcls, (size_t)a.vocab * a.dim * 2));
+		TRY(hd(dT, a.targets, tb));
+		TRY(hd(dO[0], a.pmax, pb));
+		TRY(hd(dO[1], a.psum, pb));
+		TRY(hd(dO[2], a.tgt_logit, tb));
+		TRY(hd(dO[3], a.lp, tb));
+		TRY(enqueue_logprob(f, (const uint16_t *)dA.p, a.dim, dW[0].p, a.vocab, (const int *)dT.p, (float *)dO[0].p,
+		                    (float *)dO[1].p, (float *)dO[2].p, (float *)dO[3].p, T, nullptr));
+		HIPCHK(hipDeviceSynchronize());
+		TRY(hd_back(a.pmax, dO[0], pb));
+		TRY(hd_back(a.psum, dO[1], pb));
+		TRY(hd_back(a.tgt_logit, dO[2], tb));
+		TRY(hd_back(a.lp, dO[3], tb));
+		break;
+	}
+	default:
+		set_err("yalm_prefill_stage: unknown stage");
+		return YALM_ERR_ARG;
+	}
+	if (dR.p)
+		TRY(hd_back(a.range, dR, 4));
+	if (a.info)
+		*a.info = info;
+	return YALM_OK;
+}
+
+extern "C" int yalm_attn_prefill(uint16_t *o, const uint16_t *q,const uint16_t *kc, const uint16_t *vc, int T,
                                  int pos0, int n_heads, int n_kv_heads, int head_dim) {
 	ARGCHK(T > 0 && pos0 >= 0, "yalm_attn_prefill: bad argument");
 	return yalm_attn_prefill_rows(o, T, q, kc, vc, pos0 + T, T, pos0, n_heads, n_kv_heads, head_dim, 0);

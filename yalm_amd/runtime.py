@@ -114,6 +114,30 @@ class GemvArgs(ctypes.Structure):
                 + [("q_len", c_int), ("raw_len", c_int)] + [(n, c_void_p) for n in ("bq", "bk", "bv")])
 
 
+class PrefillStageInfo(ctypes.Structure):
+    """yalm_prefill_stage_info: the path one prefill stage took."""
+
+    _fields_ = [(n, c_int) for n in ("skinny", "ks", "ks2", "n_gemm")] + [("bn", c_int * 2)] + [
+        (n, c_int) for n in ("eight_phase", "two_depth", "tiles", "grid", "persistent", "norm_nv")]
+
+
+class PrefillStageArgs(ctypes.Structure):
+    """yalm_prefill_stage_args: one stage of the prefill on host arrays (yalm_prefill_stage)."""
+
+    _fields_ = ([(n, c_int) for n in ("stage", "T", "cus", "split", "dim")]
+                + [("a", c_void_p), ("range", c_void_p), ("info", ctypes.POINTER(PrefillStageInfo))]
+                + [("x", c_void_p), ("normw", c_void_p), ("eps", c_float), ("xn", c_void_p), ("xn_rows", c_int)]
+                + [(n, c_int) for n in ("n_heads", "n_kv_heads", "head_dim", "pos0", "q_rows", "cache_rows")]
+                + [("clip", c_float)]
+                + [(n, c_void_p) for n in ("wq", "wk", "wv", "rope", "bq", "bk", "bv", "q", "kc", "vc")]
+                + [(n, c_int) for n in ("kind", "n", "k", "x_rows")]
+                + [("w", c_void_p), ("scale", c_float), ("xres", c_void_p)]
+                + [(n, c_int) for n in ("hidden", "act", "h_rows")]
+                + [("w1", c_void_p), ("w3", c_void_p), ("hscale", c_float), ("h", c_void_p)]
+                + [("vocab", c_int)]
+                + [(n, c_void_p) for n in ("wcls", "targets", "lp", "pmax", "psum", "tgt_logit")])
+
+
 class RopeScaling(ctypes.Structure):
     """yalm_rope_scaling: type 0 none, 1 llama3."""
 
@@ -232,6 +256,7 @@ _sig("yalm_rows_plan", c_int, [c_int] * 5 + [ctypes.POINTER(c_int)] * 4 + [ctype
 _sig("yalm_matmul_rows", c_int, [c_void_p] * 5 + [c_float] + [c_int] * 8)
 _sig("yalm_gemv_plan", c_int, [c_int] * 11 + [ctypes.POINTER(GemvGeometry)])
 _sig("yalm_gemv_one", c_int, [ctypes.POINTER(GemvArgs)])
+_sig("yalm_prefill_stage", c_int, [ctypes.POINTER(PrefillStageArgs)])
 _sig("yalm_batch_create", c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)])
 _sig("yalm_batch_destroy", c_int, [c_void_p])
 _sig("yalm_batch_load", c_int, [c_void_p, c_int, c_int])
@@ -264,7 +289,7 @@ EXPORTED = [
     "yalm_decoder_set_qk_norm",
     "yalm_rows_plan", "yalm_matmul_rows",
     "yalm_gemv_plan", "yalm_gemv_one",
-    "yalm_attn_prefill_rows",
+    "yalm_attn_prefill_rows", "yalm_prefill_stage",
     "yalm_batch_create", "yalm_batch_destroy", "yalm_batch_load", "yalm_batch_forward",
     "yalm_batch_generate_greedy", "yalm_batch_generate_sampled", "yalm_batch_state", "yalm_batch_set_launch",
     "yalm_batch_buffers",
@@ -636,6 +661,55 @@ def attn_prefill_rows(o, q, kc, vc, T, pos0, n_heads, n_kv_heads, head_dim, spli
     check(lib.yalm_attn_prefill_rows(_ptr(o), o.shape[0], _ptr(q), _ptr(kc), _ptr(vc), kc.shape[0], T, pos0, n_heads,
                                      n_kv_heads, head_dim, int(bool(split))))
     return o
+
+
+PF_NORM, PF_QKV, PF_RESIDUAL, PF_GLU, PF_LOGPROB = range(5)  # yalm_prefill_stage stages
+PF_WO, PF_W2 = 1, 3  # ... and the RESIDUAL stage's forms kinds
+_PF_INT = ("T", "cus", "split", "dim", "xn_rows", "n_heads", "n_kv_heads", "head_dim", "pos0", "q_rows", "cache_rows",
+           "kind", "n", "k", "x_rows", "hidden", "act", "h_rows", "vocab")
+_PF_FLOAT = ("eps", "clip", "scale", "hscale")
+_PF_IN = dict(a=np.uint16, x=np.float32, normw=np.float32, wq=np.uint16, wk=np.uint16, wv=np.uint16, rope=np.float32,
+              bq=np.float32, bk=np.float32, bv=np.float32, w=np.uint16, w1=np.uint16, w3=np.uint16, wcls=np.uint16,
+              targets=np.int32)
+_PF_OUT = dict(range=np.uint32, xn=np.uint16, q=np.uint16, kc=np.uint16, vc=np.uint16, xres=np.float32, h=np.uint16,
+               lp=np.float32, pmax=np.float32, psum=np.float32, tgt_logit=np.float32)
+
+
+def prefill_stage(stage: int, **kw):
+    """One stage of the prefill through the function the prefill itself calls (yalm_prefill_stage),
+    under the forms of set_gemm_forms. Keywords are the fields of yalm_prefill_stage_args: scalars,
+    read-only arrays (f16 operands as uint16 bits or float16) and the arrays the stage may write
+    (range, xn, q, kc, vc, xres, h, lp, pmax, psum, tgt_logit), given as they stand before the launch.
+    Returns (out, info): copies of the writable arrays after the launch under the same names, and
+    the path taken as a dict. The arguments are not written."""
+    a, keep, out = PrefillStageArgs(), [], {}
+    a.stage = stage
+    for name, v in kw.items():
+        if v is None:
+            continue
+        if name in _PF_INT:
+            setattr(a, name, int(v))
+        elif name in _PF_FLOAT:
+            setattr(a, name, float(v))
+        elif name in _PF_IN:
+            v = np.asarray(v)
+            v = v.view(np.uint16) if v.dtype == np.float16 else v
+            v = np.ascontiguousarray(v, dtype=_PF_IN[name])
+            keep.append(v)
+            setattr(a, name, _ptr(v))
+        elif name in _PF_OUT:
+            v = np.asarray(v)
+            v = v.view(np.uint16) if v.dtype == np.float16 else v
+            out[name] = np.array(v, dtype=_PF_OUT[name], order="C", copy=True)
+            setattr(a, name, _ptr(out[name]))
+        else:
+            raise TypeError(f"prefill_stage: unknown argument {name}")
+    info = PrefillStageInfo()
+    a.info = ctypes.pointer(info)
+    check(lib.yalm_prefill_stage(ctypes.byref(a)))
+    d = {k: int(getattr(info, k)) for k, _ in PrefillStageInfo._fields_ if k != "bn"}
+    d["bn"] = (int(info.bn[0]), int(info.bn[1]))
+    return out, d
 
 
 # ------------------------------------------------------------- model + decoder
