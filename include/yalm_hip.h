@@ -207,6 +207,39 @@ typedef struct yalm_sampling {
  * (yalm_decoder_create_tp / _tp_ipc): their vocabulary is sharded over the ranks. */
 int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
                           const float *uniforms, int *out_tokens);
+/* Repetition, frequency and presence penalties and min-p on top of the rule above. The history
+ * of a step is the caller's context, then the call's `token`, then every token the call has
+ * produced so far (the last of them is the token being fed); the window is its last
+ * min(window, length) tokens and c_i the number of times token i occurs in the window. Every
+ * logit with c_i > 0 is replaced, in f32 with one rounding per operation and no contraction, by
+ *   l'_i = (l_i > 0 ? l_i / repetition : l_i * repetition) - (frequency * (float)c_i + presence)
+ * (a NaN stays NaN); all other logits are untouched. The rule above then runs on these logits as
+ * it is written: m, q_i, the order, top-k, top-p (its target still from S_k). min_p: with
+ * qmin = (uint64) ceil((double)min_p * 2^40) a token is kept only if top-k / top-p keep it and
+ * q_i >= qmin; the first-maximum has q = 2^40 and always stays, equal logits have equal q, so
+ * the kept set is still a prefix of the order; S and the draw are taken over it.
+ * repetition = 1, frequency = presence = 0, min_p = 0 (or window = 0 with min_p = 0) is the
+ * plain rule bit for bit. */
+typedef struct yalm_penalties {
+	float repetition; /* > 0, finite; 1 = off */
+	float frequency;  /* finite; 0 = off */
+	float presence;   /* finite; 0 = off */
+	float min_p;      /* in [0, 1]; 0 = off */
+	int window;       /* 0 .. 1024: how many of the most recent history tokens count; 0 = penalties off */
+} yalm_penalties;
+/* yalm_generate_sampled with the penalties p: the same launch count (yalm_graph_kernels mode 4
+ * == mode 3), only the tokens leave the device, and the logits yalm_get_logits reads afterwards
+ * are the forward's (the kernel patches at most 1024 of them in place and stores them back).
+ * context: the n_context host tokens that precede `token`, oldest first (may be NULL with
+ * n_context 0); only its last `window` tokens are uploaded, once per call. Scope and
+ * continuation as yalm_generate_sampled. YALM_ERR_ARG: that call's, and repetition <= 0 or not
+ * finite, frequency or presence not finite, min_p outside [0, 1], window outside 0 .. 1024,
+ * n_context < 0, a context token outside the vocabulary. The speculative sampled loops and the
+ * batch keep the plain rule: a row's history would depend on which drafts are accepted, and a
+ * batch row has no context argument. */
+int yalm_generate_sampled_ex(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
+                             const yalm_penalties *p, const int *context, int n_context, const float *uniforms,
+                             int *out_tokens);
 /* Launch-only variant for benchmarking: enqueue n_steps greedy steps
  * continuing from the decoder's device-resident token/pos; no sync. */
 int yalm_enqueue_greedy(yalm_decoder d, int n_steps);
@@ -239,7 +272,8 @@ int yalm_get_logits(yalm_decoder d, float *host);
  * timed separately and subtracted), 10 = the sampling launch of yalm_generate_sampled on
  * the decoder's current logits, with the parameters of the last such call (before any:
  * temperature 1, no truncation) and its first uniform; it commits into a scratch step
- * state, not the decoder's; 11 = the q / k norm launch (yalm_decoder_set_qk_norm, which it
+ * state, not the decoder's; 15 = the same for yalm_generate_sampled_ex, with the penalties of
+ * the last such call over the context it uploaded; 11 = the q / k norm launch (yalm_decoder_set_qk_norm, which it
  * needs) on what the last QKV launch left; 12 / 13 = the draw and the accept launch of a 4-row
  * sampled speculative step, 14 = the verify launch of a greedy one, on the rows' current logits
  * and a scratch step state (decoders with a multi-row form). Used by bench.py for the roofline of the
@@ -258,7 +292,7 @@ int yalm_stream_envelope(size_t bytes, int iters, float *avg_ms);
  * Drops captured graphs (re-captured on next use). Tuning/ablation hook. */
 int yalm_set_gemv_config(yalm_decoder d, int kind, int threads, int unroll, int gpw);
 /* Kernel launches per forward of graph `mode` (0 = HYDRATE, 1 = OUTPUT_LOGITS, 2 = the
- * device greedy step, 3 = the device sampled step of yalm_generate_sampled): *kernels = kernel nodes of the captured per-token hipGraph (RCCL
+ * device greedy step, 3 = the device sampled step of yalm_generate_sampled, 4 = that of yalm_generate_sampled_ex): *kernels = kernel nodes of the captured per-token hipGraph (RCCL
  * collectives count as the kernels they capture), *nodes (may be NULL) = all nodes. Test
  * and measurement hook (tensor parallelism adds no exchange launches over IPC). */
 int yalm_graph_kernels(yalm_decoder d, int mode, int *kernels, int *nodes);
@@ -819,6 +853,12 @@ int yalm_argmax(const float *logits, int n, int n_shards, int *out);
  * may be NULL): the q_i the kernel used. */
 int yalm_sample(const float *logits, int n, const yalm_sampling *s, const float *uniforms, int n_draws,
                 int *out_tokens, int *kept, uint64_t *weights_out);
+/* The same for yalm_generate_sampled_ex: the launch of its kernel on host logits with the
+ * penalties p over the host history (n_history tokens, oldest first, may be NULL with 0; every
+ * token in [0, n)); all draws see the same history. logits_after (n floats, may be NULL): the
+ * device buffer after the launches, bit for bit the input. Argument errors as the call's. */
+int yalm_sample_ex(const float *logits, int n, const yalm_sampling *s, const yalm_penalties *p, const int *history,
+                   int n_history, const float *uniforms, int n_draws, int *out, float *logits_after);
 
 /* Prefill building blocks (host pointers, synchronous):
  * c[M][N] f32 = a[M][K] f16 · w[N][K]^T f16 (the MFMA GEMM; N % 128 == 0, K % 64 == 0). */

@@ -52,7 +52,8 @@ enum { GK_QKV = 0, GK_WO = 1, GK_GLU = 2, GK_W2 = 3, GK_CLS = 4, GK_N = 5 };
 enum {
 	KID_QKV = 0, KID_ATTN = 1, KID_WO = 2, KID_GLU = 3, KID_W2 = 4, KID_CLS = 5, KID_EXCHANGE = 6, KID_ATTN_WO = 8,
 	KID_ROUTER = 9, KID_SAMPLE = 10, KID_QK_NORM = 11, KID_SPEC_SAMPLE = 12, KID_SPEC_ACCEPT = 13, KID_SPEC_VERIFY = 14,
-	KID_LAST = KID_SPEC_VERIFY
+	KID_SAMPLE_PEN = 15,
+	KID_LAST = KID_SAMPLE_PEN
 };
 
 int device_cu_count();
@@ -120,7 +121,7 @@ struct PfForms {
 PfForms pf_forms_default(); // prefill.hip: the production forms (A/B build: YALM_PF_FORMS)
 
 // ------------------------------------------------------------------ decoder
-enum { GRAPH_HYDRATE = 0, GRAPH_LOGITS = 1, GRAPH_GREEDY = 2, GRAPH_SAMPLED = 3, N_GRAPHS = 4 };
+enum { GRAPH_HYDRATE = 0, GRAPH_LOGITS = 1, GRAPH_GREEDY = 2, GRAPH_SAMPLED = 3, GRAPH_PENALISED = 4, N_GRAPHS = 5 };
 
 struct yalm_decoder_s {
 	yalm_config c{};
@@ -140,6 +141,9 @@ struct yalm_decoder_s {
 	struct SampleParams *smp_params = nullptr;
 	float *smp_u = nullptr;          // [tokens_cap], one consumed per step (index StepState::n_gen)
 	StepState *smp_step = nullptr;   // yalm_time_kernel id 10 commits here, not into the decode state
+	// yalm_generate_sampled_ex: the call's penalties and context length, and the tail of its context
+	struct PenaltyState *pen_state = nullptr;
+	int *pen_ctx = nullptr;          // [SMP_WINDOW]
 	float *logits_pinned = nullptr;
 	std::vector<void *> dev_allocs;
 	hipGraph_t graph[N_GRAPHS] = {};

@@ -27,6 +27,18 @@
 // digit's crossing bin to a list in LDS; when they fit (1024), its third pass and the top-p select
 // after a top-k select read the list in the place of the logits. top_k == 0 and top_p == 1 skip the
 // selects: two passes after the maximum.
+//
+// Penalties and min-p (sample_pen_kernel, yalm_generate_sampled_ex): the rule above on logits
+// of which the at most 1024 whose token occurs in the history window were replaced by
+//   l' = (l > 0 ? l / repetition : l * repetition) - (frequency * c + presence),
+// c the token's count in the window, each operation one f32 rounding; the kept set is then cut
+// to q_i >= qmin = ceil((double)min_p * 2^40) (q is monotone in the key, so the kept set stays a
+// prefix of the order and a plateau stays whole). The passes are not taught about any of it:
+// thread t takes window slot t, the window lies in LDS (over hw, idle until the first select),
+// every thread counts its token by scanning the window with 16-byte LDS reads, and the thread
+// of a token's first slot patches logits[token] in place, keeps (token, l) in two registers
+// through the unchanged passes, and stores l back once the token is drawn: the logits buffer
+// leaves the launch as the forward wrote it. min-p is one comparison in the draw's weight.
 #pragma once
 
 #include <float.h>
@@ -42,12 +54,24 @@ struct SampleParams {
 	float top_p;
 };
 
+// layout of yalm_penalties (include/yalm_hip.h), then what the step needs of the call: all read
+// from device memory, like SampleParams
+struct PenaltyParams {
+	float repetition, frequency, presence, min_p;
+	int window;
+};
+struct PenaltyState {
+	PenaltyParams p;
+	int n_ctx; // tokens in the call's device context: the tail of the caller's context, then the call's first token
+};
+
 constexpr int SMP_THREADS = 1024;
 constexpr int SMP_SPAN = 4 * SMP_THREADS;
 constexpr int SMP_MAX_N = 131072;
 constexpr int SMP_MAX_SPANS = SMP_MAX_N / SMP_SPAN;
 constexpr int SMP_BINS = 4096;
 constexpr int SMP_CAND = 1024; // candidate list: the elements at or above the first digit's crossing bin
+constexpr int SMP_WINDOW = SMP_THREADS; // penalty window: one history token per thread
 
 struct SampleShared {
 	unsigned long long hw[SMP_BINS]; // q per key digit
@@ -358,10 +382,11 @@ struct SampleDraw {
 
 // The rule's draw from logits[0, n), n <= SMP_MAX_N, with the uniform u, after smp_first_max on
 // the same logits. sh is this workgroup's alone. VEC: logits is 16-byte aligned. Called by all
-// threads; every thread gets the result.
-template <bool VEC>
+// threads; every thread gets the result. MINP: only the kept elements with q >= qmin are drawn
+// from (kept still counts what top-k / top-p keep).
+template <bool VEC, bool MINP = false>
 __device__ __forceinline__ SampleDraw sample_row(const float *__restrict__ logits, int n, const SampleParams prm,
-                                                 float u, SampleShared &sh) {
+                                                 float u, SampleShared &sh, unsigned long long qmin = 0ull) {
 	const float m = sh.m, T = prm.temperature, top_p = prm.top_p;
 	const int amax = sh.amax, top_k = prm.top_k;
 	// the kept set {key > K or (key == K and i <= istar)}; everything to begin with
@@ -416,7 +441,10 @@ __device__ __forceinline__ SampleDraw sample_row(const float *__restrict__ logit
 	if (!empty) {
 		auto val = [&](int i, float l) {
 			const unsigned key = smp_key(l);
-			return key > K || (key == K && i <= istar) ? smp_q(l, m, T) : 0ull;
+			if (!(key > K || (key == K && i <= istar)))
+				return 0ull;
+			const unsigned long long q = smp_q(l, m, T);
+			return !MINP || q >= qmin ? q : 0ull;
 		};
 		const unsigned long long S = smp_span_sums<VEC>(logits, n, val, sh);
 		if (S > 0) {
@@ -449,6 +477,95 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float *__rest
 		    logits, n, [&](int i, float l) { weights_out[i] = smp_q(l, m, T); }, [](int) {});
 	const SampleDraw r = sample_row<true>(logits, n, SampleParams{T, top_k, top_p}, u, sh);
 	if (threadIdx.x == 0) {
+		if (kept_out && gen >= 0 && gen < cap)
+			kept_out[gen] = (int)r.kept;
+		argmax_commit(st, r.token, tokens_out, cap);
+	}
+}
+
+// The count of `tok` in win[0, W) (W <= SMP_WINDOW, padded with -1 to a multiple of 4) and
+// whether slot t is its first occurrence: 16-byte LDS reads, the same address in every lane.
+__device__ __forceinline__ int smp_window_count(const int *win, int W, int tok, int t, bool &first) {
+	typedef int int4_t __attribute__((ext_vector_type(4)));
+	int c = 0, before = 0;
+	for (int j = 0; j < W; j += 4) {
+		const int4_t v = *(const int4_t *)(win + j);
+#pragma unroll
+		for (int e = 0; e < 4; ++e) {
+			const int eq = v[e] == tok ? 1 : 0;
+			c += eq;
+			before += j + e < t ? eq : 0;
+		}
+	}
+	first = before == 0;
+	return c;
+}
+
+// sample_kernel with the penalties of `pen` on the history window and min-p. The history of the
+// step is ctx[0, pen->n_ctx) then, with `produced`, the st->n_gen tokens the call has committed
+// to tokens_out (the last of them is the token being fed); its last min(window, length) tokens
+// count. logits is read and written: patched, drawn from, restored. kept_out as sample_kernel's.
+__global__ __launch_bounds__(SMP_THREADS) void sample_pen_kernel(float *logits, int n,
+                                                                 const SampleParams *__restrict__ prm,
+                                                                 const PenaltyState *__restrict__ pen,
+                                                                 const int *__restrict__ ctx, bool produced,
+                                                                 const float *__restrict__ uniforms, int u_cap,
+                                                                 StepState *st, int *tokens_out, int cap,
+                                                                 int *__restrict__ kept_out) {
+	__shared__ alignas(16) SampleShared sh; // the window's 16-byte reads
+	__shared__ unsigned long long qmin_sh;
+	const int gen = st->n_gen; // read by every thread before thread 0 commits
+	const PenaltyParams pp = pen->p;
+	const int t = threadIdx.x;
+	const int n_ctx = pen->n_ctx < 0 ? 0 : pen->n_ctx < SMP_WINDOW ? pen->n_ctx : SMP_WINDOW;
+	const int n_prod = produced && gen > 0 ? (gen < cap ? gen : cap) : 0;
+	const int len = n_ctx + n_prod;
+	const int W = pp.window < len ? (pp.window > 0 ? pp.window : 0) : len; // <= SMP_WINDOW
+	if (t == 0)
+		qmin_sh = (unsigned long long)ceil((double)pp.min_p * 1099511627776.0);
+	int pi = -1; // the logit this thread patched, and its value before
+	float pl = 0.0f;
+	if (W > 0) {
+		int *win = (int *)sh.hw; // idle until a select clears it
+		int tok = -1;
+		if (t < W) {
+			const int h = len - W + t; // history index; the context comes first
+			tok = h < n_ctx ? ctx[h] : tokens_out[h - n_ctx];
+		}
+		if (t < ((W + 3) & ~3))
+			win[t] = tok;
+		__syncthreads();
+		if (t < W && tok >= 0 && tok < n) {
+			bool first = false;
+			const int c = smp_window_count(win, W, tok, t, first);
+			if (first) {
+				const float l = logits[tok];
+				const float a = l > 0.0f ? __fdiv_rn(l, pp.repetition) : __fmul_rn(l, pp.repetition);
+				const float b = __fadd_rn(__fmul_rn(pp.frequency, (float)c), pp.presence);
+				pi = tok;
+				pl = l;
+				logits[tok] = __fsub_rn(a, b);
+			}
+		}
+		// the patch reaches every wave of the workgroup before the passes read the logits: the
+		// writers' stores drained, then every reader's vector cache dropped
+		__threadfence();
+		__syncthreads();
+		__threadfence();
+	} else {
+		__syncthreads(); // qmin_sh
+	}
+	const unsigned long long qmin = qmin_sh;
+	smp_first_max<true>(logits, n, sh);
+	const float T = prm->temperature, top_p = prm->top_p;
+	const int top_k = prm->top_k;
+	const int ui = gen < 0 ? 0 : gen < u_cap ? gen : u_cap - 1;
+	const float u = uniforms[ui];
+	const SampleDraw r = sample_row<true, true>(logits, n, SampleParams{T, top_k, top_p}, u, sh, qmin);
+	__syncthreads(); // every thread's last pass is over: nothing reads the patched values any more
+	if (pi >= 0)
+		logits[pi] = pl;
+	if (t == 0) {
 		if (kept_out && gen >= 0 && gen < cap)
 			kept_out[gen] = (int)r.kept;
 		argmax_commit(st, r.token, tokens_out, cap);

@@ -1191,6 +1191,11 @@ static int enqueue_forward(yalm_decoder_s *d, int which) {
 		                                                d->tokens_cap, d->step, d->tokens, d->tokens_cap, nullptr,
 		                                                nullptr);
 		HIPCHK(hipGetLastError());
+	} else if (which == GRAPH_PENALISED) { // the same launch with the call's penalties (yalm_generate_sampled_ex)
+		sample_pen_kernel<<<1, SMP_THREADS, 0, d->stream>>>(d->logits, d->c.vocab_size, d->smp_params, d->pen_state,
+		                                                    d->pen_ctx, true, d->smp_u, d->tokens_cap, d->step,
+		                                                    d->tokens, d->tokens_cap, nullptr);
+		HIPCHK(hipGetLastError());
 	} else if (!d->comm) {
 		argmax_kernel<<<1, 1024, 0, d->stream>>>(d->logits, d->c.vocab_size, d->step, d->tokens, d->tokens_cap);
 		HIPCHK(hipGetLastError());
@@ -1402,7 +1407,7 @@ int dalloc(yalm_decoder_s *d, void **p, size_t bytes) {
 // One forward of graph `which`: a graph replay, or the same kernels launched
 // eagerly when d->eager.
 static int replay(yalm_decoder_s *d, int which) {
-	if (d->eager || ((which == GRAPH_GREEDY || which == GRAPH_SAMPLED) && d->greedy_eager))
+	if (d->eager || ((which == GRAPH_GREEDY || which == GRAPH_SAMPLED || which == GRAPH_PENALISED) && d->greedy_eager))
 		return enqueue_forward(d, which);
 	HIPCHK(hipGraphLaunch(d->exec[which], d->stream));
 	if (d->graph_sync)
@@ -1485,7 +1490,9 @@ static int create_decoder(const yalm_config *config, const yalm_model_weights *w
 	    (r = dalloc(d, (void **)&d->tokens, sizeof(int) * d->tokens_cap)) ||
 	    (r = dalloc(d, (void **)&d->smp_params, sizeof(SampleParams))) ||
 	    (r = dalloc(d, (void **)&d->smp_u, sizeof(float) * d->tokens_cap)) ||
-	    (r = dalloc(d, (void **)&d->smp_step, sizeof(StepState))))
+	    (r = dalloc(d, (void **)&d->smp_step, sizeof(StepState))) ||
+	    (r = dalloc(d, (void **)&d->pen_state, sizeof(PenaltyState))) ||
+	    (r = dalloc(d, (void **)&d->pen_ctx, sizeof(int) * SMP_WINDOW)))
 		return fail(r);
 	// RoPE frequencies on the host, bit for bit as the reference's compiled rope computes
 	// them. infer.cpp:203 reads 1/powf(theta, j/rotary_dim), but under its -ffast-math
@@ -1853,29 +1860,84 @@ static int validate_sampling(const yalm_sampling *s, const float *uniforms, int 
 	return YALM_OK;
 }
 
-extern "C" int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
-                                     const float *uniforms, int *out_tokens) {
+static int validate_penalties(const yalm_penalties *p) {
+	ARGCHK(p, "penalties: null argument");
+	ARGCHK(p->repetition > 0.0f && std::isfinite(p->repetition), "penalties: repetition must be finite and > 0 (1 = off)");
+	ARGCHK(std::isfinite(p->frequency), "penalties: frequency must be finite (0 = off)");
+	ARGCHK(std::isfinite(p->presence), "penalties: presence must be finite (0 = off)");
+	ARGCHK(p->min_p >= 0.0f && p->min_p <= 1.0f, "penalties: min_p must be in [0, 1] (0 = off)");
+	ARGCHK(p->window >= 0 && p->window <= SMP_WINDOW, "penalties: window must be in 0 .. 1024 (0 = off)");
+	return YALM_OK;
+}
+
+// The penalties and the last tokens of `history` (then `last`, when >= 0) into device memory for
+// sample_pen_kernel: the window never reaches further back than SMP_WINDOW tokens.
+static int upload_penalties(const yalm_penalties *p, const int *history, int n_history, int last, PenaltyState *dstate,
+                            int *dctx, hipStream_t st) {
+	std::vector<int> tail;
+	const int own = last >= 0 ? 1 : 0, keep = std::min(n_history, std::max(p->window - own, 0));
+	tail.assign(history + (n_history - keep), history + n_history);
+	if (own && p->window > 0)
+		tail.push_back(last);
+	static_assert(sizeof(yalm_penalties) == sizeof(PenaltyParams), "yalm_penalties layout");
+	PenaltyState h;
+	memcpy(&h.p, p, sizeof(h.p));
+	h.n_ctx = (int)tail.size();
+	// pageable sources: both copies have left the host buffers when the calls return
+	HIPCHK(hipMemcpyAsync(dstate, &h, sizeof(h), hipMemcpyHostToDevice, st));
+	if (!tail.empty())
+		HIPCHK(hipMemcpyAsync(dctx, tail.data(), sizeof(int) * tail.size(), hipMemcpyHostToDevice, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return YALM_OK;
+}
+
+// yalm_generate_sampled (pen == nullptr) and yalm_generate_sampled_ex
+static int generate_sampled(yalm_decoder d, const std::string &who, int token, int pos, int n_steps,
+                            const yalm_sampling *s, const yalm_penalties *pen, const int *context, int n_context,
+                            const float *uniforms, int *out_tokens) {
 	ARGCHK(d && out_tokens, "null argument");
 	ARGCHK(token >= 0 && token < d->vocab_full && pos >= 0 && n_steps >= 0, "bad token/pos/n_steps");
-	ARGCHK(n_steps <= d->tokens_cap, "yalm_generate_sampled: n_steps exceeds the token buffer (65536)");
+	ARGCHK(n_steps <= d->tokens_cap, who + ": n_steps exceeds the token buffer (65536)");
 	TRY(validate_sampling(s, uniforms, n_steps));
+	if (pen) {
+		TRY(validate_penalties(pen));
+		ARGCHK(n_context >= 0 && (context || n_context == 0), who + ": n_context must be >= 0, with a context");
+		for (int i = 0; i < n_context; ++i)
+			ARGCHK(context[i] >= 0 && context[i] < d->vocab_full, who + ": a context token outside the vocabulary");
+	}
 	if (d->tp_size > 1 || d->comm || d->ipc) {
-		set_err("yalm_generate_sampled: tensor-parallel decoders shard the vocabulary; device sampling runs on one GPU");
+		set_err(who + ": tensor-parallel decoders shard the vocabulary; device sampling runs on one GPU");
 		return YALM_ERR_UNSUPPORTED;
 	}
-	ARGCHK(d->c.vocab_size <= SMP_MAX_N, "yalm_generate_sampled: vocabulary above 131072");
+	ARGCHK(d->c.vocab_size <= SMP_MAX_N, who + ": vocabulary above 131072");
 	if (n_steps == 0)
 		return YALM_OK;
 	static_assert(sizeof(yalm_sampling) == sizeof(SampleParams), "yalm_sampling layout");
 	HIPCHK(hipMemcpyAsync(d->smp_params, s, sizeof(SampleParams), hipMemcpyHostToDevice, d->stream));
 	HIPCHK(hipMemcpyAsync(d->smp_u, uniforms, sizeof(float) * n_steps, hipMemcpyHostToDevice, d->stream));
+	if (pen)
+		TRY(upload_penalties(pen, context, n_context, token, d->pen_state, d->pen_ctx, d->stream));
 	set_step_kernel<<<1, 1, 0, d->stream>>>(d->step, token, pos, 1);
 	HIPCHK(hipGetLastError());
-	TRY(replay_greedy(d, n_steps, pos, GRAPH_SAMPLED));
+	TRY(replay_greedy(d, n_steps, pos, pen ? GRAPH_PENALISED : GRAPH_SAMPLED));
 	d->host_pos = (long long)pos + n_steps;
 	HIPCHK(hipMemcpyAsync(out_tokens, d->tokens, sizeof(int) * n_steps, hipMemcpyDeviceToHost, d->stream));
 	HIPCHK(hipStreamSynchronize(d->stream));
 	return awo_check(d);
+}
+
+extern "C" int yalm_generate_sampled(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
+                                     const float *uniforms, int *out_tokens) {
+	return generate_sampled(d, "yalm_generate_sampled", token, pos, n_steps, s, nullptr, nullptr, 0, uniforms,
+	                        out_tokens);
+}
+
+extern "C" int yalm_generate_sampled_ex(yalm_decoder d, int token, int pos, int n_steps, const yalm_sampling *s,
+                                        const yalm_penalties *p, const int *context, int n_context,
+                                        const float *uniforms, int *out_tokens) {
+	ARGCHK(p, "yalm_generate_sampled_ex: null penalties");
+	return generate_sampled(d, "yalm_generate_sampled_ex", token, pos, n_steps, s, p, context, n_context, uniforms,
+	                        out_tokens);
 }
 
 // ------------------------------------------------------------------ multi-row forward, speculative greedy decode
@@ -2822,6 +2884,12 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 		                                                d->smp_step, nullptr, 0, nullptr, nullptr);
 		HIPCHK(hipGetLastError());
 		return YALM_OK;
+	case KID_SAMPLE_PEN: // the same with the penalties and the context of the last yalm_generate_sampled_ex
+		sample_pen_kernel<<<1, SMP_THREADS, 0, d->stream>>>(d->logits, c.vocab_size, d->smp_params, d->pen_state,
+		                                                    d->pen_ctx, false, d->smp_u, 1, d->smp_step, nullptr, 0,
+		                                                    nullptr);
+		HIPCHK(hipGetLastError());
+		return YALM_OK;
 	// the launches that end a 4-row speculative step, on the rows' current logits and a scratch step state
 	case KID_SPEC_SAMPLE:
 		if (c.vocab_size % 4 == 0)
@@ -2849,7 +2917,7 @@ static int enqueue_one_t(yalm_decoder_s *d, int kernel_id, int l) {
 extern "C" int yalm_graph_kernels(yalm_decoder d, int mode, int *kernels, int *nodes) {
 	ARGCHK(d && kernels && mode >= 0 && mode < N_GRAPHS, "yalm_graph_kernels: bad argument");
 	ARGCHK(!d->eager, "yalm_graph_kernels: the decoder launches eagerly (YALM_LAUNCH_EAGER)");
-	if (mode == GRAPH_SAMPLED && (d->tp_size > 1 || d->comm || d->ipc)) {
+	if ((mode == GRAPH_SAMPLED || mode == GRAPH_PENALISED) && (d->tp_size > 1 || d->comm || d->ipc)) {
 		set_err("yalm_graph_kernels: no sampled step on a tensor-parallel decoder");
 		return YALM_ERR_UNSUPPORTED;
 	}
@@ -2916,11 +2984,12 @@ static int time_loop(yalm_decoder_s *d, int kernel_id, int iters, bool bump, boo
 
 extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float *avg_ms) {
 	ARGCHK(d && avg_ms && iters > 0 && kernel_id >= 0 && kernel_id <= KID_LAST && kernel_id != 7,
-	       "bad argument (kernel ids 0-6, 8-14)");
+	       "bad argument (kernel ids 0-6, 8-15)");
 	ARGCHK(kernel_id != KID_QK_NORM || qkv_form(d) == QKV_NORM, "kernel 11 (q / k norm) needs yalm_decoder_set_qk_norm");
-	ARGCHK(kernel_id != KID_SAMPLE || (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
-	       "kernel 10 (device sampling) needs a one-GPU decoder and a vocabulary of at most 131072");
-	if (kernel_id >= KID_SPEC_SAMPLE) { // the speculative step's last launches: a decoder with a multi-row form, its row buffers
+	ARGCHK((kernel_id != KID_SAMPLE && kernel_id != KID_SAMPLE_PEN) ||
+	           (d->tp_size == 1 && !d->comm && !d->ipc && d->c.vocab_size <= SMP_MAX_N),
+	       "kernels 10 and 15 (device sampling) need a one-GPU decoder and a vocabulary of at most 131072");
+	if (kernel_id >= KID_SPEC_SAMPLE && kernel_id <= KID_SPEC_VERIFY) { // the speculative step's last launches: a decoder with a multi-row form, its row buffers
 		TRY(rows_supported(d, "yalm_time_kernel (kernels 12-14)"));
 		ARGCHK(d->c.vocab_size <= SMP_MAX_N, "kernels 12-14 need a vocabulary of at most 131072");
 		TRY(rows_init(d));
@@ -3004,6 +3073,9 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 		break;
 	case KID_SAMPLE:
 		s = "sample_kernel";
+		break;
+	case KID_SAMPLE_PEN:
+		s = "sample_pen_kernel";
 		break;
 	case KID_QK_NORM:
 		s = qkv_form(d) == QKV_NORM ? "qk_norm_rope_kernel<" : "";
@@ -3492,6 +3564,38 @@ extern "C" int yalm_sample(const float *logits, int n, const yalm_sampling *s, c
 		HIPCHK(hipMemcpy(kept, dkept.p, sizeof(int) * n_draws, hipMemcpyDeviceToHost));
 	if (weights_out)
 		HIPCHK(hipMemcpy(weights_out, dw.p, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+extern "C" int yalm_sample_ex(const float *logits, int n, const yalm_sampling *s, const yalm_penalties *p,
+                              const int *history, int n_history, const float *uniforms, int n_draws, int *out,
+                              float *logits_after) {
+	ARGCHK(logits && out && n > 0 && n_draws > 0 && n_draws <= (1 << 16), "yalm_sample_ex: bad argument");
+	ARGCHK(n <= SMP_MAX_N, "yalm_sample_ex: n above 131072");
+	TRY(validate_sampling(s, uniforms, n_draws));
+	TRY(validate_penalties(p));
+	ARGCHK(n_history >= 0 && (history || n_history == 0), "yalm_sample_ex: n_history must be >= 0, with a history");
+	for (int i = 0; i < n_history; ++i)
+		ARGCHK(history[i] >= 0 && history[i] < n, "yalm_sample_ex: a history token outside the vocabulary");
+	DevBuf dl, dst, dprm, dpen, dctx, du, dtok;
+	TRY(up(dl, logits, sizeof(float) * (size_t)n));
+	TRY(up(dst, nullptr, sizeof(StepState)));
+	TRY(up(dprm, s, sizeof(SampleParams)));
+	TRY(up(dpen, nullptr, sizeof(PenaltyState)));
+	TRY(up(dctx, nullptr, sizeof(int) * SMP_WINDOW));
+	TRY(up(du, uniforms, sizeof(float) * n_draws));
+	TRY(up(dtok, nullptr, sizeof(int) * n_draws));
+	TRY(upload_penalties(p, history, n_history, -1, (PenaltyState *)dpen.p, (int *)dctx.p, nullptr));
+	for (int i = 0; i < n_draws; ++i) // draw i reads uniforms[n_gen = i]; every draw sees the same history
+		sample_pen_kernel<<<1, SMP_THREADS>>>((float *)dl.p, n, (const SampleParams *)dprm.p,
+		                                      (const PenaltyState *)dpen.p, (const int *)dctx.p, false,
+		                                      (const float *)du.p, n_draws, (StepState *)dst.p, (int *)dtok.p, n_draws,
+		                                      nullptr);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(out, dtok.p, sizeof(int) * n_draws, hipMemcpyDeviceToHost));
+	if (logits_after)
+		HIPCHK(hipMemcpy(logits_after, dl.p, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
 	return YALM_OK;
 }
 

@@ -47,6 +47,15 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -k <int>   top-k: sample among the k most likely tokens (0 - off); samples on the device\n");
 	fprintf(stderr, "  -p <float> top-p: sample from the smallest set of most likely tokens whose probability\n"
 	                "             reaches p, in (0, 1] (1 - off); samples on the device\n");
+	fprintf(stderr, "  --repeat-penalty <float>    divide the positive, multiply the other logits of the tokens in\n"
+	                "                              the penalty window by this (> 0; 1 - off)\n");
+	fprintf(stderr, "  --frequency-penalty <float> subtract this times a token's count in the window (0 - off)\n");
+	fprintf(stderr, "  --presence-penalty <float>  subtract this from every token in the window (0 - off)\n");
+	fprintf(stderr, "  --min-p <float>             keep only tokens at least this likely relative to the most\n"
+	                "                              likely one, in [0, 1] (0 - off)\n");
+	fprintf(stderr, "  --penalty-window <int>      how many of the most recent tokens, prompt included, the\n"
+	                "                              penalties look at, 0..1024 (default 64 when one is set)\n");
+	fprintf(stderr, "             the five above sample on the device; they need -t > 0; not with -s or -N\n");
 	fprintf(stderr, "  -s <int>   speculative decode with this many rows per step, 2..4 (0 - off, the default);\n"
 	                "             needs -t 0 (greedy), or -t > 0 with -k or -p (sampled on the device: the\n"
 	                "             same tokens as without -s)\n");
@@ -98,7 +107,8 @@ static std::vector<int> encode_prompt(const Tokenizer &tok, const std::string &p
 
 static void run_completion(const std::string &path, const std::string &device, const std::string &prompt,
                            int context, int num_steps, float temperature, bool device_sampling, int top_k,
-                           float top_p, int spec_rows, int n_completions, const std::string &draft_path) {
+                           float top_p, int spec_rows, int n_completions, const std::string &draft_path,
+                           const yalm_penalties *pen) {
 	YALMData data;
 	if (data.from_file(path) != 0) {
 		fprintf(stderr, "error: cannot load %s\n", path.c_str());
@@ -174,7 +184,8 @@ static void run_completion(const std::string &path, const std::string &device, c
 		if (last && greedy)
 			next = model.forward_greedy(state, encoding[pos], (int)pos);
 		else if (last && sampled)
-			next = model.forward_sampled(state, encoding[pos], (int)pos, temperature, top_k, top_p, uniform());
+			next = model.forward_sampled(state, encoding[pos], (int)pos, temperature, top_k, top_p, uniform(), pen,
+			                             encoding.data(), (int)pos);
 		else
 			model.forward(state, encoding[pos], (int)pos,
 			              last ? InferenceMode::OUTPUT_LOGITS : InferenceMode::HYDRATE_KV_CACHE);
@@ -279,7 +290,7 @@ static void run_completion(const std::string &path, const std::string &device, c
 		else if (sampled) {
 			if (i + 1 == num_steps)
 				break; // no further token: no further forward, and exactly one draw per generated token
-			next = model.forward_sampled(state, token, pos, temperature, top_k, top_p, uniform());
+			next = model.forward_sampled(state, token, pos, temperature, top_k, top_p, uniform(), pen, encoding.data(), pos);
 		} else
 			model.forward(state, token, pos);
 		read_bytes += model.config->active_bytes(pos);
@@ -439,14 +450,33 @@ int main(int argc, char *argv[]) {
 	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path, draft_path;
 	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0, spec_rows = 0, n_completions = 0;
 	float temperature = 1.0f, top_p = 1.0f;
-	bool device_sampling = false;
+	bool device_sampling = false, penalised = false;
+	yalm_penalties pen{1.0f, 0.0f, 0.0f, 0.0f, -1}; // window -1: not given
 	if (argc < 2)
 		error_usage();
 	checkpoint = argv[1];
 	for (int i = 2; i < argc; i += 2) {
-		if (i + 1 >= argc || argv[i][0] != '-' || strlen(argv[i]) != 2)
+		if (i + 1 >= argc || argv[i][0] != '-')
 			error_usage();
-		const std::string v = argv[i + 1];
+		const std::string v = argv[i + 1], flag = argv[i];
+		if (flag.rfind("--", 0) == 0) { // the penalties of the device sampler
+			if (flag == "--repeat-penalty")
+				pen.repetition = std::stof(v);
+			else if (flag == "--frequency-penalty")
+				pen.frequency = std::stof(v);
+			else if (flag == "--presence-penalty")
+				pen.presence = std::stof(v);
+			else if (flag == "--min-p")
+				pen.min_p = std::stof(v);
+			else if (flag == "--penalty-window")
+				pen.window = std::stoi(v);
+			else
+				error_usage();
+			penalised = device_sampling = true;
+			continue;
+		}
+		if (flag.size() != 2)
+			error_usage();
 		switch (argv[i][1]) {
 		case 'h': error_usage();
 		case 'm':
@@ -503,6 +533,17 @@ int main(int argc, char *argv[]) {
 	if (n_completions != 0 && (n_completions < 2 || n_completions > 4 || !(temperature > 0.0f) || !device_sampling ||
 	                           spec_rows != 0 || mode != "completion"))
 		error_usage();
+	// the penalties: the plain device-sampled completion alone (a speculative row's history would
+	// depend on which drafts are accepted, and -N's completions do not share one)
+	if (penalised) {
+		if (!(temperature > 0.0f) || spec_rows != 0 || n_completions != 0 || mode != "completion") {
+			fprintf(stderr, "error: --repeat-penalty, --frequency-penalty, --presence-penalty, --min-p and "
+			                "--penalty-window need completion mode with -t > 0 and go with neither -s nor -N\n");
+			return 1;
+		}
+		if (pen.window < 0)
+			pen.window = 64;
+	}
 	const int has_prompt = prompt.size() > 0, has_path = prompt_path.size() > 0;
 	if (mode == "completion" || mode == "perplexity") {
 		if (has_prompt + has_path != 1)
@@ -525,7 +566,7 @@ int main(int argc, char *argv[]) {
 	try {
 		if (mode == "completion")
 			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p,
-			               spec_rows, n_completions, draft_path);
+			               spec_rows, n_completions, draft_path, penalised ? &pen : nullptr);
 		else if (mode == "passkey")
 			run_passkey(checkpoint, device, context, n_junk, passkey_pos);
 		else

@@ -479,11 +479,16 @@ void Model::generate_batch_sampled(InferenceState &s, int n_seq, int load, const
 	check(yalm_batch_generate_sampled(s._batch, tokens, pos, n, &sp, uniforms, out, nullptr), "batched sampled steps");
 }
 
-int Model::forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u) {
+int Model::forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u,
+                           const yalm_penalties *pen, const int *context, int n_context) {
 	ensure_decoder(s);
 	const yalm_sampling sp{temperature, top_k, top_p};
 	int next = 0;
-	check(yalm_generate_sampled(s._decoder, token, pos, 1, &sp, &u, &next), "sampled step");
+	if (pen)
+		check(yalm_generate_sampled_ex(s._decoder, token, pos, 1, &sp, pen, context, n_context, &u, &next),
+		      "penalised sampled step");
+	else
+		check(yalm_generate_sampled(s._decoder, token, pos, 1, &sp, &u, &next), "sampled step");
 	return next;
 }
 

@@ -144,7 +144,10 @@ struct Model {
 	// Sampled step on the device (yalm_generate_sampled, one step): forward, then temperature /
 	// top-k (0 = off) / top-p (1 = off) sampling of the logits with the uniform u in [0, 1];
 	// only the token comes back. Returns the next token.
-	int forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u);
+	// pen (may be null): the repetition / frequency / presence penalties and min-p of
+	// yalm_generate_sampled_ex over the n_context tokens of `context` that precede `token`.
+	int forward_sampled(InferenceState &s, int token, int pos, float temperature, int top_k, float top_p, float u,
+	                    const yalm_penalties *pen = nullptr, const int *context = nullptr, int n_context = 0);
 	// n greedy tokens by speculative steps of `rows` rows (yalm_generate_speculative, n-gram
 	// drafts of 3 down to 1 tokens from `context`, which ends with `token`): the tokens of
 	// forward_greedy, several per pass over the weights where the drafts hit. steps / accepted /

@@ -68,6 +68,24 @@ class Sampling(ctypes.Structure):
     _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float)]
 
 
+class Penalties(ctypes.Structure):
+    """yalm_penalties: repetition > 0 (1 = off), frequency, presence (0 = off), min_p in [0, 1]
+    (0 = off), window 0..1024 of the most recent history tokens (0 = penalties off)."""
+
+    _fields_ = [("repetition", c_float), ("frequency", c_float), ("presence", c_float), ("min_p", c_float),
+                ("window", c_int)]
+
+
+def _penalties(p) -> Penalties:
+    """A Penalties from one, a dict of its fields or a (repetition, frequency, presence, min_p, window) tuple."""
+    if isinstance(p, Penalties):
+        return p
+    if isinstance(p, dict):
+        return Penalties(p.get("repetition", 1.0), p.get("frequency", 0.0), p.get("presence", 0.0),
+                         p.get("min_p", 0.0), p.get("window", 64))
+    return Penalties(*p)
+
+
 class Spec(ctypes.Structure):
     """yalm_spec: rows 2..4, 1 <= ngram_min <= ngram_max <= 4, the draft_stream hook."""
 
@@ -202,6 +220,10 @@ _sig("yalm_generate_greedy", c_int, [c_void_p, c_int, c_int, c_int, c_void_p])
 _sig("yalm_enqueue_greedy", c_int, [c_void_p, c_int])
 _sig("yalm_generate_sampled", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Sampling), c_void_p, c_void_p])
 _sig("yalm_sample", c_int, [c_void_p, c_int, ctypes.POINTER(Sampling), c_void_p, c_int, c_void_p, c_void_p, c_void_p])
+_sig("yalm_generate_sampled_ex", c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(Sampling),
+                                          ctypes.POINTER(Penalties), c_void_p, c_int, c_void_p, c_void_p])
+_sig("yalm_sample_ex", c_int, [c_void_p, c_int, ctypes.POINTER(Sampling), ctypes.POINTER(Penalties), c_void_p, c_int,
+                                c_void_p, c_int, c_void_p, c_void_p])
 _sig("yalm_device_step", c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
 _sig("yalm_device_tokens", c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(c_int)])
 _sig("yalm_block", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int])
@@ -281,7 +303,7 @@ EXPORTED = [
     "yalm_stream_create_cu_part", "yalm_decoder_set_launch", "yalm_prefill_info", "yalm_set_prefill_precision",
     "yalm_decoder_create_moe", "yalm_moe_routing", "yalm_moe_ffn",
     "yalm_prefill_routing", "yalm_moe_gemm_f16", "yalm_moe_ffn_rows",
-    "yalm_generate_sampled", "yalm_sample",
+    "yalm_generate_sampled", "yalm_sample", "yalm_generate_sampled_ex", "yalm_sample_ex",
     "yalm_row_bytes", "yalm_synth_q4", "yalm_synth_e4m3",
     "yalm_forward_rows", "yalm_generate_speculative", "yalm_spec_draft",
     "yalm_generate_speculative_sampled", "yalm_spec_sample_rows",
@@ -368,6 +390,22 @@ def sample(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float 
     q = np.zeros(max(lg.size, 1), np.uint64)
     check(lib.yalm_sample(_ptr(lg), lg.size, ctypes.byref(s), _ptr(u), u.size, _ptr(tokens), _ptr(kept), _ptr(q)))
     return tokens[:u.size], kept[:u.size], q[:lg.size]
+
+
+def sample_ex(logits: np.ndarray, temperature: float, top_k: int = 0, top_p: float = 1.0, penalties=(1.0, 0.0, 0.0, 0.0, 0),
+              history=(), uniforms=(0.5,)):
+    """Device sampling of host logits with penalties and min-p (yalm_sample_ex: one launch of
+    yalm_generate_sampled_ex's kernel per uniform, every draw over the same history). Returns
+    (tokens, logits_after): the token of every draw and the device's logits after the launches."""
+    lg = np.ascontiguousarray(logits, dtype=np.float32)
+    u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
+    h = np.ascontiguousarray(history, dtype=np.int32).reshape(-1)
+    s, p = Sampling(temperature, top_k, top_p), _penalties(penalties)
+    tokens = np.zeros(max(u.size, 1), np.int32)
+    after = np.zeros(max(lg.size, 1), np.float32)
+    check(lib.yalm_sample_ex(_ptr(lg), lg.size, ctypes.byref(s), ctypes.byref(p), _ptr(h) if h.size else None, h.size,
+                             _ptr(u), u.size, _ptr(tokens), _ptr(after)))
+    return tokens[:u.size], after[:lg.size]
 
 
 def spec_draft(history, rows: int, ngram_max: int = 3, ngram_min: int = 1) -> list:
@@ -1048,9 +1086,11 @@ class Decoder:
                                   "plain_steps": st.plain_steps, "launches_per_step": st.launches_per_step}
 
     def generate_sampled(self, token: int, pos: int, n: int, temperature: float, top_k: int = 0,
-                         top_p: float = 1.0, uniforms=None, seed: int = 0) -> list:
+                         top_p: float = 1.0, uniforms=None, seed: int = 0, penalties=None, context=None) -> list:
         """n tokens sampled on the device (yalm_generate_sampled): temperature, then top-k, then
-        top-p, one uniform per step. uniforms None: numpy.random.default_rng(seed).random(n, float32)."""
+        top-p, one uniform per step. uniforms None: numpy.random.default_rng(seed).random(n, float32).
+        penalties (a Penalties, a dict of its fields or a tuple): yalm_generate_sampled_ex, with
+        context the tokens that precede `token`, oldest first."""
         if uniforms is None:
             uniforms = np.random.default_rng(seed).random(n, dtype=np.float32)
         u = np.ascontiguousarray(uniforms, dtype=np.float32).reshape(-1)
@@ -1060,7 +1100,15 @@ class Decoder:
             u = np.zeros(1, np.float32)
         s = Sampling(temperature, top_k, top_p)
         out = np.zeros(max(n, 1), np.int32)
-        check(lib.yalm_generate_sampled(self.h, token, pos, n, ctypes.byref(s), _ptr(u), out.ctypes.data))
+        if penalties is None:
+            if context is not None:
+                raise ValueError("generate_sampled: a context counts only with penalties")
+            check(lib.yalm_generate_sampled(self.h, token, pos, n, ctypes.byref(s), _ptr(u), out.ctypes.data))
+            return out[:n].tolist()
+        p = _penalties(penalties)
+        ctx = np.ascontiguousarray(context if context is not None else [], dtype=np.int32).reshape(-1)
+        check(lib.yalm_generate_sampled_ex(self.h, token, pos, n, ctypes.byref(s), ctypes.byref(p),
+                                           _ptr(ctx) if ctx.size else None, ctx.size, _ptr(u), out.ctypes.data))
         return out[:n].tolist()
 
     def generate_speculative_sampled(self, token: int, pos: int, n: int, temperature: float, top_k: int = 0,
