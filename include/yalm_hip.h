@@ -738,6 +738,30 @@ int yalm_batch_set_launch(yalm_batch b, int flags);
  * before it and directly after its last byte, which nothing ever writes. */
 #define YALM_BATCH_GUARD_BYTES 256
 int yalm_batch_buffers(yalm_batch b, int seq, int layer, uint16_t **kcache, uint16_t **vcache, int **tokens);
+/* Rows [0, n_positions) of EVERY sequence are read from the decoder's own caches (where yalm_prefill /
+ * yalm_forward put them), not from the sequence's; rows from n_positions on stay the sequence's own.
+ * No copy is made. 0 = off (the default: the batch launches exactly what it launches today).
+ * With a prefix shared the attention of a layer is the two launches of csrc/batch_prefix.h (every
+ * shared K / V row read once per kv head and step for all sequences, on the matrix cores; then a
+ * merge), whatever YALM_BATCH_ATTN_PER_SEQ says: launches_per_step is 3 + n_layers * 6 (+ n_layers
+ * with the q / k norm). The QKV launch still writes row pos[s] into sequence s's own cache.
+ * While a prefix is shared every yalm_batch_forward / yalm_batch_generate_* call needs pos[s] >=
+ * n_positions for every s: YALM_ERR_ARG otherwise, and the refused call changes nothing. The caller
+ * must not rewrite the decoder's rows below n_positions while they are shared (no yalm_forward /
+ * yalm_prefill below it, no generation that wraps the ring), as it must keep the decoder alive.
+ * The first share allocates the batch's partial buffer (guarded like its caches).
+ * YALM_ERR_ARG: n_positions outside [0, max_seq_len]. YALM_ERR_UNSUPPORTED, naming the reason:
+ * head_dim other than 64 or 128, or n_seq x (n_heads / n_kv_heads) > 32. */
+int yalm_batch_share_prefix(yalm_batch b, int n_positions);
+/* Test hook (host pointers, synchronous, no decoder): the two launches of the shared-prefix
+ * attention as a batch step makes them. q / out: [n_seq][n_heads * head_dim] f32; every cache is
+ * [cache_rows][n_kv_heads * head_dim] f16; 1 <= prefix < kv_len[s] <= cache_rows. Row s attends to
+ * rows [0, prefix) of k_shared / v_shared and to rows [prefix, kv_len[s]) of k_seq[s] / v_seq[s].
+ * out is uploaded as given, between two guard rows, and returned whole; YALM_ERR_HIP if a guard row
+ * was written. YALM_ERR_UNSUPPORTED as yalm_batch_share_prefix. */
+int yalm_attn_batch_prefix(float *out, const float *q, const uint16_t *k_shared, const uint16_t *v_shared,
+                           const uint16_t *const *k_seq, const uint16_t *const *v_seq, int cache_rows, int n_seq,
+                           int prefix, const int *kv_len, int n_heads, int n_kv_heads, int head_dim);
 
 /* ---------------- test API: replaces infer.cu:890-1019 (model.h:370-384) ---------------- */
 /* Host pointers in and out; synchronous. dtype selects the weight type

@@ -20,6 +20,7 @@
 #include "attention.h"
 #include "attn_wo.h"
 #include "batch.h"
+#include "batch_prefix.h"
 #include "decoder.h"
 #include "device_common.h"
 #include "gemv.h"
@@ -2431,6 +2432,8 @@ extern "C" int yalm_decoder_get_stream(yalm_decoder d, yalm_stream *out) {
 struct yalm_batch_s {
 	yalm_decoder_s *d = nullptr;
 	int n_seq = 0, flags = 0;
+	int prefix = 0;                        // yalm_batch_share_prefix: rows [0, prefix) are the decoder's (0 = off)
+	float *pfx_part = nullptr;             // batch_prefix.h partials, allocated by the first share (guarded)
 	StepState *seq = nullptr;              // [n_seq] sequence = row states
 	float *x = nullptr, *q = nullptr, *xb2 = nullptr, *hb = nullptr, *logits = nullptr; // [n_seq][...]
 	float *logits_pinned = nullptr;        // [n_seq][vocab] host
@@ -2561,6 +2564,44 @@ extern "C" int yalm_batch_load(yalm_batch b, int seq, int n_positions) {
 	return YALM_OK;
 }
 
+// The shared-prefix attention (batch_prefix.h): its two launches, as the batch step and the
+// yalm_attn_batch_prefix hook make them. a: everything but S0 / S1; cache_rows: rows of every cache.
+static const char *pfx_unsupported(int head_dim, int n_seq, int G) {
+	if (head_dim != 64 && head_dim != 128)
+		return "the shared-prefix attention needs head_dim 64 or 128";
+	if (n_seq * G > PFX_ROWS)
+		return "the shared-prefix attention takes at most 32 query rows per kv head (n_seq x n_heads / n_kv_heads)";
+	return nullptr;
+}
+static int launch_attn_batch_prefix(int head_dim, PfxArgs a, int cache_rows, hipStream_t st) {
+	a.S0 = pfx_s0(a.prefix);
+	a.S1 = pfx_s1(a.prefix, cache_rows);
+	const int units = a.n_kv * (a.S0 + a.n_seq * a.S1), rows = a.n_seq * a.n_heads;
+	if (head_dim == 64) {
+		attn_prefix_part_kernel<64><<<units, YALM_WAVE, 0, st>>>(a);
+		attn_prefix_merge_kernel<64><<<rows, YALM_WAVE, 0, st>>>(a);
+	} else {
+		attn_prefix_part_kernel<128><<<units, YALM_WAVE, 0, st>>>(a);
+		attn_prefix_merge_kernel<128><<<rows, YALM_WAVE, 0, st>>>(a);
+	}
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+extern "C" int yalm_batch_share_prefix(yalm_batch b, int n_positions) {
+	ARGCHK(b, "yalm_batch_share_prefix: null batch");
+	const yalm_config &c = b->d->c;
+	ARGCHK(n_positions >= 0 && n_positions <= c.max_seq_len, "yalm_batch_share_prefix: n_positions outside [0, max_seq_len]");
+	if (const char *why = pfx_unsupported(c.head_dim, b->n_seq, c.n_heads / c.n_kv_heads)) {
+		set_err(std::string("yalm_batch_share_prefix: ") + why);
+		return YALM_ERR_UNSUPPORTED;
+	}
+	if (n_positions > 0 && !b->pfx_part)
+		TRY(batch_alloc(b, (void **)&b->pfx_part, sizeof(float) * pfx_part_floats(b->n_seq, c.n_heads, c.head_dim), true));
+	b->prefix = n_positions;
+	return YALM_OK;
+}
+
 // The attention of every sequence as one launch: launch_attn_D's choices of S, hmax and nsplit.
 template <int D>
 static void launch_attn_batch_D(const yalm_batch_s *b, int l) {
@@ -2591,6 +2632,14 @@ static int enqueue_batch_attn(const yalm_batch_s *b, int l) {
 	const yalm_decoder_s *d = b->d;
 	const yalm_config &c = d->c;
 	const int q_dim = c.n_heads * c.head_dim;
+	if (b->prefix > 0) { // whatever YALM_BATCH_ATTN_PER_SEQ says
+		PfxArgs a{};
+		a.q = b->q, a.out = b->xb2, a.q_stride = q_dim;
+		a.ks = d->b[l].key_cache, a.vs = d->b[l].value_cache, a.kv = b->kv[l];
+		a.steps = b->seq, a.part = b->pfx_part;
+		a.n_seq = b->n_seq, a.prefix = b->prefix, a.n_heads = c.n_heads, a.n_kv = c.n_kv_heads;
+		return launch_attn_batch_prefix(c.head_dim, a, c.max_seq_len, d->stream);
+	}
 	if (b->flags & YALM_BATCH_ATTN_PER_SEQ) {
 		for (int s = 0; s < b->n_seq; ++s)
 			TRY(launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, b->q + (size_t)s * q_dim, b->kv[l].k[s], b->kv[l].v[s],
@@ -2673,7 +2722,7 @@ static int enqueue_batch_forward(yalm_batch_s *b) {
 }
 
 static int batch_launches(const yalm_batch_s *b) {
-	const int L = b->d->c.n_layers, attn = (b->flags & YALM_BATCH_ATTN_PER_SEQ) ? b->n_seq : 1;
+	const int L = b->d->c.n_layers, attn = b->prefix > 0 ? 2 : (b->flags & YALM_BATCH_ATTN_PER_SEQ) ? b->n_seq : 1;
 	return 3 + L * (4 + attn + (b->d->gq.empty() ? 0 : 1));
 }
 
@@ -2694,6 +2743,7 @@ extern "C" int yalm_batch_forward(yalm_batch b, const int *tokens, const int *po
 		ARGCHK(tokens[s] >= 0 && tokens[s] < d->vocab_full, "yalm_batch_forward: token out of range");
 		ARGCHK(pos[s] >= 0 && pos[s] < d->c.max_seq_len,
 		       "yalm_batch_forward: pos must be in [0, max_seq_len) (a batched step never wraps the ring or rotates the sinks)");
+		ARGCHK(pos[s] >= b->prefix, "yalm_batch_forward: pos is inside the shared prefix (yalm_batch_share_prefix)");
 	}
 	TRY(batch_set(b, tokens, pos, 0));
 	TRY(enqueue_batch_forward(b));
@@ -2719,6 +2769,7 @@ static int batch_generate(yalm_batch_s *b, const char *name, const int *tokens, 
 		ARGCHK(tokens[s] >= 0 && tokens[s] < d->vocab_full, who + ": token out of range");
 		ARGCHK(pos[s] >= 0 && (long long)pos[s] + n_steps <= d->c.max_seq_len,
 		       who + ": pos + n_steps must not exceed max_seq_len (a batched step never wraps the ring or rotates the sinks)");
+		ARGCHK(pos[s] >= b->prefix, who + ": pos is inside the shared prefix (yalm_batch_share_prefix)");
 	}
 	if (smp) {
 		TRY(validate_sampling(smp, uniforms, b->n_seq * n_steps));
@@ -3512,6 +3563,58 @@ extern "C" int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint1
 		set_err("yalm_mha: the split-KV merger gave up waiting for a chunk");
 		return YALM_ERR_HIP;
 	}
+	return YALM_OK;
+}
+
+extern "C" int yalm_attn_batch_prefix(float *out, const float *q, const uint16_t *k_shared, const uint16_t *v_shared,
+                                      const uint16_t *const *k_seq, const uint16_t *const *v_seq, int cache_rows,
+                                      int n_seq, int prefix, const int *kv_len, int n_heads, int n_kv_heads,
+                                      int head_dim) {
+	ARGCHK(out && q && k_shared && v_shared && k_seq && v_seq && kv_len, "yalm_attn_batch_prefix: null argument");
+	ARGCHK(n_seq >= 1 && n_seq <= ROWS_MAX_T && n_kv_heads > 0 && n_heads > 0 && n_heads % n_kv_heads == 0 &&
+	           prefix >= 1 && prefix < cache_rows,
+	       "yalm_attn_batch_prefix: bad shape");
+	for (int s = 0; s < n_seq; ++s)
+		ARGCHK(k_seq[s] && v_seq[s] && kv_len[s] > prefix && kv_len[s] <= cache_rows,
+		       "yalm_attn_batch_prefix: prefix < kv_len[s] <= cache_rows and a cache per sequence");
+	if (const char *why = pfx_unsupported(head_dim, n_seq, n_heads / n_kv_heads)) {
+		set_err(std::string("yalm_attn_batch_prefix: ") + why);
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const size_t kvb = sizeof(uint16_t) * (size_t)cache_rows * n_kv_heads * head_dim;
+	const size_t qb = sizeof(float) * (size_t)n_seq * n_heads * head_dim;
+	DevBuf dks, dvs, dk[ROWS_MAX_T], dv[ROWS_MAX_T], dq, dout, dpart, dstep;
+	TRY(up(dks, k_shared, kvb));
+	TRY(up(dvs, v_shared, kvb));
+	TRY(up(dq, q, qb));
+	// out between two guard rows of 0xA5 bytes, checked after the launches
+	const size_t rowb = qb / n_seq;
+	std::vector<unsigned char> oh(qb + 2 * rowb, 0xA5);
+	memcpy(oh.data() + rowb, out, qb);
+	TRY(up(dout, oh.data(), oh.size()));
+	TRY(up(dpart, nullptr, sizeof(float) * pfx_part_floats(n_seq, n_heads, head_dim)));
+	TRY(up(dstep, nullptr, sizeof(StepState) * n_seq));
+	PfxArgs a{};
+	for (int s = 0; s < n_seq; ++s) {
+		TRY(up(dk[s], k_seq[s], kvb));
+		TRY(up(dv[s], v_seq[s], kvb));
+		set_step_full_kernel<<<1, 1>>>((StepState *)dstep.p + s, kv_len[s] - 1, 0, kv_len[s] - 1, kv_len[s]);
+	}
+	for (int s = 0; s < ROWS_MAX_T; ++s) // rows past n_seq alias sequence 0's, as in a batch
+		a.kv.k[s] = (uint16_t *)dk[s < n_seq ? s : 0].p, a.kv.v[s] = (uint16_t *)dv[s < n_seq ? s : 0].p;
+	a.q = (const float *)dq.p, a.out = (float *)((char *)dout.p + rowb), a.q_stride = n_heads * head_dim;
+	a.ks = (const uint16_t *)dks.p, a.vs = (const uint16_t *)dvs.p;
+	a.steps = (const StepState *)dstep.p, a.part = (float *)dpart.p;
+	a.n_seq = n_seq, a.prefix = prefix, a.n_heads = n_heads, a.n_kv = n_kv_heads;
+	TRY(launch_attn_batch_prefix(head_dim, a, cache_rows, nullptr));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(oh.data(), dout.p, oh.size(), hipMemcpyDeviceToHost));
+	memcpy(out, oh.data() + rowb, qb);
+	for (size_t i = 0; i < rowb; ++i)
+		if (oh[i] != 0xA5 || oh[rowb + qb + i] != 0xA5) {
+			set_err("yalm_attn_batch_prefix: a guard row of out was written");
+			return YALM_ERR_HIP;
+		}
 	return YALM_OK;
 }
 

@@ -64,6 +64,8 @@ static uint64_t now_ms() {
 	fprintf(stderr, "  -N <int>   completions of one prompt decoded together, 2..4 (0 - off, the default): one pass\n"
 	                "             over the weights per step for all of them; needs -t > 0 with -k or -p (greedy\n"
 	                "             completions would be identical); not with -s\n");
+	fprintf(stderr, "  --share-prompt   with -N: the completions attend to the prompt's KV rows where they are (no\n"
+	                "             copy per completion, each row read once per step); head_dim 64 or 128\n");
 	fprintf(stderr, "  Choose one:\n    -i <string> input prompt\n    -f <filepath> input file with prompt\n");
 	fprintf(stderr, "Passkey mode options:\n  -n <int>    number of junk lines to insert (default - 250)\n");
 	fprintf(stderr, "  -l <int>    passkey position (-1 - random)\n");
@@ -107,8 +109,8 @@ static std::vector<int> encode_prompt(const Tokenizer &tok, const std::string &p
 
 static void run_completion(const std::string &path, const std::string &device, const std::string &prompt,
                            int context, int num_steps, float temperature, bool device_sampling, int top_k,
-                           float top_p, int spec_rows, int n_completions, const std::string &draft_path,
-                           const yalm_penalties *pen) {
+                           float top_p, int spec_rows, int n_completions, bool share_prompt,
+                           const std::string &draft_path, const yalm_penalties *pen) {
 	YALMData data;
 	if (data.from_file(path) != 0) {
 		fprintf(stderr, "error: cannot load %s\n", path.c_str());
@@ -229,6 +231,8 @@ static void run_completion(const std::string &path, const std::string &device, c
 	// (sequence 0's BATCH_CHUNK draws, then sequence 1's, ...), a finished sequence included: its
 	// row keeps running and its tokens are dropped, so the others' draws do not depend on it.
 	// A batched step never leaves the window: the completions end at max_seq_len.
+	// --share-prompt: no copy; every sequence attends to the prompt's rows where they are
+	// (yalm_batch_share_prefix), each row read once per step for all the completions.
 	if (n_completions > 0) {
 		constexpr int BATCH_CHUNK = 16;
 		const int N = n_completions, pos0 = (int)encoding.size() - 1;
@@ -243,8 +247,8 @@ static void run_completion(const std::string &path, const std::string &device, c
 			for (int q = 0; q < N; ++q)
 				for (int j = 0; j < chunk; ++j)
 					u[(size_t)q * chunk + j] = uniform();
-			model.generate_batch_sampled(state, N, done == 0 ? pos0 : -1, tok.data(), pos.data(), chunk, temperature, top_k,
-			                             top_p, u.data(), out.data());
+			model.generate_batch_sampled(state, N, done == 0 ? pos0 : -1, share_prompt, tok.data(), pos.data(), chunk,
+			                             temperature, top_k, top_p, u.data(), out.data());
 			for (int q = 0; q < N; ++q) {
 				for (int j = 0; j < chunk && !stopped[q]; ++j) {
 					const int t = out[(size_t)q * chunk + j];
@@ -450,12 +454,17 @@ int main(int argc, char *argv[]) {
 	std::string checkpoint, device = "hip", mode = "completion", prompt, prompt_path, draft_path;
 	int context = 0, num_steps = 256, n_junk = 250, passkey_pos = -1, top_k = 0, spec_rows = 0, n_completions = 0;
 	float temperature = 1.0f, top_p = 1.0f;
-	bool device_sampling = false, penalised = false;
+	bool device_sampling = false, penalised = false, share_prompt = false;
 	yalm_penalties pen{1.0f, 0.0f, 0.0f, 0.0f, -1}; // window -1: not given
 	if (argc < 2)
 		error_usage();
 	checkpoint = argv[1];
 	for (int i = 2; i < argc; i += 2) {
+		if (std::string(argv[i]) == "--share-prompt") { // of -N; takes no value
+			share_prompt = true;
+			--i;
+			continue;
+		}
 		if (i + 1 >= argc || argv[i][0] != '-')
 			error_usage();
 		const std::string v = argv[i + 1], flag = argv[i];
@@ -533,6 +542,8 @@ int main(int argc, char *argv[]) {
 	if (n_completions != 0 && (n_completions < 2 || n_completions > 4 || !(temperature > 0.0f) || !device_sampling ||
 	                           spec_rows != 0 || mode != "completion"))
 		error_usage();
+	if (share_prompt && n_completions == 0)
+		error_usage();
 	// the penalties: the plain device-sampled completion alone (a speculative row's history would
 	// depend on which drafts are accepted, and -N's completions do not share one)
 	if (penalised) {
@@ -566,7 +577,7 @@ int main(int argc, char *argv[]) {
 	try {
 		if (mode == "completion")
 			run_completion(checkpoint, device, prompt, context, num_steps, temperature, device_sampling, top_k, top_p,
-			               spec_rows, n_completions, draft_path, penalised ? &pen : nullptr);
+			               spec_rows, n_completions, share_prompt, draft_path, penalised ? &pen : nullptr);
 		else if (mode == "passkey")
 			run_passkey(checkpoint, device, context, n_junk, passkey_pos);
 		else

@@ -462,8 +462,8 @@ void Model::generate_speculative_sampled(InferenceState &s, int token, int pos, 
 		*plain += st.plain_steps;
 }
 
-void Model::generate_batch_sampled(InferenceState &s, int n_seq, int load, const int *tokens, const int *pos, int n,
-                                   float temperature, int top_k, float top_p, const float *uniforms, int *out) {
+void Model::generate_batch_sampled(InferenceState &s, int n_seq, int load, bool share, const int *tokens, const int *pos,
+                                   int n, float temperature, int top_k, float top_p, const float *uniforms, int *out) {
 	ensure_decoder(s);
 	if (s._batch && s._batch_n != n_seq) {
 		check(yalm_batch_destroy(s._batch), "batch destroy");
@@ -473,7 +473,9 @@ void Model::generate_batch_sampled(InferenceState &s, int n_seq, int load, const
 		check(yalm_batch_create(s._decoder, n_seq, &s._batch), "batch create");
 		s._batch_n = n_seq;
 	}
-	if (load >= 0)
+	if (load >= 0 && share)
+		check(yalm_batch_share_prefix(s._batch, load), "batch share prefix");
+	else if (load >= 0)
 		check(yalm_batch_load(s._batch, -1, load), "batch load");
 	const yalm_sampling sp{temperature, top_k, top_p};
 	check(yalm_batch_generate_sampled(s._batch, tokens, pos, n, &sp, uniforms, out, nullptr), "batched sampled steps");

@@ -289,6 +289,8 @@ _sig("yalm_batch_generate_sampled", c_int, [c_void_p, c_void_p, c_void_p, c_int,
 _sig("yalm_batch_state", c_int, [c_void_p, c_void_p, c_void_p])
 _sig("yalm_batch_set_launch", c_int, [c_void_p, c_int])
 _sig("yalm_batch_buffers", c_int, [c_void_p, c_int, c_int] + [ctypes.POINTER(c_void_p)] * 3)
+_sig("yalm_batch_share_prefix", c_int, [c_void_p, c_int])
+_sig("yalm_attn_batch_prefix", c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] + [c_int] * 3)
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -314,7 +316,7 @@ EXPORTED = [
     "yalm_attn_prefill_rows", "yalm_prefill_stage",
     "yalm_batch_create", "yalm_batch_destroy", "yalm_batch_load", "yalm_batch_forward",
     "yalm_batch_generate_greedy", "yalm_batch_generate_sampled", "yalm_batch_state", "yalm_batch_set_launch",
-    "yalm_batch_buffers",
+    "yalm_batch_buffers", "yalm_batch_share_prefix", "yalm_attn_batch_prefix",
     "yalm_generate_speculative_model", "yalm_decoder_get_stream",
 ]
 BATCH_ATTN_PER_SEQ = 1  # yalm_batch_set_launch
@@ -354,6 +356,23 @@ def matmul(x: np.ndarray, w: np.ndarray, dtype: int) -> np.ndarray:
     w = np.ascontiguousarray(w)
     out = np.zeros(d, np.float32)
     check(lib.yalm_matmul(_ptr(out), _ptr(x), _ptr(w), n, d, dtype))
+    return out
+
+
+def attn_batch_prefix(out, q, k_shared, v_shared, k_seq, v_seq, prefix, kv_len, n_heads, n_kv_heads, head_dim):
+    """yalm_attn_batch_prefix (test hook): out / q (n_seq, n_heads * head_dim) f32, every cache
+    (cache_rows, n_kv_heads * head_dim) f16 bits; row s attends to rows [0, prefix) of the shared
+    caches and to rows [prefix, kv_len[s]) of k_seq[s] / v_seq[s]. Returns out (given, overwritten)."""
+    n_seq = len(k_seq)
+    out = np.ascontiguousarray(out, np.float32)
+    q = np.ascontiguousarray(q, np.float32)
+    caches = [np.ascontiguousarray(a).view(np.uint16) for a in [k_shared, v_shared, *k_seq, *v_seq]]
+    kp = (c_void_p * n_seq)(*[a.ctypes.data for a in caches[2:2 + n_seq]])
+    vp = (c_void_p * n_seq)(*[a.ctypes.data for a in caches[2 + n_seq:]])
+    kl = np.ascontiguousarray(kv_len, np.int32)
+    check(lib.yalm_attn_batch_prefix(_ptr(out), _ptr(q), _ptr(caches[0]), _ptr(caches[1]), kp, vp,
+                                     caches[0].size // (n_kv_heads * head_dim), n_seq, prefix, _ptr(kl), n_heads,
+                                     n_kv_heads, head_dim))
     return out
 
 
@@ -1276,6 +1295,7 @@ class Batch:
         check(lib.yalm_batch_create(decoder.h, n_seq, ctypes.byref(h)))
         self.h = h
         self.launch = 0
+        self.prefix = 0
         if launch:
             self.set_launch(launch)
 
@@ -1293,6 +1313,13 @@ class Batch:
     def load(self, n_positions: int, seq: int = -1) -> None:
         """KV rows [0, n_positions) of the decoder's caches into sequence seq (-1: all)."""
         check(lib.yalm_batch_load(self.h, seq, n_positions))
+
+    def share_prefix(self, n_positions: int) -> None:
+        """yalm_batch_share_prefix: every sequence reads rows [0, n_positions) from the decoder's own
+        caches (no copy; 0 = off). Every later step needs pos[s] >= n_positions, and the decoder's
+        rows below it must stay as they are while they are shared."""
+        check(lib.yalm_batch_share_prefix(self.h, n_positions))
+        self.prefix = n_positions
 
     def forward(self, tokens, pos, logits: bool = True):
         """One step without a commit: row s feeds tokens[s] at pos[s]; logits (n_seq, vocab) or None."""
@@ -1339,9 +1366,9 @@ class Batch:
 
     def stats(self) -> dict:
         """The launch count of one step in the current attention form."""
-        z = np.zeros(self.n_seq, np.int32)
+        z, p = np.zeros(self.n_seq, np.int32), np.full(self.n_seq, self.prefix, np.int32)  # no step below a shared prefix
         st = BatchStats()
-        check(lib.yalm_batch_generate_greedy(self.h, _ptr(z), _ptr(z), 0, None, ctypes.byref(st)))
+        check(lib.yalm_batch_generate_greedy(self.h, _ptr(z), _ptr(p), 0, None, ctypes.byref(st)))
         return {"launches_per_step": st.launches_per_step}
 
     def buffers(self, seq: int, layer: int = 0):
