@@ -45,8 +45,8 @@ enum { YALM_F32 = 0, YALM_F16 = 1, YALM_BF16 = 2, YALM_F8E5M2 = 3 };
  * elements 8 j .. 8 j + 7, element 8 j + i in the nibble at bits 4 * ((i >> 1) + 4 * (i & 1))
  * (models.q4_pack / q4_unpack). Every weight matrix of a q4 model, the embedding included,
  * has this layout; norms stay f32. Dense one-GPU decoders only: yalm_decoder_create,
- * yalm_forward, the greedy / sampled loops, yalm_block, yalm_prefill (through a per-layer
- * exact f16 upcast, as fp8), yalm_matmul, yalm_ffn, yalm_time_kernel, yalm_set_gemv_config.
+ * yalm_forward, the greedy / sampled loops, yalm_block, yalm_prefill (the rows as stored up to
+ * 64 positions; for more than 64 through a per-layer exact f16 upcast, as fp8), yalm_matmul, yalm_ffn, yalm_time_kernel, yalm_set_gemv_config.
  * Attention and Wo run as separate launches (yalm_attn_wo_plan returns 0).
  * YALM_ERR_UNSUPPORTED, with a yalm_last_error naming q4: yalm_decoder_create_moe,
  * yalm_decoder_create_tp, yalm_decoder_create_tp_ipc, yalm_moe_ffn, yalm_moe_ffn_rows.
@@ -66,7 +66,8 @@ enum { YALM_Q4 = 16 };
  * weight matrix of an e4m3 model, the embedding included, has this layout; norms, biases and
  * q / k norm gains stay f32. Dense one-GPU decoders only: yalm_decoder_create, yalm_forward,
  * the greedy / sampled loops, yalm_block, yalm_forward_rows, yalm_generate_speculative,
- * yalm_prefill (through a per-layer exact f16 upcast, as fp8), yalm_matmul, yalm_matmul_rows,
+ * yalm_prefill (the rows as stored up to 64 positions; for more than 64 through a per-layer exact
+ * f16 upcast, as fp8), yalm_matmul, yalm_matmul_rows,
  * yalm_ffn, yalm_time_kernel, yalm_set_gemv_config. Attention and Wo fuse where the Wo row is
  * 4096 or 8192 codes (yalm_attn_wo_plan).
  * YALM_ERR_UNSUPPORTED, with a yalm_last_error naming e4m3: yalm_decoder_create_moe,
@@ -484,7 +485,9 @@ int yalm_copy_2d(void *dst, size_t dst_pitch, const void *src, size_t src_pitch,
  * pos0 + n. logprobs (host, n floats, may be NULL): logprobs[i] =
  * log softmax(logits at position pos0 + i)[tokens[i + 1]] for i < n - 1 (the
  * quantity main.cpp:155 sums), logprobs[n - 1] = 0. Requires f16 weights (fp8, e4m3 and q4:
- * through an exact f16 upcast of one layer at a time),
+ * up to 64 positions a dense decoder's GEMMs read the weights as stored and convert them
+ * in registers; for more than 64 positions, for the log-prob classifier and for expert models,
+ * through an exact f16 upcast of one layer at a time; both compute the f16 twin's bits),
  * dims multiple of 128, head_dim 64 | 128 and pos0 + n <= max_seq_len
  * (the sliding window past max_seq_len stays on the decode path).
  * Synchronous. Activations are rounded to f16 for the MFMA inputs: results
@@ -527,7 +530,9 @@ int yalm_prefill_time(yalm_decoder d, int n, int iters, float *avg_ms);
  * defaults: qkv|wo|glu|w2|cls|test:<128|192|256|320> force that GEMM's tile width;
  * 8p:0 the 2-phase kernel; persist:0 one workgroup per tile; skinny:0 the large tiles
  * for T <= 64 too; qkv1:0 the q and k|v GEMMs as two launches; skl:0 the skinny GEMMs'
- * weights as register loads; wnorm:0 the row norms as one workgroup per row (default:
+ * f16 weights as register loads (no effect on the native-weight form, which has one
+ * weight-movement form); skq:0 the skinny GEMMs of a dense fp8 / e4m3 / q4 decoder through
+ * the per-layer f16 upcast (default: the weights as stored); wnorm:0 the row norms as one workgroup per row (default:
  * one wave per row). Every GEMM form is exact against the others (tests). An
  * unknown key is YALM_ERR_ARG. */
 int yalm_set_prefill_forms(yalm_decoder d, const char *spec);
@@ -887,6 +892,13 @@ int yalm_sample_ex(const float *logits, int n, const yalm_sampling *s, const yal
 /* Prefill building blocks (host pointers, synchronous):
  * c[M][N] f32 = a[M][K] f16 · w[N][K]^T f16 (the MFMA GEMM; N % 128 == 0, K % 64 == 0). */
 int yalm_gemm_f16(float *c, const uint16_t *a, const uint16_t *w, int M, int N, int K);
+/* c[M][N] f32 = a[M][K] f16 · W^T, W [N] rows of yalm_row_bytes(dtype, K) bytes in dtype
+ * (YALM_F8E5M2, YALM_Q4, YALM_E4M3), through the launches a decoder's prefill makes for
+ * one plain GEMM at T = M under the forms of yalm_set_prefill_forms(NULL, ...);
+ * *native (may be NULL) = 1 when the native-weight skinny kernel ran, 0 when the upcast did.
+ * N % 64 == 0, K % 64 == 0; where the large tiles run (M > 64, skinny:0, K % 256 != 0) N
+ * must also divide by a tile width. */
+int yalm_gemm_wq(float *c, const uint16_t *a, const void *w, int dtype, int M, int N, int K, int *native);
 /* The grouped GEMM of the mixture-of-experts prefill: c[r] = a[r] . w[expert_of_row[r]]^T,
  * w (E, N, K) f16, through the device grouping pass, the M-tile table and the grouped tile
  * kernels (plain store in slot order, scattered back to row order); follows the forms of

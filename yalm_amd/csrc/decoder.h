@@ -110,6 +110,8 @@ struct PfForms {
 	bool no_skinny = false; // T <= 64: split-K skinny GEMMs (prefill_skinny.h) unless set
 	bool qkv1 = true;       // the q and k | v GEMMs as ONE two-depth launch when BN 256 fits both
 	bool skl = true;        // skinny GEMMs: weight rows staged by LDS-DMA (prefill_skinny.h)
+	bool skq = true;        // skinny GEMMs of a dense fp8 / e4m3 / q4 decoder: the weights streamed as stored
+							// (prefill_skinny_wq.h); false: through the per-layer f16 upcast, as at T > 64
 	bool split = false;     // split-operand precision form (yalm_set_prefill_precision): every f16
 							// activation operand as [hi | lo], the large-tile GEMMs at every T
 	bool wnorm = true;      // row norms: one wave per row, the row in registers (rmsnorm_rows_wave_kernel)

@@ -19,6 +19,7 @@
 #include "moe_prefill.h"
 #include "prefill_gemm.h"
 #include "prefill_skinny.h"
+#include "prefill_skinny_wq.h"
 
 // Large-tile GEMM form per GEMM kind (prefill_gemm.h): the tile width BN of the
 // 256-row tile. Default: auto -- the BN dividing N that minimises rounds x (BN + 64),
@@ -27,7 +28,8 @@
 // explicitly through yalm_set_prefill_forms: "qkv:256,wo:128,..." forces widths, 8p:0
 // the 2-phase kernel, persist:0 one workgroup per tile, skinny:0 the large tiles at
 // T <= 64 too (prefill_skinny.h otherwise), qkv1:0 the q and k | v GEMMs as two
-// launches, skl:0 the skinny GEMMs' weights as register loads instead of LDS-DMA stages,
+// launches, skl:0 the skinny GEMMs' f16 weights as register loads instead of LDS-DMA stages,
+// skq:0 a quantised decoder's skinny GEMMs over the f16 upcast (prefill_skinny_wq.h otherwise),
 // wnorm:0 the workgroup-per-row norm kernel instead of one wave per row.
 // The production library reads no environment for them; the A/B build (-DYALM_AB)
 // takes a decoder's initial forms from YALM_PF_FORMS (same syntax).
@@ -62,6 +64,8 @@ static int parse_pf_forms(const char *spec, PfForms &f) {
 			f.qkv1 = val != 0, known = true;
 		else if (!strcmp(key, "skl"))
 			f.skl = val != 0, known = true;
+		else if (!strcmp(key, "skq"))
+			f.skq = val != 0, known = true;
 		else if (!strcmp(key, "split"))
 			f.split = val != 0, known = true;
 		else if (!strcmp(key, "wnorm"))
@@ -296,6 +300,61 @@ int launch_skinny(const PfForms &f, const uint16_t *A, int lda, int T, int K, in
 	default:
 		return launch_skinny_mt<4>(f, A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
 	}
+}
+
+// The same GEMM over weight rows in their stored format WT (prefill_skinny_wq.h): one
+// weight-movement form (LDS-DMA stages), so skl does not apply
+template <int MT, class BMAP, class WT>
+int launch_skinny_wq_mt(const uint16_t *A, int lda, int T, int K, int kb, const BMAP &bm, int N, int KS, int c0, int Np,
+                        float *part, hipStream_t st) {
+	auto kern = pf::skinny_gemm_wq_kernel<MT, BMAP, WT>;
+	constexpr size_t ring = pf::SkqGeo<WT>::RING_BYTES;
+	static bool attr = false;
+	if (!attr) {
+		HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 32768 + (int)ring));
+		attr = true;
+	}
+	const int KC = K / KS;
+	const size_t lds = (size_t)16 * MT * KC * sizeof(uint16_t) + ring;
+	hipLaunchKernelGGL(kern, dim3((N / pf::SK_ROWS) * KS), dim3(256), lds, st, A, lda, T, K, kb, bm, N, KC, c0, Np,
+	                   part);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+template <class BMAP, class WT>
+int launch_skinny_wq_t(const uint16_t *A, int lda, int T, int K, int kb, const BMAP &bm, int N, int KS, int c0, int Np,
+                       float *part, hipStream_t st) {
+	switch ((T + 15) / 16) {
+	case 1:
+		return launch_skinny_wq_mt<1, BMAP, WT>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	case 2:
+		return launch_skinny_wq_mt<2, BMAP, WT>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	case 3:
+		return launch_skinny_wq_mt<3, BMAP, WT>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	default:
+		return launch_skinny_wq_mt<4, BMAP, WT>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	}
+}
+// wdt: YALM_F8E5M2, YALM_E4M3 or YALM_Q4; bm: a row policy over rows of yalm_row_bytes(wdt, kb) bytes
+template <class BMAP>
+int launch_skinny_wq(int wdt, const uint16_t *A, int lda, int T, int K, int kb, const BMAP &bm, int N, int KS, int c0,
+                     int Np, float *part, hipStream_t st) {
+	if (wdt == YALM_F8E5M2)
+		return launch_skinny_wq_t<BMAP, WF8>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	if (wdt == YALM_E4M3)
+		return launch_skinny_wq_t<BMAP, WE4M3>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	if (wdt == YALM_Q4)
+		return launch_skinny_wq_t<BMAP, WQ4>(A, lda, T, K, kb, bm, N, KS, c0, Np, part, st);
+	set_err("skinny GEMM: no native-weight kernel for this weight type");
+	return YALM_ERR_UNSUPPORTED;
+}
+// A skinny GEMM over plain rows b (q | k | v segments, or one matrix) of weight type wdt: f16
+// through the forms' kernel, a quantised type as stored
+int launch_skinny_rows(const PfForms &f, int wdt, const uint16_t *A, int lda, int T, int K, int kb, const pf::BSrc &b,
+                       int N, int KS, int c0, int Np, float *part, hipStream_t st) {
+	if (wdt == YALM_F16)
+		return launch_skinny(f, A, lda, T, K, kb, pf::BRowsPlain{b}, N, KS, c0, Np, part, st);
+	return launch_skinny_wq(wdt, A, lda, T, K, kb, pf::BRowsPlainQ{b, yalm_row_bytes(wdt, kb)}, N, KS, c0, Np, part, st);
 }
 
 // columns < c_split sum KS partials, the others KS2
@@ -706,6 +765,7 @@ struct PfQkv {
 	float clip;
 	bool small;
 	int ks;
+	int wdt = YALM_F16; // the weights' type: f16, or (small alone) fp8 / e4m3 / q4 rows as stored
 };
 // every form over the epilogue with or without the q / k / v bias (yalm_decoder_set_qkv_bias): a
 // compile-time flag, so an unbiased model runs the instantiations it always ran
@@ -740,11 +800,10 @@ int enqueue_qkv(const PfForms &f, const PfQkv &a, hipStream_t st) {
 	// two GEMMs: q (K = dim over hi) and k | v from column q_dim (K = 2 dim over hi | lo, the
 	// B rows wrapping at dim)
 	if (a.small) {
-		const pf::BRowsPlain bm{qkv};
 		const int np = q_dim + 2 * kv_dim;
 		note_skinny(f, a.ks, 2 * a.ks);
-		TRY(launch_skinny(f, a.Xn, 2 * dim, T, dim, dim, bm, q_dim, a.ks, 0, np, a.skp, st));
-		TRY(launch_skinny(f, a.Xn, 2 * dim, T, 2 * dim, dim, bm, 2 * kv_dim, 2 * a.ks, q_dim, np, a.skp, st));
+		TRY(launch_skinny_rows(f, a.wdt, a.Xn, 2 * dim, T, dim, dim, qkv, q_dim, a.ks, 0, np, a.skp, st));
+		TRY(launch_skinny_rows(f, a.wdt, a.Xn, 2 * dim, T, 2 * dim, dim, qkv, 2 * kv_dim, 2 * a.ks, q_dim, np, a.skp, st));
 		TRY(launch_skinny_reduce<false>(a.skp, a.ks, 2 * a.ks, q_dim, T, np, e, st));
 	} else if (f.split) { // q | k | v all over [hi | lo], Q stored [hi | lo]
 		pf::E16QKVt<true, B> es;
@@ -768,8 +827,9 @@ int enqueue_qkv(const PfForms &f, const PfQkv &a, hipStream_t st) {
 
 // X[t] += scale * A[t] . W^T over T rows (Wo: kind PG_WO, W2: PG_W2): A [T][sp K] f16 ([hi | lo]
 // in the split-operand form), W [N][K], X [.][N] f32. small / ks: pf_small and sk_ks(N, K, T).
+// wdt: W's type, f16 or (small alone) a quantised type as stored.
 int enqueue_residual(const PfForms &f, int kind, const uint16_t *A, int T, int K, const void *w, int N, float *X,
-                     float scale, bool small, int ks, float *skp, hipStream_t st) {
+                     float scale, bool small, int ks, float *skp, hipStream_t st, int wdt = YALM_F16) {
 	pf::E16Residual e;
 	e.x = X;
 	e.ldx = N;
@@ -777,7 +837,7 @@ int enqueue_residual(const PfForms &f, int kind, const uint16_t *A, int T, int K
 	e.scale = scale;
 	if (small) {
 		note_skinny(f, ks, ks);
-		TRY(launch_skinny(f, A, K, T, K, K, pf::BRowsPlain{one(w, N)}, N, ks, 0, N, skp, st));
+		TRY(launch_skinny_rows(f, wdt, A, K, T, K, K, one(w, N), N, ks, 0, N, skp, st));
 		return launch_skinny_reduce<false>(skp, ks, ks, N, T, N, e, st);
 	}
 	const int sp = f.split ? 2 : 1;
@@ -808,14 +868,20 @@ int launch_glu_t(const PfForms &f, const uint16_t *Xn, int dim, int hidden, cons
 	return YALM_ERR_UNSUPPORTED;
 }
 
-// small / ks: pf_small and sk_ks(2 hidden, dim, T)
+// small / ks: pf_small and sk_ks(2 hidden, dim, T); wdt: W1 / W3's type, as enqueue_residual
 template <int ACT>
 int enqueue_glu_act(const PfForms &f, const uint16_t *Xn, int dim, int hidden, const void *w1, const void *w3, int T,
-                    float hscale, unsigned *range, uint16_t *H, bool small, int ks, float *skp, hipStream_t st) {
+                    float hscale, unsigned *range, uint16_t *H, bool small, int ks, float *skp, hipStream_t st,
+                    int wdt) {
 	if (small) {
-		const pf::BRowsGlu<64> bm{(const uint16_t *)w1, (const uint16_t *)w3};
 		note_skinny(f, ks, ks);
-		TRY(launch_skinny(f, Xn, dim, T, dim, dim, bm, 2 * hidden, ks, 0, 2 * hidden, skp, st));
+		if (wdt == YALM_F16) {
+			const pf::BRowsGlu<64> bm{(const uint16_t *)w1, (const uint16_t *)w3};
+			TRY(launch_skinny(f, Xn, dim, T, dim, dim, bm, 2 * hidden, ks, 0, 2 * hidden, skp, st));
+		} else {
+			const pf::BRowsGluQ<64> bm{(const char *)w1, (const char *)w3, yalm_row_bytes(wdt, dim)};
+			TRY(launch_skinny_wq(wdt, Xn, dim, T, dim, dim, bm, 2 * hidden, ks, 0, 2 * hidden, skp, st));
+		}
 		pf::E16Glu<ACT> e;
 		e.h = H, e.ldh = hidden, e.M = T, e.hscale = hscale, e.range = range;
 		return launch_skinny_reduce<true>(skp, ks, ks, 2 * hidden, T, 2 * hidden, e, st);
@@ -824,9 +890,10 @@ int enqueue_glu_act(const PfForms &f, const uint16_t *Xn, int dim, int hidden, c
 	               : launch_glu_t<ACT, false>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, st);
 }
 int enqueue_glu(const PfForms &f, int act, const uint16_t *Xn, int dim, int hidden, const void *w1, const void *w3,
-                int T, float hscale, unsigned *range, uint16_t *H, bool small, int ks, float *skp, hipStream_t st) {
-	return act == YALM_SILU ? enqueue_glu_act<1>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, small, ks, skp, st)
-	                        : enqueue_glu_act<0>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, small, ks, skp, st);
+                int T, float hscale, unsigned *range, uint16_t *H, bool small, int ks, float *skp, hipStream_t st,
+                int wdt = YALM_F16) {
+	return act == YALM_SILU ? enqueue_glu_act<1>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, small, ks, skp, st, wdt)
+	                        : enqueue_glu_act<0>(f, Xn, dim, hidden, w1, w3, T, hscale, range, H, small, ks, skp, st, wdt);
 }
 
 // The logits GEMM's per-tile (max, sum exp, target logit) and log p(target) per row: Xn [T][sp dim],
@@ -886,11 +953,15 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	// each GEMM over K = 2 x its depth with the B rows wrapping (prefill_gemm.h), so no operand
 	// carries an f16 rounding the reference's f32 lacks
 	const bool split = f.split;
+	// a dense quantised decoder's short prompt: the skinny GEMMs read the weights as stored
+	// (prefill_skinny_wq.h), no f16 copy of the layer; wdt is the type the GEMMs are handed
+	const bool native = small && !moe && f.skq && (fp8 || q4 || e4m3);
+	const int wdt = native ? c.weight_dtype : YALM_F16;
 	const int bn_qkv_all = pick_bn(f, PG_QKV, T, q_dim + 2 * kv_dim, false);
 	for (int l = 0; l < c.n_layers; ++l) {
 		yalm_block_weights w = d->b[l];
 		const uint16_t *gate16 = nullptr; // fp8 expert models: the router's gate as f16
-		if (fp8) { // this layer's weights as f16 (exact), in the scratch the previous layer's GEMMs are done with
+		if (fp8 && !native) { // this layer's weights as f16 (exact), in the scratch the previous layer's GEMMs are done with
 			const uint16_t *p[8];
 			const size_t qd = (size_t)q_dim * c.dim, kd = (size_t)kv_dim * c.dim;
 			const size_t hd = (size_t)c.hidden_dim * c.dim * (moe ? d->moe_E : 1);
@@ -902,7 +973,7 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			w.wq = p[0], w.wk = p[1], w.wv = p[2], w.wo = p[3], w.w1 = p[4], w.w2 = p[5], w.w3 = p[6];
 			gate16 = moe ? p[7] : nullptr;
 		}
-		if (q4 || e4m3) { // the same for a q4 or e4m3 layer (dense only)
+		if ((q4 || e4m3) && !native) { // the same for a q4 or e4m3 layer (dense only)
 			const uint16_t *p[7];
 			const size_t qr = (size_t)q_dim, kr = (size_t)kv_dim, hr = (size_t)c.hidden_dim, dr = (size_t)c.dim;
 			TRY((e4m3 ? dequant_e4m3_into : dequant_q4_into)(d->pf.wdq, {{w.wq, qr, c.dim}, {w.wk, kr, c.dim}, {w.wv, kr, c.dim}, {w.wo, dr, q_dim},
@@ -927,7 +998,7 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			qa.Q = b.Q, qa.kc = (uint16_t *)w.key_cache, qa.vc = (uint16_t *)w.value_cache;
 			qa.range = rg + RG_Q, qa.skp = b.skp;
 			qa.dim = c.dim, qa.q_dim = q_dim, qa.kv_dim = kv_dim, qa.head_dim = c.head_dim, qa.T = T, qa.pos0 = pos0;
-			qa.clip = c.qkv_clip, qa.small = small, qa.ks = ks_qkv;
+			qa.clip = c.qkv_clip, qa.small = small, qa.ks = ks_qkv, qa.wdt = wdt;
 			if (!d->bq.empty())
 				qa.bq = d->bq[l], qa.bk = d->bk[l], qa.bv = d->bv[l];
 			// a q / k normed model (Qwen3; never biased): every form leaves raw f32 q | k | v rows --
@@ -941,10 +1012,9 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 				e.ldc = np;
 				e.M = T;
 				if (small) {
-					const pf::BRowsPlain bm{qkv};
-					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, c.dim, c.dim, bm, q_dim, ks_qkv, 0, np, b.skp, st));
-					TRY(launch_skinny(f, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, bm, 2 * kv_dim, 2 * ks_qkv, q_dim, np, b.skp,
-					                  st));
+					TRY(launch_skinny_rows(f, wdt, b.Xn, 2 * c.dim, T, c.dim, c.dim, qkv, q_dim, ks_qkv, 0, np, b.skp, st));
+					TRY(launch_skinny_rows(f, wdt, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, 2 * kv_dim, 2 * ks_qkv, q_dim,
+					                       np, b.skp, st));
 					TRY(launch_skinny_reduce<false>(b.skp, ks_qkv, 2 * ks_qkv, q_dim, T, np, e, st));
 				} else {
 					TRY(launch_plain(f, bn_qkv_all, b.Xn, 2 * c.dim, T, 2 * c.dim, c.dim, qkv, np, e, st));
@@ -964,7 +1034,7 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 		}
 		TRY(launch_attn_prefill(b.Q, w.key_cache, w.value_cache, T, pos0, c.n_heads, c.n_kv_heads, c.head_dim, b.O,
 								st, split));
-		TRY(enqueue_residual(f, PG_WO, b.O, T, q_dim, w.wo, c.dim, b.X, 1.0f, small, ks_wo, b.skp, st));
+		TRY(enqueue_residual(f, PG_WO, b.O, T, q_dim, w.wo, c.dim, b.X, 1.0f, small, ks_wo, b.skp, st, wdt));
 		TRY(launch_rmsnorm(split, f, b.X, w.rms_ffn, c.dim, T, c.norm_eps, b.Xn, rg + RG_XFFN, st));
 		const float hscale = ldexpf(1.0f, -he);
 		if (moe) {
@@ -982,8 +1052,9 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 			continue;
 		}
 		TRY(enqueue_glu(f, c.act, b.Xn, c.dim, c.hidden_dim, w.w1, w.w3, T, hscale, rg + RG_H, b.H, small, ks_glu, b.skp,
-		                st));
-		TRY(enqueue_residual(f, PG_W2, b.H, T, c.hidden_dim, w.w2, c.dim, b.X, ldexpf(1.0f, he), small, ks_w2, b.skp, st));
+		                st, wdt));
+		TRY(enqueue_residual(f, PG_W2, b.H, T, c.hidden_dim, w.w2, c.dim, b.X, ldexpf(1.0f, he), small, ks_w2, b.skp, st,
+		                     wdt));
 	}
 	if (!want_lp)
 		return YALM_OK;
@@ -1140,6 +1211,49 @@ extern "C" int yalm_gemm_f16(float *c, const uint16_t *a, const uint16_t *w, int
 	                 nullptr));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(c, dc.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+	return YALM_OK;
+}
+
+extern "C" int yalm_gemm_wq(float *c, const uint16_t *a, const void *w, int dtype, int M, int N, int K, int *native) {
+	ARGCHK(c && a && w && M > 0 && N > 0 && K > 0, "yalm_gemm_wq: bad argument");
+	ARGCHK(dtype == YALM_F8E5M2 || dtype == YALM_Q4 || dtype == YALM_E4M3, "yalm_gemm_wq: dtype is fp8, q4 or e4m3");
+	ARGCHK(N % pf::SK_ROWS == 0 && K % pf::BK == 0, "yalm_gemm_wq: N % 64 and K % 64 must be 0");
+	const size_t rb = yalm_row_bytes(dtype, K);
+	HostDev da, dw, dq, dc, dp;
+	TRY(hd(da, a, (size_t)M * K * 2));
+	TRY(hd(dw, w, (size_t)N * rb));
+	TRY(hd(dc, nullptr, (size_t)M * N * 4));
+	pf::E16StoreF32 e16;
+	e16.c = (float *)dc.p;
+	e16.ldc = N;
+	e16.M = M;
+	const PfForms f = g_test_forms; // a test hook: the forms set by yalm_set_prefill_forms(NULL, ...)
+	const int ks = sk_ks(N, K, M);
+	const bool small = pf_small(f, M, {ks}), nat = small && f.skq;
+	const void *w16 = dw.p;
+	if (!nat) { // the decoder's upcast of the matrix
+		const uint16_t *p[1];
+		TRY(hd(dq, nullptr, (size_t)N * K * 2));
+		if (dtype == YALM_F8E5M2)
+			TRY(dequant_into((uint16_t *)dq.p, {{dw.p, (size_t)N * K}}, p, nullptr));
+		else
+			TRY((dtype == YALM_E4M3 ? dequant_e4m3_into : dequant_q4_into)((uint16_t *)dq.p, {{dw.p, (size_t)N, K}}, p,
+			                                                                 nullptr));
+		w16 = dq.p;
+	}
+	if (small) {
+		TRY(hd(dp, nullptr, (size_t)ks * 16 * ((M + 15) / 16) * N * 4));
+		TRY(launch_skinny_rows(f, nat ? dtype : YALM_F16, (const uint16_t *)da.p, K, M, K, K, one(w16, N), N, ks, 0, N,
+		                       (float *)dp.p, nullptr));
+		TRY(launch_skinny_reduce<false>((const float *)dp.p, ks, ks, N, M, N, e16, nullptr));
+	} else {
+		TRY(launch_plain(f, pick_bn(f, PG_TEST, M, N, false), (const uint16_t *)da.p, K, M, K, K, one(w16, N), N, e16,
+		                 nullptr));
+	}
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(c, dc.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+	if (native)
+		*native = nat;
 	return YALM_OK;
 }
 

@@ -252,6 +252,7 @@ _sig("yalm_prefill_time", c_int, [c_void_p, c_int, c_int, ctypes.POINTER(c_float
 _sig("yalm_prefill_info", c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)])
 _sig("yalm_set_prefill_precision", c_int, [c_void_p, c_int])
 _sig("yalm_gemm_f16", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int])
+_sig("yalm_gemm_wq", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)])
 _sig("yalm_attn_prefill", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int])
 _sig("yalm_attn_prefill_rows", c_int, [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 7)
 _sig("yalm_set_prefill_forms", c_int, [c_void_p, ctypes.c_char_p])
@@ -298,7 +299,7 @@ EXPORTED = [
     "yalm_synth", "yalm_decoder_create", "yalm_decoder_destroy", "yalm_forward", "yalm_generate_greedy",
     "yalm_enqueue_greedy", "yalm_device_step", "yalm_device_tokens", "yalm_block", "yalm_get_x", "yalm_set_x", "yalm_get_logits",
     "yalm_time_kernel", "yalm_kernel_name", "yalm_set_gemv_config", "yalm_matmul", "yalm_mha", "yalm_ffn",
-    "yalm_prefill", "yalm_prefill_time", "yalm_gemm_f16", "yalm_attn_prefill", "yalm_tp_unique_id",
+    "yalm_prefill", "yalm_prefill_time", "yalm_gemm_f16", "yalm_gemm_wq", "yalm_attn_prefill", "yalm_tp_unique_id",
     "yalm_decoder_create_tp", "yalm_copy_2d", "yalm_tp_ipc_alloc", "yalm_decoder_create_tp_ipc",
     "yalm_decoder_attn_wo", "yalm_attn_wo_trace", "yalm_stream_envelope",
     "yalm_argmax", "yalm_set_prefill_forms", "yalm_attn_wo_plan", "yalm_graph_kernels",
@@ -547,6 +548,20 @@ def gemm_f16(a: np.ndarray, w: np.ndarray) -> np.ndarray:
     c = np.zeros((M, N), np.float32)
     check(lib.yalm_gemm_f16(_ptr(c), _ptr(a), _ptr(w), M, N, K))
     return c
+
+
+def gemm_wq(a: np.ndarray, w: np.ndarray, dtype: int):
+    """a (M, K) f16 @ W^T -> ((M, N) f32, native): w holds W's N rows in `dtype` (fp8, q4 or e4m3) as stored,
+    (N, row_bytes(dtype, K)) bytes, through the launches of a decoder's prefill GEMM at T = M
+    (yalm_gemm_wq); native: the native-weight skinny kernel ran, not the f16 upcast."""
+    a = np.ascontiguousarray(a, dtype=np.float16)
+    (m, K), N = a.shape, w.shape[0]
+    w = np.ascontiguousarray(w).view(np.uint8).reshape(N, -1)
+    assert w.shape[1] == M.row_bytes(dtype, K), "gemm_wq: w is not (N, row_bytes(dtype, K)) bytes"
+    c = np.zeros((m, N), np.float32)
+    native = c_int(-1)
+    check(lib.yalm_gemm_wq(_ptr(c), _ptr(a), _ptr(w), dtype, m, N, K, ctypes.byref(native)))
+    return c, bool(native.value)
 
 
 def moe_gemm_f16(a: np.ndarray, w: np.ndarray, expert_of_row: np.ndarray) -> np.ndarray:
