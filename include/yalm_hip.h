@@ -857,6 +857,58 @@ int yalm_gemv_one(const yalm_gemv_args *args);
  * probabilities for t < kv_len. */
 int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint16_t *vb, const float *q, int head_dim, int kv_len,
              int max_seq_len, int n_heads, int n_kv_heads);
+/* A sequence of fused attention + Wo launches (attn_wo.h), the decoder's own -- the launcher the
+ * forward pass, yalm_block and yalm_time_kernel 8 call -- on host arrays over ONE set of device
+ * buffers, synchronous, without a decoder. head_dim is 128. Wo is `dim` rows of yalm_row_bytes(dtype,
+ * n_heads * 128) in dtype (YALM_F16, YALM_F8E5M2 or YALM_E4M3); kcache / vcache are max_seq_len rows
+ * of n_kv_heads * 128 f16, uploaded once.
+ * Geometry: S key splits per kv head, 1..32 (taken down to the window's 64-key chunks, as the plan
+ * does); 0 = the value yalm_attn_wo_plan returns for `slots` co-resident workgroups, and slots 0 =
+ * this device's occupancy x CUs, as a decoder takes it. head_max, the partial stride and the grid
+ * follow from them by the decoder's own code. delay: ticks of 10 ns the Wo workgroups wait before
+ * their slice loads, -1 = the decoder's default for the type. S_out / grid_out (may be NULL)
+ * receive the key splits and the grid used. A forced S is not held to the co-resident slots: the
+ * grid may exceed them (n_kv_heads 32 at S 32 does), which costs time and not correctness --
+ * workgroups are dispatched in index order and no attention or merger workgroup waits on a later
+ * one, so every workgroup a Wo workgroup waits for was dispatched before it (attn_wo.h).
+ * Not reached by this hook: the last Wo slice shifted back over the rows of the slice before it
+ * (a dim that is no multiple of 16, which the hook refuses): no one-launch test covers that tail.
+ * Launch i of n_launch (1..8) runs at kv_len[i], epoch epoch0 + i (epoch0 >= 1) for `layer` of
+ * n_layers (partial tag (epoch0 + i) * n_layers + layer, as in a forward), on q[i] (n_heads * 128
+ * floats) and x[i] (dim floats, the residual going in). The partial buffer and the granule buffer
+ * (n_layers * n_heads * 128 granules, this layer's slice in use) are zeroed once per call and NOT
+ * cleared between launches, as in a decoder.
+ * out is [n_launch][dim], uploaded as given between two guard rows of 0xA5 bytes and returned
+ * whole. alias 1: launch i's out row IS its x row (the one-GPU form; the row starts as x[i], x is
+ * not written); alias 0: a separate buffer (the RCCL-partial form) and x is returned too -- it must
+ * come back as it went in. add_base 1: out = x + Wo a; 0: out = Wo a (alias 0 only). gran_out
+ * ([n_launch][n_heads * 128] 64-bit words, may be NULL): this layer's granules read back after each
+ * launch, value in the low word, tag in the high word. err_out (may be NULL): the error word after
+ * the last launch.
+ * YALM_ERR_ARG before anything is uploaded or launched: a NULL array, dim below 16 or no multiple of
+ * 16, a kv_len outside [1, max_seq_len], S outside 0..32, n_launch outside 1..8, epoch0 < 1, layer
+ * outside [0, n_layers), add_base 0 with alias 1. YALM_ERR_UNSUPPORTED where yalm_attn_wo_plan does
+ * not fuse the shape (a Wo row that is not 1, 2, 4 or 8 KiB, e4m3 below 4 KiB, G above 8).
+ * YALM_ERR_HIP, in the words of the decoder's own check, if an error bit is set (a bounded wait gave
+ * up), or if a guard row was written.
+ * Out of scope: the IPC push of the rows (push.n > 0 needs exchange buffers and peers) and the
+ * trace buffer. */
+typedef struct {
+	int dtype, n_heads, n_kv_heads, dim, max_seq_len;
+	int S, slots, delay;
+	int n_launch, epoch0, layer, n_layers;
+	int add_base, alias;
+	const int *kv_len;
+	const float *q;
+	float *x;
+	const uint16_t *kcache, *vcache;
+	const void *wo;
+	float *out;
+	unsigned long long *gran_out;
+	unsigned *err_out;
+	int *S_out, *grid_out;
+} yalm_attn_wo_args;
+int yalm_attn_wo_one(const yalm_attn_wo_args *args);
 /* ffn_cuda: xout = W2 (act(W1 x) * W3 x). */
 int yalm_ffn(float *xout, const float *x, const void *w1, const void *w2, const void *w3, int hidden_dim, int dim,
              int act, int dtype);

@@ -85,8 +85,9 @@ struct AttnWoArgs {
 // load to see each granule whole (never the new tag with the old value). The HIP
 // memory model does not promise this for a plain asm load racing an atomic store;
 // gfx950 delivers it (MI355X_MICROARCH.md:190, "observed untorn on gfx950 / ROCm
-// 7.2, also for 16-B sc1"), and tests/test_gpu_attn_wo.py::test_attn_wo_stress
-// replays many forwards at high split counts against the separate-launch path.
+// 7.2, also for 16-B sc1"), and tests/test_gpu_attn_wo.py::test_attn_wo_stress_vs_separate
+// replays many forwards at high split counts against the separate-launch path;
+// tests/test_gpu_attn_wo_one.py checks the gather directly, one launch at a time.
 __device__ __forceinline__ void awo_ld8_sc1(u32x4_t (&v)[8], const void *const (&a)[8]) {
 	asm volatile("global_load_dwordx4 %0, %8, off sc1\n\t"
 	             "global_load_dwordx4 %1, %9, off sc1\n\t"

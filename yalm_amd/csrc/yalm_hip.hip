@@ -663,6 +663,26 @@ static const void *attn_wo_pick(int dtype, int G, int KB) {
 		return KB == 4 ? attn_wo_fn_g<WE4M3, 4>(G) : attn_wo_fn_g<WE4M3, 8>(G);
 	return dtype == YALM_F16 ? attn_wo_fn_kb<WF16>(G, KB) : attn_wo_fn_kb<WF8>(G, KB);
 }
+// head + split units, one merger per query head, then the Wo workgroups (attn_wo.h)
+static int attn_wo_grid(int n_heads, int n_kv, int S, int dim) {
+	return n_kv * (S + n_heads / n_kv - 1) + n_heads + (dim + AWO_RPW - 1) / AWO_RPW;
+}
+// co-resident workgroup slots of the launch's kernel on this device (0: the query failed)
+static int attn_wo_slots(int dtype, int G, int KB) {
+	int occ = 0; // the Wo workgroups spin, but only on attention workgroups dispatched before them
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, attn_wo_pick(dtype, G, KB), ATTN_THREADS, 0) != hipSuccess ||
+	    occ < 1)
+		return 0;
+	return occ * device_cu_count();
+}
+// default 0.2 us (fp16) / 0.5 us (fp8): the attention workgroups' K/V loads reach HBM
+// ahead of the Wo stream. fp16 (33.5 MB, slice lands ~5.4 us, after the heads):
+// profiles/r2_sweep_awo_delay.txt 10.6 -> 10.1 us at kv_len 17. fp8 (16.8 MB, slice lands
+// ~3.1 us, before the heads): 0.5 us gives 9.4 -> 8.4 us at kv 17, 11.3 -> 10.3 at kv 151,
+// 579 -> 586 tok/s (profiles/r3_ab_awo_delay.txt); fp16 at 0.5 us is within noise
+static int attn_wo_default_delay(int dtype) {
+	return dtype == YALM_F8E5M2 || dtype == YALM_E4M3 ? 50 : 20; // (e4m3: the same slice bytes)
+}
 // The fused launch's plan for a (per-rank) config: 1 with the key splits S and the grid,
 // or 0 = separate attention and Wo launches. Fused needs head_dim 128, G <= 8, fp16 / fp8
 // Wo rows of 1, 2, 4 or 8 KiB (one GPU: 4 / 8; a tensor-parallel rank's Wo slice: 1 / 2 too)
@@ -702,7 +722,7 @@ extern "C" int yalm_attn_wo_plan(const yalm_config *cp, int slots, int *splits, 
 	if (splits)
 		*splits = S;
 	if (grid)
-		*grid = c.n_kv_heads * (S + G - 1) + c.n_heads + n_wo;
+		*grid = attn_wo_grid(c.n_heads, c.n_kv_heads, S, c.dim);
 	return 1;
 }
 
@@ -717,26 +737,17 @@ static int attn_wo_init(yalm_decoder_s *d) {
 	const int rb = c.n_heads * c.head_dim * (c.weight_dtype == YALM_F16 ? 2 : 1);
 	if (!yalm_attn_wo_plan(&c, 1 << 30, nullptr, nullptr))
 		return YALM_OK;
-	int occ = 0; // the Wo workgroups spin, but only on attention workgroups dispatched before them
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, attn_wo_pick(c.weight_dtype, G, rb / 1024), ATTN_THREADS,
-	                                                 0) != hipSuccess ||
-	    occ < 1)
+	const int slots = attn_wo_slots(c.weight_dtype, G, rb / 1024);
+	if (slots < 1 || !yalm_attn_wo_plan(&c, slots, &d->awo_S, &d->awo_nb))
 		return YALM_OK;
-	if (!yalm_attn_wo_plan(&c, occ * device_cu_count(), &d->awo_S, &d->awo_nb))
-		return YALM_OK;
-	d->awo_slots = occ * device_cu_count();
+	d->awo_slots = slots;
 	// per layer: the attention output as {value, epoch} granules (zero tags never match:
 	// the epoch is >= 1 from the first forward / yalm_block on)
 	const size_t gran = (size_t)c.n_layers * c.n_heads * c.head_dim;
 	TRY(dalloc(d, (void **)&d->awo_gran, sizeof(unsigned long long) * gran));
 	const char *denv = ab_env("YALM_ATTN_WO_DELAY");
-	// default 0.2 us (fp16) / 0.5 us (fp8): the attention workgroups' K/V loads reach HBM
-	// ahead of the Wo stream. fp16 (33.5 MB, slice lands ~5.4 us, after the heads):
-	// profiles/r2_sweep_awo_delay.txt 10.6 -> 10.1 us at kv_len 17. fp8 (16.8 MB, slice lands
-	// ~3.1 us, before the heads): 0.5 us gives 9.4 -> 8.4 us at kv 17, 11.3 -> 10.3 at kv 151,
-	// 579 -> 586 tok/s (profiles/r3_ab_awo_delay.txt); fp16 at 0.5 us is within noise
-	const bool fp8 = c.weight_dtype == YALM_F8E5M2 || c.weight_dtype == YALM_E4M3; // (e4m3: the same slice bytes)
-	d->awo_delay = denv ? std::max(0, atoi(denv)) : (fp8 ? 50 : 20);
+	const bool fp8 = c.weight_dtype == YALM_F8E5M2 || c.weight_dtype == YALM_E4M3;
+	d->awo_delay = denv ? std::max(0, atoi(denv)) : attn_wo_default_delay(c.weight_dtype);
 	d->awo_delay_short = denv ? -1 : (fp8 ? 0 : -1);
 	// Removed in round 4 (measured losers, round 3, profiles/r3_ab_awo*.txt): the combined
 	// first gather attempt (YALM_AWO_SPEC), per-XCD copies of the head outputs
@@ -750,23 +761,26 @@ static int attn_wo_init(yalm_decoder_s *d) {
 
 // After a sync: report (once) a bounded spin that gave up -- the fused attention + Wo
 // launch waiting for its heads, or an IPC exchange waiting for a peer.
+// bit 1: a Wo workgroup of the fused launch gave up waiting for its head granules;
+// bit 2: a split-KV merger (fused or standalone attention) gave up waiting for a chunk
+static std::string awo_err_text(unsigned e) {
+	std::string m = "bounded in-launch wait gave up (results invalid):";
+	if (e & 1u)
+		m += " the fused attention + Wo launch's Wo gather timed out waiting for the attention heads"
+		     " (yalm_decoder_set_launch YALM_LAUNCH_SEPARATE_ATTN_WO selects separate launches);";
+	if (e & 2u)
+		m += " the split-KV attention merger timed out waiting for a key-chunk partial;";
+	if (e & ~3u)
+		m += " unknown error bits " + std::to_string(e & ~3u) + ";";
+	return m;
+}
 int awo_check(yalm_decoder_s *d) {
 	if (d->awo_err) {
 		unsigned e = 0;
 		HIPCHK(hipMemcpy(&e, d->awo_err, sizeof(e), hipMemcpyDeviceToHost));
 		if (e) { // cleared so that later calls report only their own failures
 			HIPCHK(hipMemset(d->awo_err, 0, sizeof(e)));
-			// bit 1: a Wo workgroup of the fused launch gave up waiting for its head granules;
-			// bit 2: a split-KV merger (fused or standalone attention) gave up waiting for a chunk
-			std::string m = "bounded in-launch wait gave up (results invalid):";
-			if (e & 1u)
-				m += " the fused attention + Wo launch's Wo gather timed out waiting for the attention heads"
-				     " (yalm_decoder_set_launch YALM_LAUNCH_SEPARATE_ATTN_WO selects separate launches);";
-			if (e & 2u)
-				m += " the split-KV attention merger timed out waiting for a key-chunk partial;";
-			if (e & ~3u)
-				m += " unknown error bits " + std::to_string(e & ~3u) + ";";
-			set_err(m);
+			set_err(awo_err_text(e));
 			return YALM_ERR_HIP;
 		}
 	}
@@ -806,72 +820,97 @@ template <class WT>
 constexpr bool wt_dense_one_gpu() {
 	return WT::Q4 || WT::ROW_SCALE;
 }
-template <class WT, int GT, int KB>
-static void launch_attn_wo_k(yalm_decoder_s *d, const yalm_block_weights &w, const AttnWoArgs &p) {
-	attn_wo_kernel<WT, GT, KB><<<d->awo_nb, ATTN_THREADS, 0, d->stream>>>(d->q, w.key_cache, w.value_cache, d->step, p);
-}
-template <class WT, int KB>
-static void launch_attn_wo_g(yalm_decoder_s *d, const yalm_block_weights &w, const AttnWoArgs &p, int G) {
-	if (G <= 1)
-		launch_attn_wo_k<WT, 1, KB>(d, w, p);
-	else if (G <= 2)
-		launch_attn_wo_k<WT, 2, KB>(d, w, p);
-	else if (G <= 4)
-		launch_attn_wo_k<WT, 4, KB>(d, w, p);
-	else
-		launch_attn_wo_k<WT, 8, KB>(d, w, p);
+// The plain values of one fused attention + Wo launch: the shape, the geometry (S key splits per
+// kv head: attn_wo_grid workgroups) and the buffers. Nothing of a decoder. Two places fill one and
+// call launch_attn_wo_v: launch_attn_wo<WT> (from the decoder's fields; the forward, yalm_block and
+// timing id 8 all go through it) and yalm_attn_wo_one (from host arrays).
+struct AttnWoLaunch {
+	int dtype;                              // YALM_F16, YALM_F8E5M2 or YALM_E4M3 (Wo's stored type)
+	int n_heads, n_kv, dim, max_seq_len;    // head_dim is 128
+	int S, grid;                            // key splits per kv head; attn_wo_grid(n_heads, n_kv, S, dim)
+	int layer, n_layers;
+	int add_base, delay;
+	const float *q;
+	const uint16_t *kc, *vc;
+	const StepState *step;
+	unsigned long long *part;               // (n_heads, attn_nsplit(max_seq_len), 130) granules
+	const unsigned long long *gran;         // THIS layer's q_dim granules
+	const void *wo;
+	float *x, *out;
+	TpX push;
+	unsigned *err;
+	unsigned long long *trace;
+};
+// Fills AttnWoArgs and launches, on st, the kernel attn_wo_pick gives for (dtype, Wo row bytes, G):
+// the one map to attn_wo_kernel<WT, GT, KB>, which the occupancy query (attn_wo_slots) reads too.
+static int launch_attn_wo_v(const AttnWoLaunch &a, hipStream_t st) {
+	AttnWoArgs p;
+	p.n_heads = a.n_heads;
+	p.n_kv = a.n_kv;
+	p.max_seq_len = a.max_seq_len;
+	p.nsplit = attn_nsplit(a.max_seq_len);
+	p.S = a.S;
+	p.head_max = attn_head_max(a.S, (a.max_seq_len + attn_chunk<128>() - 1) / attn_chunk<128>());
+	p.q_dim = a.n_heads * 128;
+	p.dim = a.dim;
+	p.part = a.part;
+	p.layer = a.layer;
+	p.n_layers = a.n_layers;
+	p.gran = a.gran;
+	p.wo = (const char *)a.wo;
+	p.x = a.x;
+	p.out = a.out;
+	p.add_base = a.add_base;
+	p.push = a.push;
+	p.err = a.err;
+	p.trace = a.trace;
+	p.delay = a.delay;
+	const int KB = p.q_dim * (a.dtype == YALM_F16 ? 2 : 1) / 1024; // 1, 2, 4 or 8 (yalm_attn_wo_plan)
+	// the kernel's five arguments, in its order (what a <<<>>> launch of it passes)
+	const float *q = a.q;
+	const uint16_t *kc = a.kc, *vc = a.vc;
+	const StepState *step = a.step;
+	void *args[] = {(void *)&q, (void *)&kc, (void *)&vc, (void *)&step, (void *)&p};
+	HIPCHK(hipLaunchKernel(attn_wo_pick(a.dtype, a.n_heads / a.n_kv, KB), dim3(a.grid), dim3(ATTN_THREADS), args, 0, st));
+	return YALM_OK;
 }
 // The fused attention + Wo launch of one layer. One GPU: x += Wo attn(q). Tensor parallel:
 // the rank's partial (+ x on rank 0) -- into xs, then the RCCL all-reduce into x; or pushed
 // to the IPC exchange `ex` (consumed by the GLU GEMV's x staging, tp_exchange.h).
 template <class WT>
 static int launch_attn_wo(yalm_decoder_s *d, int layer, int ex) {
+	if constexpr (!wt_fused_wo<WT>()) { // (attn_wo_init fuses no such decoder)
+		set_err("no fused attention + Wo kernel for this weight type");
+		return YALM_ERR_UNSUPPORTED;
+	}
 	const yalm_config &c = d->c;
 	const yalm_block_weights &w = d->b[layer];
-	AttnWoArgs p;
-	p.n_heads = c.n_heads;
-	p.n_kv = c.n_kv_heads;
-	p.max_seq_len = c.max_seq_len;
-	p.nsplit = attn_nsplit(c.max_seq_len);
-	p.S = d->awo_S;
-	p.head_max = attn_head_max(d->awo_S, (c.max_seq_len + attn_chunk<128>() - 1) / attn_chunk<128>());
-	p.q_dim = c.n_heads * c.head_dim;
-	p.dim = c.dim;
-	p.part = d->part;
-	p.layer = layer;
-	p.n_layers = c.n_layers;
-	p.gran = d->awo_gran + (size_t)layer * p.q_dim;
-	p.wo = (const char *)w.wo;
-	p.x = d->x;
-	p.out = d->comm ? d->xs : d->x;
-	p.add_base = d->tp_rank == 0;
-	p.push = d->ipc ? tpx_ex(d, ex) : TpX{};
-	p.err = d->awo_err;
-	p.trace = d->awo_trace;
-	p.delay = d->awo_delay_short >= 0 && d->awo_kv_hint >= 0 && d->awo_kv_hint <= AWO_SHORT_KV ? d->awo_delay_short
+	AttnWoLaunch a{};
+	a.dtype = c.weight_dtype;
+	a.n_heads = c.n_heads;
+	a.n_kv = c.n_kv_heads;
+	a.dim = c.dim;
+	a.max_seq_len = c.max_seq_len;
+	a.S = d->awo_S;
+	a.grid = d->awo_nb;
+	a.layer = layer;
+	a.n_layers = c.n_layers;
+	a.add_base = d->tp_rank == 0;
+	a.delay = d->awo_delay_short >= 0 && d->awo_kv_hint >= 0 && d->awo_kv_hint <= AWO_SHORT_KV ? d->awo_delay_short
 	                                                                                         : d->awo_delay;
-	const int G = c.n_heads / c.n_kv_heads;
-	if constexpr (WT::ROW_SCALE) { // one GPU only: rows of 4 or 8 KiB of codes (attn_wo_plan)
-		if (p.q_dim == 4096)
-			launch_attn_wo_g<WT, 4>(d, w, p, G);
-		else
-			launch_attn_wo_g<WT, 8>(d, w, p, G);
-	} else if constexpr (wt_fused_wo<WT>()) {
-		switch (p.q_dim * WT::BYTES) {
-		case 1024:
-			launch_attn_wo_g<WT, 1>(d, w, p, G);
-			break;
-		case 2048:
-			launch_attn_wo_g<WT, 2>(d, w, p, G);
-			break;
-		case 4096:
-			launch_attn_wo_g<WT, 4>(d, w, p, G);
-			break;
-		default:
-			launch_attn_wo_g<WT, 8>(d, w, p, G);
-		}
-	}
-	HIPCHK(hipGetLastError());
+	a.q = d->q;
+	a.kc = w.key_cache;
+	a.vc = w.value_cache;
+	a.step = d->step;
+	a.part = d->part;
+	a.gran = d->awo_gran + (size_t)layer * c.n_heads * c.head_dim;
+	a.wo = w.wo;
+	a.x = d->x;
+	a.out = d->comm ? d->xs : d->x;
+	a.push = d->ipc ? tpx_ex(d, ex) : TpX{};
+	a.err = d->awo_err;
+	a.trace = d->awo_trace;
+	TRY(launch_attn_wo_v(a, d->stream));
 	if (d->comm && ncclAllReduce(d->xs, d->x, c.dim, ncclFloat, ncclSum, (ncclComm_t)d->comm, d->stream) != ncclSuccess) {
 		set_err("ncclAllReduce failed");
 		return YALM_ERR_HIP;
@@ -3563,6 +3602,105 @@ extern "C" int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint1
 		set_err("yalm_mha: the split-KV merger gave up waiting for a chunk");
 		return YALM_ERR_HIP;
 	}
+	return YALM_OK;
+}
+
+extern "C" int yalm_attn_wo_one(const yalm_attn_wo_args *ap) {
+	ARGCHK(ap, "yalm_attn_wo_one: null argument");
+	const yalm_attn_wo_args &a = *ap;
+	ARGCHK(a.kv_len && a.q && a.x && a.kcache && a.vcache && a.wo && a.out, "yalm_attn_wo_one: null array");
+	ARGCHK(a.dim >= AWO_RPW && a.dim % 16 == 0, "yalm_attn_wo_one: dim must be a multiple of 16, at least 16");
+	ARGCHK(a.n_launch >= 1 && a.n_launch <= 8, "yalm_attn_wo_one: 1 <= n_launch <= 8");
+	ARGCHK(a.max_seq_len >= 1, "yalm_attn_wo_one: max_seq_len must be positive");
+	for (int i = 0; i < a.n_launch; ++i)
+		ARGCHK(a.kv_len[i] >= 1 && a.kv_len[i] <= a.max_seq_len, "yalm_attn_wo_one: 1 <= kv_len <= max_seq_len");
+	ARGCHK(a.S >= 0 && a.S <= ATTN_SPLITS, "yalm_attn_wo_one: S must be 0 (the plan's) or 1..32");
+	ARGCHK(a.slots >= 0, "yalm_attn_wo_one: slots must be 0 (this device's) or positive");
+	ARGCHK(a.epoch0 >= 1, "yalm_attn_wo_one: epoch0 must be at least 1 (a zero tag is the cleared buffer's)");
+	ARGCHK(a.n_layers >= 1 && a.layer >= 0 && a.layer < a.n_layers, "yalm_attn_wo_one: 0 <= layer < n_layers");
+	ARGCHK((a.add_base == 0 || a.add_base == 1) && (a.alias == 0 || a.alias == 1) && (a.add_base || !a.alias),
+	       "yalm_attn_wo_one: add_base and alias are 0 or 1, and out without the base is a buffer of its own");
+	yalm_config c{};
+	c.dim = a.dim, c.head_dim = 128, c.n_layers = a.n_layers, c.n_heads = a.n_heads, c.n_kv_heads = a.n_kv_heads;
+	c.max_seq_len = a.max_seq_len, c.weight_dtype = a.dtype;
+	if (a.n_heads <= 0 || !yalm_attn_wo_plan(&c, 1 << 30, nullptr, nullptr)) {
+		set_err("yalm_attn_wo_one: yalm_attn_wo_plan does not fuse this shape (f16 / fp8 Wo rows of 1, 2, 4 or 8 KiB, "
+		        "e4m3 of 4 or 8 KiB of codes, n_heads / n_kv_heads a whole number up to 8)");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const int G = a.n_heads / a.n_kv_heads, q_dim = a.n_heads * 128;
+	const int KB = q_dim * (a.dtype == YALM_F16 ? 2 : 1) / 1024;
+	const int nchunks = attn_nsplit(a.max_seq_len);
+	int S = std::min(a.S, nchunks);
+	if (a.S == 0) {
+		const int slots = a.slots ? a.slots : attn_wo_slots(a.dtype, G, KB);
+		if (slots < 1 || !yalm_attn_wo_plan(&c, slots, &S, nullptr)) {
+			set_err("yalm_attn_wo_one: yalm_attn_wo_plan does not fuse this shape at these workgroup slots");
+			return YALM_ERR_UNSUPPORTED;
+		}
+	}
+	const int grid = attn_wo_grid(a.n_heads, a.n_kv_heads, S, a.dim);
+	if (a.S_out)
+		*a.S_out = S;
+	if (a.grid_out)
+		*a.grid_out = grid;
+	const size_t kvb = sizeof(uint16_t) * (size_t)a.max_seq_len * a.n_kv_heads * 128;
+	const size_t rowb = sizeof(float) * a.dim, xb = rowb * a.n_launch;
+	const size_t lgran = (size_t)a.layer * q_dim; // this layer's slice of the granule buffer
+	DevBuf dk, dv, dq, dx, dout, dwo, dpart, dgran, dstep, derr;
+	TRY(up(dk, a.kcache, kvb));
+	TRY(up(dv, a.vcache, kvb));
+	TRY(up(dq, a.q, sizeof(float) * (size_t)a.n_launch * q_dim));
+	TRY(up(dwo, a.wo, yalm_row_bytes(a.dtype, q_dim) * (size_t)a.dim));
+	// out between two guard rows of 0xA5 bytes; alias: its rows start as x's
+	std::vector<unsigned char> oh(xb + 2 * rowb, 0xA5);
+	memcpy(oh.data() + rowb, a.alias ? a.x : a.out, xb);
+	TRY(up(dout, oh.data(), oh.size()));
+	if (!a.alias)
+		TRY(up(dx, a.x, xb));
+	TRY(up(dpart, nullptr, sizeof(unsigned long long) * (size_t)a.n_heads * nchunks * (128 + 2)));
+	TRY(up(dgran, nullptr, sizeof(unsigned long long) * (size_t)a.n_layers * q_dim));
+	TRY(up(dstep, nullptr, sizeof(StepState)));
+	TRY(up(derr, nullptr, sizeof(unsigned) * AWO_REPL_STRIDE));
+	AttnWoLaunch v{};
+	v.dtype = a.dtype, v.n_heads = a.n_heads, v.n_kv = a.n_kv_heads, v.dim = a.dim, v.max_seq_len = a.max_seq_len;
+	v.S = S, v.grid = grid, v.layer = a.layer, v.n_layers = a.n_layers, v.add_base = a.add_base;
+	v.delay = a.delay < 0 ? attn_wo_default_delay(a.dtype) : a.delay;
+	v.kc = (const uint16_t *)dk.p, v.vc = (const uint16_t *)dv.p, v.step = (const StepState *)dstep.p;
+	v.part = (unsigned long long *)dpart.p, v.gran = (const unsigned long long *)dgran.p + lgran, v.wo = dwo.p;
+	v.err = (unsigned *)derr.p;
+	for (int i = 0; i < a.n_launch; ++i) {
+		StepState h{};
+		h.pos = h.kv_pos = a.kv_len[i] - 1;
+		h.kv_len = a.kv_len[i];
+		h.epoch = (unsigned)a.epoch0 + (unsigned)i;
+		HIPCHK(hipMemcpy(dstep.p, &h, sizeof(h), hipMemcpyHostToDevice));
+		v.q = (const float *)dq.p + (size_t)i * q_dim;
+		v.out = (float *)((char *)dout.p + rowb) + (size_t)i * a.dim;
+		v.x = a.alias ? v.out : (float *)dx.p + (size_t)i * a.dim;
+		TRY(launch_attn_wo_v(v, nullptr));
+		HIPCHK(hipDeviceSynchronize());
+		if (a.gran_out)
+			HIPCHK(hipMemcpy(a.gran_out + (size_t)i * q_dim, v.gran, sizeof(unsigned long long) * q_dim,
+			                 hipMemcpyDeviceToHost));
+	}
+	HIPCHK(hipMemcpy(oh.data(), dout.p, oh.size(), hipMemcpyDeviceToHost));
+	memcpy(a.out, oh.data() + rowb, xb);
+	if (!a.alias)
+		HIPCHK(hipMemcpy(a.x, dx.p, xb, hipMemcpyDeviceToHost));
+	unsigned e = 0;
+	HIPCHK(hipMemcpy(&e, derr.p, sizeof(e), hipMemcpyDeviceToHost));
+	if (a.err_out)
+		*a.err_out = e;
+	if (e) {
+		set_err("yalm_attn_wo_one: " + awo_err_text(e));
+		return YALM_ERR_HIP;
+	}
+	for (size_t i = 0; i < rowb; ++i)
+		if (oh[i] != 0xA5 || oh[rowb + xb + i] != 0xA5) {
+			set_err("yalm_attn_wo_one: a guard row of out was written");
+			return YALM_ERR_HIP;
+		}
 	return YALM_OK;
 }
 

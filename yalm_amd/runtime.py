@@ -132,6 +132,15 @@ class GemvArgs(ctypes.Structure):
                 + [("q_len", c_int), ("raw_len", c_int)] + [(n, c_void_p) for n in ("bq", "bk", "bv")])
 
 
+class AttnWoArgs(ctypes.Structure):
+    """yalm_attn_wo_args: a sequence of fused attention + Wo launches on host arrays (yalm_attn_wo_one)."""
+
+    _fields_ = ([(n, c_int) for n in ("dtype", "n_heads", "n_kv_heads", "dim", "max_seq_len", "S", "slots", "delay",
+                                      "n_launch", "epoch0", "layer", "n_layers", "add_base", "alias")]
+                + [(n, c_void_p) for n in ("kv_len", "q", "x", "kcache", "vcache", "wo", "out", "gran_out", "err_out")]
+                + [("S_out", ctypes.POINTER(c_int)), ("grid_out", ctypes.POINTER(c_int))])
+
+
 class PrefillStageInfo(ctypes.Structure):
     """yalm_prefill_stage_info: the path one prefill stage took."""
 
@@ -280,6 +289,7 @@ _sig("yalm_matmul_rows", c_int, [c_void_p] * 5 + [c_float] + [c_int] * 8)
 _sig("yalm_gemv_plan", c_int, [c_int] * 11 + [ctypes.POINTER(GemvGeometry)])
 _sig("yalm_gemv_one", c_int, [ctypes.POINTER(GemvArgs)])
 _sig("yalm_prefill_stage", c_int, [ctypes.POINTER(PrefillStageArgs)])
+_sig("yalm_attn_wo_one", c_int, [ctypes.POINTER(AttnWoArgs)])
 _sig("yalm_batch_create", c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p)])
 _sig("yalm_batch_destroy", c_int, [c_void_p])
 _sig("yalm_batch_load", c_int, [c_void_p, c_int, c_int])
@@ -314,7 +324,7 @@ EXPORTED = [
     "yalm_decoder_set_qk_norm",
     "yalm_rows_plan", "yalm_matmul_rows",
     "yalm_gemv_plan", "yalm_gemv_one",
-    "yalm_attn_prefill_rows", "yalm_prefill_stage",
+    "yalm_attn_prefill_rows", "yalm_prefill_stage", "yalm_attn_wo_one",
     "yalm_batch_create", "yalm_batch_destroy", "yalm_batch_load", "yalm_batch_forward",
     "yalm_batch_generate_greedy", "yalm_batch_generate_sampled", "yalm_batch_state", "yalm_batch_set_launch",
     "yalm_batch_buffers", "yalm_batch_share_prefix", "yalm_attn_batch_prefix",
@@ -588,6 +598,43 @@ def attn_wo_plan(cfg: M.ModelConfig, slots: int):
     s, g = c_int(), c_int()
     ok = lib.yalm_attn_wo_plan(ctypes.byref(c), slots, ctypes.byref(s), ctypes.byref(g))
     return bool(ok), s.value, g.value
+
+
+def attn_wo_one(dtype: int, n_heads: int, n_kv_heads: int, dim: int, max_seq_len: int, kv_len, q, x, kcache, vcache,
+                wo, *, out=None, S: int = 0, slots: int = 0, delay: int = -1, epoch0: int = 1, layer: int = 0,
+                n_layers: int = 1, add_base: int = 1, alias: int = 1) -> dict:
+    """A sequence of fused attention + Wo launches through the decoder's launcher (yalm_attn_wo_one)
+    over one set of device buffers: launch i at kv_len[i] on q[i] (n_launch, n_heads * 128) and
+    x[i] (n_launch, dim), epoch epoch0 + i. kcache / vcache: (max_seq_len, n_kv_heads * 128) f16;
+    wo: the stored rows (e4m3: uint8 rows of row_bytes). out (n_launch, dim) as it stands before the
+    launches (alias = 0; zeros without one). Returns copies in a dict: out, x (as it comes back),
+    gran (n_launch, n_heads * 128) uint64 granules of the layer, values (their low words as f32),
+    tags (their high words), err, S and grid; the arguments are not written."""
+    kv = np.ascontiguousarray(np.atleast_1d(kv_len), dtype=np.int32)
+    n, q_dim = kv.size, n_heads * 128
+    q = np.ascontiguousarray(q, dtype=np.float32).reshape(n, -1)
+    xs = np.array(x, dtype=np.float32, order="C").reshape(n, -1)
+    assert q.shape[1] == q_dim and xs.shape[1] == dim
+    kc = np.ascontiguousarray(kcache).view(np.uint16)
+    vc = np.ascontiguousarray(vcache).view(np.uint16)
+    assert kc.size == vc.size == max_seq_len * n_kv_heads * 128
+    w = np.ascontiguousarray(wo)
+    rb = lib.yalm_row_bytes(dtype, q_dim)  # (0: a row length the library refuses)
+    assert rb == 0 or w.nbytes == dim * rb, "wo: dim rows of row_bytes(dtype, n_heads * 128)"
+    o = np.zeros((n, dim), np.float32) if out is None else np.array(out, dtype=np.float32, order="C").reshape(n, dim)
+    gran = np.zeros((n, q_dim), np.uint64)
+    err, s_used, grid = ctypes.c_uint(0), c_int(0), c_int(0)
+    a = AttnWoArgs()
+    a.dtype, a.n_heads, a.n_kv_heads, a.dim, a.max_seq_len = dtype, n_heads, n_kv_heads, dim, max_seq_len
+    a.S, a.slots, a.delay, a.n_launch, a.epoch0, a.layer, a.n_layers = S, slots, delay, n, epoch0, layer, n_layers
+    a.add_base, a.alias = add_base, alias
+    a.kv_len, a.q, a.x, a.kcache, a.vcache, a.wo = _ptr(kv), _ptr(q), _ptr(xs), _ptr(kc), _ptr(vc), _ptr(w)
+    a.out, a.gran_out, a.err_out = _ptr(o), _ptr(gran), ctypes.addressof(err)
+    a.S_out, a.grid_out = ctypes.pointer(s_used), ctypes.pointer(grid)
+    check(lib.yalm_attn_wo_one(ctypes.byref(a)))
+    g32 = gran.view(np.uint32).reshape(n, q_dim, 2)
+    return dict(out=o, x=xs, gran=gran, values=g32[:, :, 0].copy().view(np.float32), tags=g32[:, :, 1].copy(),
+                err=int(err.value), S=s_used.value, grid=grid.value)
 
 
 ROWS_STORE, ROWS_RESIDUAL, ROWS_GLU = 0, 1, 2  # yalm_matmul_rows epilogues
