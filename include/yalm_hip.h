@@ -316,6 +316,29 @@ int yalm_decoder_attn_wo(yalm_decoder d);
 #define YALM_LAUNCH_SYNC 2
 #define YALM_LAUNCH_SEPARATE_ATTN_WO 4
 int yalm_decoder_set_launch(yalm_decoder d, int flags);
+/* The opt-in 8-bit shadow of the KV cache ("q8 kv", attention_q8.h). Every (cache row, kv head)
+ * gets head_dim 8-bit codes and one f32 scale, for K and for V: in float32 a = max|x| over the
+ * head's row, inv = 127 / a, c = clamp(rint(x * inv), -127, 127), s = a / 127 (a == 0: s = 0, all
+ * c = 0); the value is c * s, a code is stored as the byte c + 128. The f16 cache stays and
+ * everything that writes or rotates it is unchanged; the decode attention
+ * (attn_decode_q8_kernel) reads rows < kv_sink and the step's own row from it and every other
+ * live row from the shadow, and quantises the step's row for the later steps; yalm_prefill
+ * quantises the rows it wrote. on != 0 allocates the shadow, 0 frees it; both drop the captured
+ * graphs. Only before the first position is written (else YALM_ERR_ARG). A q8 kv decoder runs
+ * attention and Wo as two launches (yalm_decoder_attn_wo returns 0) and serves yalm_forward, the
+ * greedy and sampled loops, yalm_enqueue_greedy, yalm_block, yalm_prefill and yalm_time_kernel;
+ * yalm_forward_rows, the speculative loops and yalm_batch_create return YALM_ERR_UNSUPPORTED
+ * ("q8 kv"). Dense one-GPU decoders of every weight format with head_dim 64 or 128 and caches
+ * of their own; YALM_ERR_UNSUPPORTED ("q8 kv") for a mixture-of-experts or tensor-parallel
+ * decoder, caller-supplied caches or another head_dim. */
+int yalm_decoder_set_kv_q8(yalm_decoder d, int on);
+/* 1 if the decoder's attention reads the q8 shadow. */
+int yalm_decoder_kv_q8(yalm_decoder d);
+/* One layer's f16 caches and their shadow to the host (after a stream sync; any output may be
+ * NULL): f16 rows k16 / v16 and K / V codes [max_seq_len][n_kv_heads][head_dim], scales
+ * [max_seq_len][n_kv_heads]. Test hook. */
+int yalm_decoder_get_kv_q8(yalm_decoder d, int layer, uint16_t *k16, uint16_t *v16, uint8_t *kcodes, float *kscales,
+                           uint8_t *vcodes, float *vscales);
 /* The fused launch's plan for a (per-rank) config when `slots` workgroups of 256
  * threads are co-resident (occupancy x CUs): returns 1 and the key splits per kv head
  * and the grid size, or 0 = separate attention and Wo launches (unsupported shape, or
@@ -857,6 +880,17 @@ int yalm_gemv_one(const yalm_gemv_args *args);
  * probabilities for t < kv_len. */
 int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint16_t *vb, const float *q, int head_dim, int kv_len,
              int max_seq_len, int n_heads, int n_kv_heads);
+/* The q8 kv attention launch (yalm_decoder_set_kv_q8) on host arrays, without a decoder: uploads the
+ * f16 caches kb / vb (max_seq_len rows of n_kv_heads * head_dim), quantises all max_seq_len rows
+ * into a shadow (kv_quant_rows_kernel), then makes the decoder's own attention launch for a step
+ * with the given kv_sink <= kv_pos < kv_len (rows < kv_sink and row kv_pos from the f16 rows, the
+ * other rows < kv_len from the shadow), with `splits` key splits per kv head (0: the decoder's).
+ * xout (n_heads, head_dim); the shadow as the launch left it into kcodes / vcodes
+ * (max_seq_len, n_kv_heads, head_dim) and kscales / vscales (max_seq_len, n_kv_heads), each of
+ * which may be NULL. head_dim 64 or 128, n_heads / n_kv_heads <= 8. */
+int yalm_mha_q8(float *xout, const uint16_t *kb, const uint16_t *vb, const float *q, uint8_t *kcodes, float *kscales,
+                uint8_t *vcodes, float *vscales, int head_dim, int kv_sink, int kv_pos, int kv_len, int max_seq_len,
+                int n_heads, int n_kv_heads, int splits);
 /* A sequence of fused attention + Wo launches (attn_wo.h), the decoder's own -- the launcher the
  * forward pass, yalm_block and yalm_time_kernel 8 call -- on host arrays over ONE set of device
  * buffers, synchronous, without a decoder. head_dim is 128. Wo is `dim` rows of yalm_row_bytes(dtype,

@@ -221,6 +221,15 @@ struct yalm_decoder_s {
 	// [ROWS_MAX_T][q_dim + kv_dim] (allocated by the first set; decode uses row 0)
 	std::vector<const float *> gq, gk;
 	float *qk_raw = nullptr;
+	// the opt-in 8-bit shadow of the KV cache (yalm_decoder_set_kv_q8, attention_q8.h): one allocation
+	// (kv_q8_mem), per layer the K / V codes [max_seq_len][kv_dim] and scales [max_seq_len][n_kv_heads]
+	bool kv_q8 = false;
+	bool kv_supplied = false;          // the caller handed in a K or V cache (no shadow for those)
+	bool kv_written = false;           // a launch sequence that writes cache rows has been enqueued
+	bool sep_attn_wo = false;          // YALM_LAUNCH_SEPARATE_ATTN_WO as last set (q8 off restores the choice)
+	void *kv_q8_mem = nullptr;
+	std::vector<uint8_t *> kq8, vq8;
+	std::vector<float *> ks8, vs8;
 	std::vector<const void *> moegate; // [n_layers] router weights (n_experts, dim)
 	int *moe_sel = nullptr;            // [n_layers][moe_K] the routing of the most recent forward
 	float *moe_wts = nullptr;          // [n_layers][moe_K]
@@ -229,3 +238,4 @@ struct yalm_decoder_s {
 // ------------------------------------------------------------------ shared helpers
 int dalloc(yalm_decoder_s *d, void **p, size_t bytes); // zeroed device allocation owned by d
 int awo_check(yalm_decoder_s *d);                      // after a sync: a fused-launch spin that gave up
+int kv_q8_quant_rows(yalm_decoder_s *d, int layer, int r0, int n); // f16 cache rows [r0, r0 + n) into the q8 shadow

@@ -926,6 +926,7 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 	const PfForms &f = d->pf_forms;
 	PrefillBufs &b = d->pf;
 	hipStream_t st = d->stream;
+	d->kv_written = true; // (yalm_prefill and yalm_prefill_time: cache rows are written from here on)
 	const int q_dim = c.n_heads * c.head_dim, kv_dim = c.n_kv_heads * c.head_dim;
 	const bool fp8 = c.weight_dtype == YALM_F8E5M2, q4 = c.weight_dtype == YALM_Q4, e4m3 = c.weight_dtype == YALM_E4M3;
 	if (e4m3)
@@ -1034,6 +1035,8 @@ int enqueue_prefill(yalm_decoder_s *d, int T, int pos0, bool want_lp, const int 
 		}
 		TRY(launch_attn_prefill(b.Q, w.key_cache, w.value_cache, T, pos0, c.n_heads, c.n_kv_heads, c.head_dim, b.O,
 								st, split));
+		if (d->kv_q8) // the rows just written, into the q8 shadow (attention_q8.h)
+			TRY(kv_q8_quant_rows(d, l, pos0, T));
 		TRY(enqueue_residual(f, PG_WO, b.O, T, q_dim, w.wo, c.dim, b.X, 1.0f, small, ks_wo, b.skp, st, wdt));
 		TRY(launch_rmsnorm(split, f, b.X, w.rms_ffn, c.dim, T, c.norm_eps, b.Xn, rg + RG_XFFN, st));
 		const float hscale = ldexpf(1.0f, -he);

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "attention.h"
+#include "attention_q8.h"
 #include "attn_wo.h"
 #include "batch.h"
 #include "batch_prefix.h"
@@ -643,6 +644,79 @@ static int launch_attn(int head_dim, int n_heads, int n_kv, const float *q, cons
 	return YALM_OK;
 }
 
+// ---- attention over the q8 shadow of the KV cache (attention_q8.h)
+static bool attn_q8_supported(int head_dim, int G) {
+	return (head_dim == 64 || head_dim == 128) && G >= 1 && G <= 8;
+}
+
+// the shadow of one layer: K / V codes and scales
+struct KvQ8 {
+	uint8_t *kq, *vq;
+	float *ks, *vs;
+};
+
+// f16 cache rows [r0, r0 + n) of one layer into its shadow: one wave per (row, kv head)
+static int launch_kv_quant_rows(int head_dim, int n_kv, const uint16_t *kc, const uint16_t *vc, const KvQ8 &sh, int r0,
+                                int n, hipStream_t st) {
+	const int grid = (n * n_kv + ATTN_WAVES - 1) / ATTN_WAVES;
+	if (head_dim == 64)
+		kv_quant_rows_kernel<64><<<grid, ATTN_THREADS, 0, st>>>(kc, vc, sh.kq, sh.ks, sh.vq, sh.vs, n_kv, r0, n);
+	else if (head_dim == 128)
+		kv_quant_rows_kernel<128><<<grid, ATTN_THREADS, 0, st>>>(kc, vc, sh.kq, sh.ks, sh.vq, sh.vs, n_kv, r0, n);
+	else {
+		set_err("q8 kv: head_dim must be 64 or 128");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
+// launch_attn_D's grid and its choices of S and hmax (splits > 0: the test hook's S)
+template <int D>
+static void launch_attn_q8_D(int G, const float *q, const uint16_t *kc, const uint16_t *vc, const KvQ8 &sh,
+                             const StepState *step, int n_heads, int n_kv, int max_seq_len, int nsplit,
+                             unsigned long long *part, int layer, int n_layers, unsigned *err, float *out, int splits,
+                             hipStream_t st) {
+	const int nchunks = (max_seq_len + attn_chunk<D>() - 1) / attn_chunk<D>();
+	const int S = std::min(nchunks, splits > 0 ? splits : ATTN_SPLITS);
+	const int grid = n_kv * (S + G - 1) + n_heads;
+	const int hmax = attn_head_max(S, nchunks);
+#define YALM_ATTN_Q8(GT)                                                                                               \
+	attn_decode_q8_kernel<D, GT><<<grid, ATTN_THREADS, 0, st>>>(q, kc, vc, sh.kq, sh.ks, sh.vq, sh.vs, step, n_heads,  \
+	                                                            n_kv, max_seq_len, nsplit, S, hmax, part, layer,       \
+	                                                            n_layers, err, out)
+	if (G <= 1)
+		YALM_ATTN_Q8(1);
+	else if (G <= 2)
+		YALM_ATTN_Q8(2);
+	else if (G <= 4)
+		YALM_ATTN_Q8(4);
+	else
+		YALM_ATTN_Q8(8);
+#undef YALM_ATTN_Q8
+}
+
+// launch_attn over the shadow: rows < kv_sink and row kv_pos from the f16 caches kc / vc, every
+// other live row from sh; row kv_pos is quantised into sh by the same launch.
+static int launch_attn_q8(int head_dim, int n_heads, int n_kv, const float *q, const uint16_t *kc, const uint16_t *vc,
+                          const KvQ8 &sh, const StepState *step, int max_seq_len, unsigned long long *part, int layer,
+                          int n_layers, unsigned *err, float *out, int splits, hipStream_t st) {
+	const int G = n_heads / n_kv;
+	const int nsplit = attn_nsplit(max_seq_len);
+	if (!attn_q8_supported(head_dim, G)) {
+		set_err("q8 kv: head_dim must be 64 or 128 and n_heads / n_kv_heads <= 8");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	if (head_dim == 64)
+		launch_attn_q8_D<64>(G, q, kc, vc, sh, step, n_heads, n_kv, max_seq_len, nsplit, part, layer, n_layers, err, out,
+		                     splits, st);
+	else
+		launch_attn_q8_D<128>(G, q, kc, vc, sh, step, n_heads, n_kv, max_seq_len, nsplit, part, layer, n_layers, err, out,
+		                      splits, st);
+	HIPCHK(hipGetLastError());
+	return YALM_OK;
+}
+
 // ---- attention + Wo in one launch (attn_wo.h)
 template <class WT, int GT, int KB>
 static const void *attn_wo_fn() {
@@ -1079,6 +1153,10 @@ static int launch_qk_norm(yalm_decoder_s *d, int l, int rows, const StepState *s
 // Attention of layer l for one row: its step state and q, its output row.
 static int enqueue_attn(yalm_decoder_s *d, int l, const float *q, const StepState *step, float *out) {
 	const yalm_config &c = d->c;
+	if (d->kv_q8)
+		return launch_attn_q8(c.head_dim, c.n_heads, c.n_kv_heads, q, d->b[l].key_cache, d->b[l].value_cache,
+		                      KvQ8{d->kq8[l], d->vq8[l], d->ks8[l], d->vs8[l]}, step, c.max_seq_len, d->part, l,
+		                      c.n_layers, d->awo_err, out, 0, d->stream);
 	return launch_attn(c.head_dim, c.n_heads, c.n_kv_heads, q, d->b[l].key_cache, d->b[l].value_cache, step,
 	                   c.max_seq_len, d->part, l, c.n_layers, d->awo_err, nullptr, out, d->stream);
 }
@@ -1426,6 +1504,8 @@ static void destroy_decoder(yalm_decoder_s *d) {
 		(void)hipIpcCloseMemHandle(p);
 	if (d->ipc_own)
 		(void)hipFree(d->ipc_own);
+	if (d->kv_q8_mem)
+		(void)hipFree(d->kv_q8_mem);
 	for (void *p : d->dev_allocs)
 		(void)hipFree(p);
 	if (d->logits_pinned)
@@ -1447,6 +1527,7 @@ int dalloc(yalm_decoder_s *d, void **p, size_t bytes) {
 // One forward of graph `which`: a graph replay, or the same kernels launched
 // eagerly when d->eager.
 static int replay(yalm_decoder_s *d, int which) {
+	d->kv_written = true;
 	if (d->eager || ((which == GRAPH_GREEDY || which == GRAPH_SAMPLED || which == GRAPH_PENALISED) && d->greedy_eager))
 		return enqueue_forward(d, which);
 	HIPCHK(hipGraphLaunch(d->exec[which], d->stream));
@@ -1553,6 +1634,7 @@ static int create_decoder(const yalm_config *config, const yalm_model_weights *w
 	}
 	for (auto &bw : d->b) {
 		const size_t kvb = sizeof(uint16_t) * (size_t)c.max_seq_len * kv_dim;
+		d->kv_supplied = d->kv_supplied || bw.key_cache || bw.value_cache;
 		if (!bw.key_cache && (r = dalloc(d, (void **)&bw.key_cache, kvb)))
 			return fail(r);
 		if (!bw.value_cache && (r = dalloc(d, (void **)&bw.value_cache, kvb)))
@@ -1985,7 +2067,9 @@ extern "C" int yalm_generate_sampled_ex(yalm_decoder d, int token, int pos, int 
 static const char *const ROWS_Q4_WHY = ": q4 weights have no multi-row form (gemv_rows.h streams element-typed rows)";
 static int rows_supported(const yalm_decoder_s *d, const char *who) {
 	const char *why = nullptr;
-	if (d->c.weight_dtype == YALM_Q4)
+	if (d->kv_q8)
+		why = ": no multi-row or batched form over a q8 kv cache (yalm_decoder_set_kv_q8)";
+	else if (d->c.weight_dtype == YALM_Q4)
 		why = ROWS_Q4_WHY;
 	else if (d->moe_E > 0)
 		why = ": mixture-of-experts decoders have no multi-row form (each row routes to its own experts)";
@@ -2159,6 +2243,7 @@ static int enqueue_rows_forward_t(yalm_decoder_s *d, int T, int from_step) {
 }
 
 static int enqueue_rows_forward(yalm_decoder_s *d, int T, int from_step) {
+	d->kv_written = true;
 	return DISPATCH_WT(d->c.weight_dtype, enqueue_rows_forward_t, d, T, from_step);
 }
 
@@ -2907,6 +2992,9 @@ extern "C" int yalm_block(yalm_decoder d, int layer, int pos, int kv_sink, int k
 	ARGCHK(d && layer >= 0 && layer < d->c.n_layers, "bad layer");
 	ARGCHK(kv_len >= 1 && kv_len <= d->c.max_seq_len && kv_pos >= 0 && kv_pos < d->c.max_seq_len,
 	       "bad kv indices");
+	d->kv_written = true;
+	if (d->kv_q8) // whatever filled the layer's f16 rows: the shadow of the live ones
+		TRY(kv_q8_quant_rows(d, layer, 0, kv_len));
 	set_step_full_kernel<<<1, 64, 0, d->stream>>>(d->step, pos, kv_sink, kv_pos, kv_len, d->ipc ? 2 : 0, d->inv_freq,
 	                                              d->c.head_dim / 2);
 	HIPCHK(hipGetLastError());
@@ -3022,7 +3110,94 @@ extern "C" int yalm_decoder_set_launch(yalm_decoder d, int flags) {
 	drop_graphs(d); // captured graphs bake the old launch sequence
 	d->eager = flags & YALM_LAUNCH_EAGER;
 	d->graph_sync = flags & YALM_LAUNCH_SYNC;
-	d->attn_wo = d->attn_wo_ok && !(flags & YALM_LAUNCH_SEPARATE_ATTN_WO);
+	d->sep_attn_wo = flags & YALM_LAUNCH_SEPARATE_ATTN_WO;
+	d->attn_wo = d->attn_wo_ok && !d->sep_attn_wo && !d->kv_q8; // (a q8 kv decoder: always two launches)
+	return YALM_OK;
+}
+
+int kv_q8_quant_rows(yalm_decoder_s *d, int layer, int r0, int n) {
+	const yalm_config &c = d->c;
+	return launch_kv_quant_rows(c.head_dim, c.n_kv_heads, d->b[layer].key_cache, d->b[layer].value_cache,
+	                            KvQ8{d->kq8[layer], d->vq8[layer], d->ks8[layer], d->vs8[layer]}, r0, n, d->stream);
+}
+
+// The 8-bit shadow of the KV cache (attention_q8.h) on or off: the attention launch then reads
+// the shadow (attn_decode_q8_kernel) and runs beside a separate Wo launch. Only before the first
+// position is written.
+extern "C" int yalm_decoder_set_kv_q8(yalm_decoder d, int on) {
+	ARGCHK(d, "null decoder");
+	ARGCHK(!d->kv_written, "yalm_decoder_set_kv_q8: only before the first position is written");
+	if (!!on == d->kv_q8)
+		return YALM_OK;
+	const yalm_config &c = d->c;
+	if (on) {
+		const char *why = nullptr;
+		if (d->moe_E > 0)
+			why = "a mixture-of-experts decoder";
+		else if (d->tp_size > 1 || d->comm || d->ipc)
+			why = "a tensor-parallel decoder";
+		else if (d->kv_supplied)
+			why = "caller-supplied caches";
+		else if (c.head_dim != 64 && c.head_dim != 128)
+			why = "this head_dim (64 or 128 only)";
+		else if (!attn_q8_supported(c.head_dim, c.n_heads / c.n_kv_heads))
+			why = "this group size (n_heads / n_kv_heads <= 8 only)";
+		if (why) {
+			set_err(std::string("yalm_decoder_set_kv_q8: no q8 kv for ") + why);
+			return YALM_ERR_UNSUPPORTED;
+		}
+	}
+	HIPCHK(hipStreamSynchronize(d->stream));
+	drop_graphs(d); // captured graphs bake the attention launch
+	if (on) {
+		const size_t codes = (size_t)c.max_seq_len * c.n_kv_heads * c.head_dim;           // (a multiple of 16)
+		const size_t scales = (((size_t)c.max_seq_len * c.n_kv_heads * 4) + 15) & ~(size_t)15;
+		const size_t per_layer = 2 * (codes + scales);
+		HIPCHK(hipMalloc(&d->kv_q8_mem, per_layer * c.n_layers));
+		HIPCHK(hipMemset(d->kv_q8_mem, 0, per_layer * c.n_layers));
+		d->kq8.resize(c.n_layers), d->vq8.resize(c.n_layers), d->ks8.resize(c.n_layers), d->vs8.resize(c.n_layers);
+		for (int l = 0; l < c.n_layers; ++l) {
+			uint8_t *p = (uint8_t *)d->kv_q8_mem + per_layer * l;
+			d->kq8[l] = p;
+			d->vq8[l] = p + codes;
+			d->ks8[l] = (float *)(p + 2 * codes);
+			d->vs8[l] = (float *)(p + 2 * codes + scales);
+		}
+	} else {
+		HIPCHK(hipFree(d->kv_q8_mem));
+		d->kv_q8_mem = nullptr;
+		d->kq8.clear(), d->vq8.clear(), d->ks8.clear(), d->vs8.clear();
+	}
+	d->kv_q8 = on != 0;
+	d->attn_wo = d->attn_wo_ok && !d->sep_attn_wo && !d->kv_q8;
+	return YALM_OK;
+}
+
+extern "C" int yalm_decoder_kv_q8(yalm_decoder d) {
+	return d && d->kv_q8 ? 1 : 0;
+}
+
+// One layer's f16 caches and their shadow to the host (any output may be null): f16 rows and
+// K / V codes [max_seq_len][kv_dim], scales [max_seq_len][n_kv_heads].
+extern "C" int yalm_decoder_get_kv_q8(yalm_decoder d, int layer, uint16_t *k16, uint16_t *v16, uint8_t *kcodes,
+                                      float *kscales, uint8_t *vcodes, float *vscales) {
+	ARGCHK(d && layer >= 0 && layer < d->c.n_layers, "yalm_decoder_get_kv_q8: bad argument");
+	ARGCHK(d->kv_q8, "yalm_decoder_get_kv_q8: q8 kv is off (yalm_decoder_set_kv_q8)");
+	const size_t codes = (size_t)d->c.max_seq_len * d->c.n_kv_heads * d->c.head_dim;
+	const size_t scales = sizeof(float) * (size_t)d->c.max_seq_len * d->c.n_kv_heads;
+	HIPCHK(hipStreamSynchronize(d->stream));
+	if (k16)
+		HIPCHK(hipMemcpy(k16, d->b[layer].key_cache, 2 * codes, hipMemcpyDeviceToHost));
+	if (v16)
+		HIPCHK(hipMemcpy(v16, d->b[layer].value_cache, 2 * codes, hipMemcpyDeviceToHost));
+	if (kcodes)
+		HIPCHK(hipMemcpy(kcodes, d->kq8[layer], codes, hipMemcpyDeviceToHost));
+	if (vcodes)
+		HIPCHK(hipMemcpy(vcodes, d->vq8[layer], codes, hipMemcpyDeviceToHost));
+	if (kscales)
+		HIPCHK(hipMemcpy(kscales, d->ks8[layer], scales, hipMemcpyDeviceToHost));
+	if (vscales)
+		HIPCHK(hipMemcpy(vscales, d->vs8[layer], scales, hipMemcpyDeviceToHost));
 	return YALM_OK;
 }
 
@@ -3088,6 +3263,7 @@ extern "C" int yalm_time_kernel(yalm_decoder d, int kernel_id, int iters, float 
 	ARGCHK(kernel_id != KID_EXCHANGE || d->comm || d->ipc,
 	       "kernel 6 (tensor-parallel exchange) needs a tensor-parallel decoder");
 	ARGCHK(kernel_id != KID_ATTN_WO || d->attn_wo, "kernel 8 (fused attention + Wo) needs yalm_decoder_attn_wo");
+	d->kv_written = true;
 	// in-launch hand-offs and the IPC exchange: fresh tags per launch (one exchange per bump)
 	const bool bump = kernel_id == KID_ATTN || kernel_id == KID_ATTN_WO || (kernel_id == KID_EXCHANGE && d->ipc);
 	// the warm-up gets a fresh epoch too: under IPC it pushes exchange xbase + 0, whose slot
@@ -3136,7 +3312,7 @@ extern "C" const char *yalm_kernel_name(yalm_decoder d, int kernel_id) {
 		s = gk + qkv_policy_name(d);
 		break;
 	case KID_ATTN:
-		s = "attn_decode_kernel<";
+		s = d->kv_q8 ? "attn_decode_q8_kernel<" : "attn_decode_kernel<";
 		break;
 	case KID_WO:
 		s = gk + WO_POLICY_NAME;
@@ -3600,6 +3776,57 @@ extern "C" int yalm_mha(float *xout, float *att, const uint16_t *kb, const uint1
 	HIPCHK(hipMemcpy(&e, derr.p, sizeof(e), hipMemcpyDeviceToHost));
 	if (e) {
 		set_err("yalm_mha: the split-KV merger gave up waiting for a chunk");
+		return YALM_ERR_HIP;
+	}
+	return YALM_OK;
+}
+
+extern "C" int yalm_mha_q8(float *xout, const uint16_t *kb, const uint16_t *vb, const float *q, uint8_t *kcodes,
+                           float *kscales, uint8_t *vcodes, float *vscales, int head_dim, int kv_sink, int kv_pos,
+                           int kv_len, int max_seq_len, int n_heads, int n_kv_heads, int splits) {
+	ARGCHK(xout && kb && vb && q, "null argument");
+	ARGCHK(n_kv_heads > 0 && n_heads % n_kv_heads == 0 && kv_len >= 1 && kv_len <= max_seq_len, "bad shape");
+	ARGCHK(kv_sink >= 0 && kv_sink <= kv_pos && kv_pos < kv_len && splits >= 0 && splits <= ATTN_MAX_SPLITS,
+	       "yalm_mha_q8: 0 <= kv_sink <= kv_pos < kv_len, 0 <= splits <= 64");
+	if (!attn_q8_supported(head_dim, n_heads / n_kv_heads)) {
+		set_err("yalm_mha_q8: q8 kv needs head_dim 64 or 128 and a group of at most 8");
+		return YALM_ERR_UNSUPPORTED;
+	}
+	const size_t kvn = (size_t)max_seq_len * n_kv_heads * head_dim, sn = (size_t)max_seq_len * n_kv_heads;
+	const int nsplit = attn_nsplit(max_seq_len);
+	DevBuf dk, dv, dq, dout, dpart, dstep, derr, dkq, dvq, dks, dvs;
+	TRY(up(dk, kb, kvn * 2));
+	TRY(up(dv, vb, kvn * 2));
+	TRY(up(dq, q, sizeof(float) * n_heads * head_dim));
+	TRY(up(dout, nullptr, sizeof(float) * n_heads * head_dim));
+	TRY(up(dpart, nullptr, sizeof(unsigned long long) * (size_t)n_heads * nsplit * (head_dim + 2)));
+	TRY(up(dstep, nullptr, sizeof(StepState)));
+	TRY(up(derr, nullptr, sizeof(unsigned)));
+	TRY(up(dkq, nullptr, kvn));
+	TRY(up(dvq, nullptr, kvn));
+	TRY(up(dks, nullptr, sizeof(float) * sn));
+	TRY(up(dvs, nullptr, sizeof(float) * sn));
+	const KvQ8 sh{(uint8_t *)dkq.p, (uint8_t *)dvq.p, (float *)dks.p, (float *)dvs.p};
+	TRY(launch_kv_quant_rows(head_dim, n_kv_heads, (const uint16_t *)dk.p, (const uint16_t *)dv.p, sh, 0, max_seq_len,
+	                         nullptr));
+	set_step_full_kernel<<<1, 1>>>((StepState *)dstep.p, kv_len - 1, kv_sink, kv_pos, kv_len);
+	TRY(launch_attn_q8(head_dim, n_heads, n_kv_heads, (const float *)dq.p, (const uint16_t *)dk.p,
+	                   (const uint16_t *)dv.p, sh, (const StepState *)dstep.p, max_seq_len, (unsigned long long *)dpart.p,
+	                   0, 1, (unsigned *)derr.p, (float *)dout.p, splits, nullptr));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(xout, dout.p, sizeof(float) * n_heads * head_dim, hipMemcpyDeviceToHost));
+	if (kcodes)
+		HIPCHK(hipMemcpy(kcodes, dkq.p, kvn, hipMemcpyDeviceToHost));
+	if (vcodes)
+		HIPCHK(hipMemcpy(vcodes, dvq.p, kvn, hipMemcpyDeviceToHost));
+	if (kscales)
+		HIPCHK(hipMemcpy(kscales, dks.p, sizeof(float) * sn, hipMemcpyDeviceToHost));
+	if (vscales)
+		HIPCHK(hipMemcpy(vscales, dvs.p, sizeof(float) * sn, hipMemcpyDeviceToHost));
+	unsigned e = 0;
+	HIPCHK(hipMemcpy(&e, derr.p, sizeof(e), hipMemcpyDeviceToHost));
+	if (e) {
+		set_err("yalm_mha_q8: the split-KV merger gave up waiting for a chunk");
 		return YALM_ERR_HIP;
 	}
 	return YALM_OK;

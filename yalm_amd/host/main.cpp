@@ -66,11 +66,17 @@ static uint64_t now_ms() {
 	                "             completions would be identical); not with -s\n");
 	fprintf(stderr, "  --share-prompt   with -N: the completions attend to the prompt's KV rows where they are (no\n"
 	                "             copy per completion, each row read once per step); head_dim 64 or 128\n");
+	fprintf(stderr, "  --kv-q8    (every mode) decode attention over an 8-bit shadow of the KV cache (codes + a scale per\n"
+	                "             row and kv head, beside the f16 cache). Not a speed option: measured slower than\n"
+	                "             the f16 attention at every shape so far (README); dense models, head_dim 64 or\n"
+	                "             128; not with -s or -N\n");
 	fprintf(stderr, "  Choose one:\n    -i <string> input prompt\n    -f <filepath> input file with prompt\n");
 	fprintf(stderr, "Passkey mode options:\n  -n <int>    number of junk lines to insert (default - 250)\n");
 	fprintf(stderr, "  -l <int>    passkey position (-1 - random)\n");
 	exit(1);
 }
+
+static bool g_kv_q8 = false; // --kv-q8: every model of the run creates q8 kv decoders
 
 static bool print_token_ids() {
 	const char *e = getenv("YALM_PRINT_TOKENS");
@@ -117,6 +123,7 @@ static void run_completion(const std::string &path, const std::string &device, c
 		exit(1);
 	}
 	Model model(data, context);
+	model.kv_q8 = g_kv_q8;
 	InferenceState state(model.config);
 	Sampler sampler(model.config, sampler_seed());
 	Tokenizer tokenizer(data);
@@ -323,6 +330,7 @@ static void run_perplexity(const std::string &path, const std::string &device, c
 		exit(1);
 	}
 	Model model(data, context);
+	model.kv_q8 = g_kv_q8;
 	InferenceState state(model.config);
 	Sampler sampler(model.config, sampler_seed());
 	Tokenizer tokenizer(data);
@@ -379,6 +387,7 @@ static void run_passkey(const std::string &path, const std::string &device, int 
 		exit(1);
 	}
 	Model model(data, context);
+	model.kv_q8 = g_kv_q8;
 	InferenceState state(model.config);
 	Sampler sampler(model.config, sampler_seed());
 	Tokenizer tokenizer(data);
@@ -462,6 +471,11 @@ int main(int argc, char *argv[]) {
 	for (int i = 2; i < argc; i += 2) {
 		if (std::string(argv[i]) == "--share-prompt") { // of -N; takes no value
 			share_prompt = true;
+			--i;
+			continue;
+		}
+		if (std::string(argv[i]) == "--kv-q8") { // takes no value
+			g_kv_q8 = true;
 			--i;
 			continue;
 		}

@@ -355,6 +355,8 @@ void Model::ensure_decoder(InferenceState &s, yalm_stream stream) {
 	} else {
 		check(yalm_decoder_create(&cc, &mw, stream, &s._decoder), "decoder create");
 	}
+	if (kv_q8)
+		check(yalm_decoder_set_kv_q8(s._decoder, 1), "q8 kv");
 	if (config->rope_scaling.type)
 		check(yalm_decoder_set_rope_scaling(s._decoder, &config->rope_scaling), "rope scaling");
 	if (config->qkv_bias) {

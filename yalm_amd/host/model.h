@@ -130,6 +130,9 @@ struct Model {
 	const void *token_embedding_table = nullptr;
 	const void *rms_final_weight = nullptr;
 	const void *wcls = nullptr;
+	// the decoders this model creates read the 8-bit shadow of the KV cache (yalm_decoder_set_kv_q8;
+	// --kv-q8). Set before the first forward.
+	bool kv_q8 = false;
 
 	Model(YALMData &yalm, int context = 0);
 	~Model();

@@ -631,6 +631,26 @@ def e4m3_dequantize(a: np.ndarray, n: int) -> np.ndarray:
     return (e4m3_table()[codes].astype(np.float64) * s.astype(np.float64)[:, None]).astype(np.float32)
 
 
+def kv_q8_quantize(x: np.ndarray):
+    """The q8 kv format (attention_q8.h) in float32: x (..., head_dim) f16 / f32 cache rows per
+    kv head -> (codes uint8 (..., head_dim), offset-binary c + 128; scales float32 (...)).
+    a = max|x|, inv = 127 / a, c = clip(rint(x * inv), -127, 127), s = a / 127; a == 0: s = 0, c = 0."""
+    x = np.asarray(x, np.float32)
+    a = np.abs(x).max(axis=-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv = np.float32(127.0) / a
+        c = np.clip(np.rint(x * inv[..., None]), -127, 127)
+    c = np.where(a[..., None] > 0, c, 0)
+    s = np.where(a > 0, a / np.float32(127.0), np.float32(0)).astype(np.float32)
+    return (c.astype(np.int32) + 128).astype(np.uint8), s
+
+
+def kv_q8_dequantize(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
+    """The values a q8 kv row stands for, float32: (code - 128) * scale (one f32 rounding)."""
+    c = np.asarray(codes, np.uint8).astype(np.float32) - np.float32(128.0)
+    return c * np.asarray(scales, np.float32)[..., None]
+
+
 def e4m3_twin(cfg: ModelConfig, tensors: dict):
     """The exact f16 twin of an e4m3 model: (f16 config, tensors with every e4m3 matrix as float16)."""
     out = {}

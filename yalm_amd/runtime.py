@@ -302,6 +302,10 @@ _sig("yalm_batch_set_launch", c_int, [c_void_p, c_int])
 _sig("yalm_batch_buffers", c_int, [c_void_p, c_int, c_int] + [ctypes.POINTER(c_void_p)] * 3)
 _sig("yalm_batch_share_prefix", c_int, [c_void_p, c_int])
 _sig("yalm_attn_batch_prefix", c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] + [c_int] * 3)
+_sig("yalm_decoder_set_kv_q8", c_int, [c_void_p, c_int])
+_sig("yalm_decoder_kv_q8", c_int, [c_void_p])
+_sig("yalm_decoder_get_kv_q8", c_int, [c_void_p, c_int] + [c_void_p] * 6)
+_sig("yalm_mha_q8", c_int, [c_void_p] * 8 + [c_int] * 8)
 
 EXPORTED = [
     "yalm_last_error", "yalm_set_device", "yalm_upload", "yalm_alloc", "yalm_download", "yalm_register_host",
@@ -329,6 +333,7 @@ EXPORTED = [
     "yalm_batch_generate_greedy", "yalm_batch_generate_sampled", "yalm_batch_state", "yalm_batch_set_launch",
     "yalm_batch_buffers", "yalm_batch_share_prefix", "yalm_attn_batch_prefix",
     "yalm_generate_speculative_model", "yalm_decoder_get_stream",
+    "yalm_decoder_set_kv_q8", "yalm_decoder_kv_q8", "yalm_decoder_get_kv_q8", "yalm_mha_q8",
 ]
 BATCH_ATTN_PER_SEQ = 1  # yalm_batch_set_launch
 BATCH_GUARD_BYTES = 256  # YALM_BATCH_GUARD_BYTES
@@ -397,6 +402,22 @@ def mha(kb, vb, q, head_dim, kv_len, max_seq_len, n_heads, n_kv_heads, att_init=
     check(lib.yalm_mha(_ptr(xout), _ptr(att), _ptr(kb), _ptr(vb), _ptr(q), head_dim, kv_len, max_seq_len, n_heads,
                        n_kv_heads))
     return xout, att
+
+
+def mha_q8(kb, vb, q, head_dim, kv_sink, kv_pos, kv_len, max_seq_len, n_heads, n_kv_heads, splits=0):
+    """yalm_mha_q8 (test hook): the q8 kv attention launch over the f16 caches kb / vb
+    (max_seq_len, n_kv_heads * head_dim), all rows quantised into a shadow first. Returns
+    (xout, kcodes, kscales, vcodes, vscales): the head outputs and the shadow as the launch left
+    it (codes uint8 (max_seq_len, n_kv_heads, head_dim), scales float32 (max_seq_len, n_kv_heads))."""
+    kb = np.ascontiguousarray(kb, dtype=np.float16).view(np.uint16)
+    vb = np.ascontiguousarray(vb, dtype=np.float16).view(np.uint16)
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    xout = np.zeros(n_heads * head_dim, np.float32)
+    kc, vc = (np.zeros((max_seq_len, n_kv_heads, head_dim), np.uint8) for _ in range(2))
+    ks, vs = (np.zeros((max_seq_len, n_kv_heads), np.float32) for _ in range(2))
+    check(lib.yalm_mha_q8(_ptr(xout), _ptr(kb), _ptr(vb), _ptr(q), _ptr(kc), _ptr(ks), _ptr(vc), _ptr(vs), head_dim,
+                          kv_sink, kv_pos, kv_len, max_seq_len, n_heads, n_kv_heads, splits))
+    return xout, kc, ks, vc, vs
 
 
 def argmax(logits: np.ndarray, n_shards: int = 1) -> int:
@@ -1090,6 +1111,27 @@ class Decoder:
     def set_launch(self, flags: int) -> None:
         """yalm_decoder_set_launch: LAUNCH_EAGER | LAUNCH_SYNC | LAUNCH_SEPARATE_ATTN_WO (0 = default)."""
         check(lib.yalm_decoder_set_launch(self.h, flags))
+
+    def set_kv_q8(self, on: bool = True) -> None:
+        """yalm_decoder_set_kv_q8: the decode attention reads the 8-bit shadow of the KV cache
+        (attention_q8.h). Only before the first position is written."""
+        check(lib.yalm_decoder_set_kv_q8(self.h, int(bool(on))))
+
+    @property
+    def kv_q8(self) -> bool:
+        return bool(lib.yalm_decoder_kv_q8(self.h))
+
+    def get_kv_q8(self, layer: int):
+        """One layer's f16 caches and their shadow: (k16, v16, kcodes, kscales, vcodes, vscales),
+        rows float16 and codes uint8 (max_seq_len, n_kv_heads, head_dim), scales float32
+        (max_seq_len, n_kv_heads)."""
+        c = self.cfg
+        shape = (c.max_seq_len, c.n_kv_heads, c.head_dim)
+        k16, v16 = (np.zeros(shape, np.float16) for _ in range(2))
+        kc, vc = (np.zeros(shape, np.uint8) for _ in range(2))
+        ks, vs = (np.zeros(shape[:2], np.float32) for _ in range(2))
+        check(lib.yalm_decoder_get_kv_q8(self.h, layer, _ptr(k16), _ptr(v16), _ptr(kc), _ptr(ks), _ptr(vc), _ptr(vs)))
+        return k16, v16, kc, ks, vc, vs
 
     def forward(self, token: int, pos: int, mode: int = OUTPUT_LOGITS):
         if mode == OUTPUT_LOGITS:
